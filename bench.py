@@ -7,13 +7,21 @@ batch 256 per GPU, d_hidden 256, 8 GNN layers; weak scaling: every rank gets its
 configs[3] at 8 GPUs).  Inputs are resident in HBM before the timed region; host-side graph
 construction stays outside it, as in the reference (data.py runs in DataLoader workers).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0) with the driver's fields plus `roofline` (dominant kernel, timed live
 with HIP events on the launch stream), `roofline_segreduce` (the HBM-bound aggregation kernel) and
 `cpu_baseline` (the CPU oracle — a port of the reference op sequence — timed on the host cores,
-rank 0, N=1 only).
+rank 0, N=1 only).  `ms_per_step` is the wall time of one of the K timed steps.
+
+Every step runs at learning rate 0 (Adam included): each one starts from the default init.
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step left to its caller, as DIR/<name>.npy:
+the loss vector train_step returns and a fixed, seeded sample of the parameters after the update,
+the step's gradient and the two Adam moments (see `dump_outputs`).  Inputs (batch, weights, eps,
+dropout seeds) depend only on the arguments, so two runs or two builds can be compared output for
+output; in the default mode they differ by the rounding of the float atomics.
 """
 import argparse
 import json
@@ -464,12 +472,49 @@ def preflight_collective(facts, dev, timeout_s=90.0):
     return seen
 
 
+DUMP_SAMPLE = 1 << 21              # elements kept per flat parameter-sized array (8 MB of float32)
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, trainer, vae, out):
+    """What the last timed `train_step` gave its caller, as float32 / float64 .npy files in `dirname`:
+    losses [pitch, dur, structure, kld] (float64, the returned tensor), BatchNorm running statistics (whole), and of the
+    parameters after the Adam update, the step's gradient and both Adam moments the same seeded sample of DUMP_SAMPLE flat
+    positions (sorted; the whole array when it is smaller).  Under 64 MB in all.  Runs after the timed region."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n = vae.flat_params.numel()
+    if n > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(pick).to(vae.flat_params.device)
+    else:
+        idx = None
+    arrays = {"losses": out.detach().double(), "buffers": vae.flat_buffers.detach()}
+    for name, t in (("params", vae.flat_params), ("grads", trainer.grads), ("adam_exp_avg", trainer.exp_avg),
+                    ("adam_exp_avg_sq", trainer.exp_avg_sq)):
+        arrays[name] = t.detach() if idx is None else t.detach()[idx]
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, total
+    return sorted(arrays)
+
+
 def stub_main(args):
     """`--stub-step` (tests only, no GPU, no HIP): the launcher, rendezvous, barrier / max-over-ranks timing and JSON
-    contract of the real bench with the training step replaced by a bucketed gloo all-reduce of a small CPU buffer."""
+    contract of the real bench with the training step replaced by a bucketed gloo all-reduce of a small CPU buffer.
+    The ranks never initialise HIP (no parallel.init_from_env: it sets the device; no dist.barrier(): it probes the
+    accelerator), so on a GPU machine they do not hold the device open."""
+    import datetime
     import torch.distributed as dist
     from polyphemus_amd import parallel
-    rank, local, world = parallel.init_from_env("gloo")
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
     flat = torch.full((1000,), float(rank + 1))
     gb = parallel.GradBuckets(flat, [300, 700])
 
@@ -486,12 +531,12 @@ def stub_main(args):
     timeline = gb.timeline()
     gb.trace = False
     if world > 1:
-        dist.barrier()
+        dist.all_reduce(torch.zeros(1))                   # (a barrier over gloo, on the host)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         scale = step()
     if world > 1:
-        dist.barrier()
+        dist.all_reduce(torch.zeros(1))                   # (a barrier over gloo, on the host)
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -522,7 +567,11 @@ def main():
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the `other_workloads` block of the default run")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torch.distributed.run: be the launcher (nothing above has touched the GPU)
         raise SystemExit(launch_ranks(sys.argv[1:], args.gpus))
@@ -554,8 +603,12 @@ def main():
     torch.manual_seed(0)
     vae = VAE(**cfg, device=dev).to(dev)
     vae.train()
-    tj = dict(peak_lr=1e-4, final_lr_scale=0.01, warmup_steps=8000, decay_steps=800000)      # training.json:19-24
-    trainer = HipTrainer(vae, lr=5e-6, betas=(0.9, 0.98), eps=1e-9, lr_scheduler=tj)        # training.json:11-18
+    # Every step is the full training step, Adam included, at learning rate 0: the Adam kernel reads and writes all of its
+    # state as at any rate, and every step starts from the same parameters.  With a rate, the float atomics of the default
+    # mode change the gradient's last bits from run to run, and Adam turns the sign of that noise in gradients that are
+    # zero in exact arithmetic (biases ahead of BatchNorm) into steps of the full rate: two runs on one fixed batch drift
+    # apart (0.5 % in the losses after 25 steps), and what the timed steps compute would depend on the run.
+    trainer = HipTrainer(vae, lr=0.0, betas=(0.9, 0.98), eps=1e-9)                        # betas, eps: training.json:11-18
     batch = synthetic_batch(args.batch, args.n_bars, p=0.25, seed=args.seed + rank, dense=args.dense).to(dev)
     n_nodes, n_edges, G = batch.num_nodes, batch.edge_index.shape[1], batch.s_tensor.shape[0]
 
@@ -675,6 +728,7 @@ def main():
         torch.distributed.all_reduce(tiles_all)
     elapsed = float(t.item())
     losses = trainer.losses_dict(out)
+    dumped = dump_outputs(args.dump_outputs, trainer, vae, out) if (args.dump_outputs and rank == 0) else None
     if world > 1:                                                # every rank must hold the same parameters after the run
         ck = vae.flat_params.double().sum().reshape(1)
         lo, hi = ck.clone(), ck.clone()
@@ -822,13 +876,15 @@ def main():
             "losses_first_step": ({k: round(v, 5) for k, v in losses_first.items()} if losses_first else None),
             "losses": {k: round(v, 5) for k, v in losses.items()},
             "losses_note": ("`losses_first_step`: step 1 from the default init (reproducible; pinned against the oracle in "
-                            "tests/test_fullsize_gpu.py).  `losses`: last of warmup + steps Adam steps on ONE fixed batch; "
-                            "the unweighted kld goes through a transient at beta = 0 that the fp64 oracle shows as well "
-                            "(tests/test_native_step_gpu.py::test_loss_trajectory_follows_the_fp64_oracle)"),
+                            "tests/test_fullsize_gpu.py).  `losses`: the last timed step's; every step runs at learning rate 0 "
+                            "from the default init on ONE fixed batch, with its own eps and message-dropout seeds"),
             "roofline": roof, "roofline_segreduce": roof_seg,
         }
         if dp is not None:
             line["dp"] = dp
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "sample_per_array": DUMP_SAMPLE,
+                                      "sample_seed": DUMP_SEED}
         default_run = (args.d, args.batch, args.n_bars, args.layers, args.dense) == (256, 256, 2, 8, False)
         if world == 1 and default_run and not args.no_other_workloads:
             # the other single-GPU configurations of BASELINE.json, so that the driver's record carries them (untimed part)

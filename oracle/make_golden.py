@@ -21,16 +21,30 @@ What is captured:
 
   <case>_generate.npz   the generation helpers (`_binary_from_logits`, `decoder(z, None)`, `mtp_from_logits`)
 
-Usage:  python oracle/make_golden.py [generate|d128]     (from the repo root; `generate` rewrites only <case>_generate.npz,
-        `d128` only the slim d = 128 case)
+  train_digests_mkl_compatible.json   `digests`: the SHA-256 (`tensor_digest`) of every train-mode tensor of the
+                  four cases above — outputs, gradients, state after each Adam step — and the loss values, captured on
+                  arithmetic every host reproduces: MKL's vendor-independent code path (MKL_CBWR=COMPATIBLE) for the
+                  products, and the fused CPU Adam (ATen's vectorised kernel, IEEE square root) for the update, since
+                  the square root of the default Adam goes through MKL's vector math, which rounds differently on
+                  Intel and AMD processors whatever the MKL settings.  The <case>.npz tensors are bit-exact on the
+                  capture host's default path only, and this model has gradients that are pure rounding noise (biases
+                  ahead of BatchNorm, the attention gate's bias), which Adam turns into full-size steps
+                  (tests/test_oracle_golden.py, two train steps).
+
+Usage:  python oracle/make_golden.py [generate|d128|bnoff|digests]     (from the repo root; `generate` rewrites only
+        <case>_generate.npz, `d128` only the slim d = 128 case, `digests` only train_digests_mkl_compatible.json)
 """
+import hashlib
 import json
 import os
 import sys
 import tempfile
 
-import numpy as np
-import torch
+if sys.argv[1:] == ["digests"]:
+    os.environ["MKL_CBWR"] = "COMPATIBLE"          # read by MKL at its first call: set before torch is imported
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
@@ -102,7 +116,16 @@ def build_batch(tmpdir, disk, n_bars):
     return Batch.from_data_list([ds[i] for i in range(len(ds))])
 
 
-def capture_case(name, cfg, batch_size, p, seed, corner=False, slim=False):
+def tensor_digest(a) -> str:
+    """SHA-256 of an array's dtype, shape and bytes (restated in tests/test_oracle_golden.py)."""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256()
+    h.update(f"{a.dtype.str}{a.shape}".encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def capture_case(name, cfg, batch_size, p, seed, corner=False, slim=False, write=True, fused_adam=False):
     rng = np.random.default_rng(seed)
     nb = cfg["n_bars"]
     disk = [disk_sample(rng, nb, p) for _ in range(batch_size)]
@@ -169,7 +192,7 @@ def capture_case(name, cfg, batch_size, p, seed, corner=False, slim=False):
         if isinstance(m, ref_model.GCL):
             m.dropout = 0.0
     tj = json.load(open(os.path.join(REF, "training.json")))
-    opt = torch.optim.Adam(vae.parameters(), **tj["optimizer"])          # train.py:181
+    opt = torch.optim.Adam(vae.parameters(), **tj["optimizer"], **({"fused": True} if fused_adam else {}))   # train.py:181
     sched = ref_training.ExpDecayLRScheduler(optimizer=opt, **tj["lr_scheduler"])
     trainer = ref_training.PolyphemusTrainer("unused", vae, opt, lr_scheduler=sched)
     trainer.beta = 0                                                     # training.py:116
@@ -206,12 +229,15 @@ def capture_case(name, cfg, batch_size, p, seed, corner=False, slim=False):
         s_logits, c_logits, mu, lv = fwd(vae, graph)
         _, ev_losses = trainer._losses(graph.s_tensor, s_logits, graph.c_tensor, c_logits, mu, lv)
         accs = trainer._accuracies(graph.s_tensor, s_logits, graph.c_tensor, c_logits, graph.is_drum)
+    if not write:
+        return out
     np.savez_compressed(os.path.join(OUT, f"{name}_metrics.npz"), accs=np.array(json.dumps(accs)),
                         losses=np.array(json.dumps(ev_losses)))
     np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **out)
     print(f"{name}_metrics.npz: {accs}")
     print(f"{name}.npz: N={int(graph.num_nodes)} E={graph.edge_index.shape[1]} "
           f"params={sum(q.numel() for q in vae.parameters())} losses={losses}")
+    return out
 
 
 def capture_generation(name):
@@ -263,19 +289,48 @@ def capture_generation(name):
           f"corner on={int(out['corner/s_binary'].sum())}")
 
 
+CASES = {
+    "lmd2_tiny": dict(cfg=dict(dropout=0, batch_norm=True, gnn_n_layers=2, d=32, n_bars=2, resolution=8),
+                      batch_size=8, p=0.06, seed=11, corner=True),
+    "nb3_tiny": dict(cfg=dict(dropout=0, batch_norm=True, gnn_n_layers=1, d=16, n_bars=3, resolution=8),
+                     batch_size=6, p=0.05, seed=12),
+    # a model built with batch_norm = False (model.py:176-188: no norm layers in the GCNs; :218-238,278-292: CNNs without
+    # BatchNorm2d, so the Sequential indices of the second convolutions shift): state_dict keys and arithmetic of that
+    # constructor switch, pinned to the reference
+    "bnoff_tiny": dict(cfg=dict(dropout=0, batch_norm=False, gnn_n_layers=2, d=16, n_bars=2, resolution=8),
+                       batch_size=5, p=0.08, seed=14),
+    # d = 128 (a multiple of 128: the GCL forward and input-gradient products of the native step take the B-direct
+    # planes GEMM, the weight gradient the planes TN kernel) — the variant bench.py measures, pinned to the reference
+    "d128_l2": dict(cfg=dict(dropout=0, batch_norm=True, gnn_n_layers=2, d=128, n_bars=2, resolution=8),
+                    batch_size=4, p=0.2, seed=13, slim=True),
+}
+
+
 def capture_bnoff():
-    """A model built with batch_norm = False (model.py:176-188: no norm layers in the GCNs; :218-238,278-292: CNNs without
-    BatchNorm2d, so the Sequential indices of the second convolutions shift): state_dict keys and arithmetic of that
-    constructor switch, pinned to the reference."""
-    capture_case("bnoff_tiny", dict(dropout=0, batch_norm=False, gnn_n_layers=2, d=16, n_bars=2, resolution=8),
-                 batch_size=5, p=0.08, seed=14)
+    capture_case("bnoff_tiny", **CASES["bnoff_tiny"])
 
 
 def capture_d128():
-    """d = 128 (a multiple of 128: the GCL forward and input-gradient products of the native step take the B-direct
-    planes GEMM, the weight gradient the planes TN kernel) — the variant bench.py measures, pinned to the reference."""
-    capture_case("d128_l2", dict(dropout=0, batch_norm=True, gnn_n_layers=2, d=128, n_bars=2, resolution=8),
-                 batch_size=4, p=0.2, seed=13, slim=True)
+    capture_case("d128_l2", **CASES["d128_l2"])
+
+
+def capture_digests():
+    """train_digests_mkl_compatible.json (run as its own process: MKL_CBWR is set above, before torch is imported)."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE"
+    rec = {"_capture": {"MKL_CBWR": "COMPATIBLE", "threads": 1, "adam": "fused"}}
+    for name, args in CASES.items():
+        out = capture_case(name, **args, write=False, fused_adam=True)
+        r = {}
+        for k, v in out.items():
+            if not k.startswith("train") or k.endswith(("/lr", "/grad_none")):
+                continue
+            r[k] = json.loads(str(v)) if k.endswith("/losses") else tensor_digest(v)
+        rec[name] = r
+    path = os.path.join(OUT, "train_digests_mkl_compatible.json")
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{path}: {sum(len(r) for r in rec.values())} entries")
 
 
 if __name__ == "__main__":
@@ -290,11 +345,12 @@ if __name__ == "__main__":
         capture_generation("lmd2_tiny")
         capture_generation("nb3_tiny")
         sys.exit(0)
+    if sys.argv[1:] == ["digests"]:
+        capture_digests()
+        sys.exit(0)
     make_graphs()
-    capture_case("lmd2_tiny", dict(dropout=0, batch_norm=True, gnn_n_layers=2, d=32, n_bars=2, resolution=8),
-                 batch_size=8, p=0.06, seed=11, corner=True)
-    capture_case("nb3_tiny", dict(dropout=0, batch_norm=True, gnn_n_layers=1, d=16, n_bars=3, resolution=8),
-                 batch_size=6, p=0.05, seed=12)
+    capture_case("lmd2_tiny", **CASES["lmd2_tiny"])
+    capture_case("nb3_tiny", **CASES["nb3_tiny"])
     capture_generation("lmd2_tiny")
     capture_generation("nb3_tiny")
     capture_d128()

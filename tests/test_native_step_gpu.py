@@ -464,8 +464,8 @@ def test_gcl_kernels_match_the_segment_reduce_plus_grouped_product_step(d, L):
 
 
 def test_loss_trajectory_follows_the_fp64_oracle():
-    """bench.py trains ONE fixed synthetic batch with training.json's optimizer (Adam, lr 1e-4 in the warm-up
-    of the schedule the bench uses, beta = 0) and prints the last step's losses; the unweighted KLD goes through a
+    """training ONE fixed synthetic batch with training.json's optimizer (Adam, lr 1e-4 in the warm-up of its
+    schedule, beta = 0; what bench.py ran before its steps went to learning rate 0), the unweighted KLD goes through a
     transient of several orders of magnitude in the first steps.  Is that the model or a fault of the HIP path (which
     shares its BatchNorm, loss and Adam kernels between all kernel sets)?  Six steps of oracle/vae_cpu.py in fp64 with
     stock torch Adam on the same batch, weights, eps and schedule, message dropout off (so that both paths see the same
@@ -484,7 +484,7 @@ def test_loss_trajectory_follows_the_fp64_oracle():
     vae.msg_dropout = 0.0
     sd = {k: v.detach().cpu().clone() for k, v in vae.state_dict().items()}
     names = [n for n, _ in vae.named_parameters()]
-    tj = dict(peak_lr=1e-4, final_lr_scale=0.01, warmup_steps=8000, decay_steps=800000)        # as bench.py (training.json:19-24)
+    tj = dict(peak_lr=1e-4, final_lr_scale=0.01, warmup_steps=8000, decay_steps=800000)        # training.json:19-24
     tr = HipTrainer(vae, lr=5e-6, betas=(0.9, 0.98), eps=1e-9, lr_scheduler=tj)
     gen = torch.Generator().manual_seed(7)
     eps = [torch.randn(B, d, generator=gen) for _ in range(6)]

@@ -233,6 +233,7 @@ def test_bench_preflight_names_what_keeps_the_communicator_from_forming(monkeypa
                  ("MASTER_PORT", "29999")):
         monkeypatch.setenv(k, v)
     monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 0)   # a box with no visible GPU, whatever this host has
     facts = bench.preflight("gloo")                               # gloo: nothing to object to on a CPU box
     assert facts["world_size"] == 2 and facts["rank"] == 1 and facts["device_count"] == 0
     with pytest.raises(SystemExit) as e:                          # nccl with no visible GPU: one rank per device is impossible
