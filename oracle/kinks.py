@@ -27,19 +27,75 @@ from . import vae_cpu
 
 
 class _FProxy:
-    """torch.nn.functional with `relu` replaced (installed as vae_cpu.F for the duration of a probe)."""
+    """torch.nn.functional with `relu` replaced (installed as vae_cpu.F for the duration of a probe); `msg_relu_site` is what
+    the edge-chunked aggregation of vae_cpu (`_MsgMean`) takes a message ReLU site's decisions from."""
 
-    def __init__(self, relu):
+    def __init__(self, relu, msg_relu_site):
         self.relu = relu
+        self.msg_relu_site = msg_relu_site
 
     def __getattr__(self, k):
         return getattr(_F, k)
 
 
+class _ChunkSite:
+    """One message ReLU site of vae_cpu's edge-chunked aggregation, seen by a ReluProbe: the decisions of rows
+    [r0, r0 + len) of the site's [E_r, d] pre-activation, evaluated chunk by chunk (forced, flipped or relu's own), with
+    the probe's bookkeeping (`disagree`, `pre`) accumulated over the chunks of the forward pass (`record`)."""
+
+    def __init__(self, probe, i):
+        self.probe, self.i = probe, i
+        self.forced = probe.forced.get(i)
+        self.flips = probe.flips.get(i)
+        self.pre = []
+        if self.forced is not None:
+            probe.disagree[i] = 0
+
+    def __call__(self, pre, r0, record):
+        own = pre > 0
+        rows = torch.arange(r0, r0 + pre.shape[0], device=pre.device)
+        if self.forced is not None:
+            mask = _forced_rows(self.forced, rows, pre).to(pre.device)
+            if record:
+                self.probe.disagree[self.i] += int((mask != own).sum())
+        elif self.flips is not None:
+            d = pre.shape[1]
+            idx = self.flips.to(pre.device)
+            idx = idx[(idx >= r0 * d) & (idx < (r0 + pre.shape[0]) * d)] - r0 * d
+            mask = own.clone()
+            flat = mask.reshape(-1)
+            flat[idx] = ~flat[idx]
+        else:
+            mask = own
+        if record and self.probe.keep:
+            self.pre.append(pre.detach().cpu().clone())
+        return mask
+
+    def finish(self):
+        if self.probe.keep:
+            d = self.pre[0].shape[1] if self.pre else 0
+            self.probe.pre.append(torch.cat(self.pre) if self.pre else torch.zeros(0, d, dtype=torch.float64))
+
+
+def _forced_rows(forced, rows, pre):
+    """rows `rows` of a forced site's decisions: a materialised bool tensor of the site's shape, or lazily a callable
+    (row ids of the site -> bool mask [len(rows), d])"""
+    if callable(forced):
+        mask = forced(rows)
+    else:
+        mask = forced[rows.to(forced.device)]
+    assert mask.shape == pre.shape, (tuple(mask.shape), tuple(pre.shape))
+    return mask
+
+
 class ReluProbe:
     """Context manager: records the pre-activations of every ReLU the oracle executes (call order = site index) and
     inverts the decisions listed in `flips` {site: LongTensor of flat element indices}; `forced` {site: bool tensor of the
-    site's shape} replaces a site's decisions altogether (relu(x) becomes x * mask: the decisions another implementation took)."""
+    site's shape} replaces a site's decisions altogether (relu(x) becomes x * mask: the decisions another implementation took).
+    A message site (oracle/vae_cpu.gcl_forward's relu(x_j * w) of one relation) may be forced lazily instead, by a callable
+    (row ids of the site's [E_r, d] pre-activation, i.e. positions in the relation's edge list -> bool mask [rows, d]): it is
+    evaluated on every row at once on the default path, chunk by chunk on the edge-chunked one (vae_cpu.chunked_aggregation).
+    Both paths number the sites alike."""
 
     def __init__(self, flips: Optional[Dict[int, torch.Tensor]] = None, keep: bool = True,
                  forced: Optional[Dict[int, torch.Tensor]] = None):
@@ -50,14 +106,21 @@ class ReluProbe:
         self.pre: List[torch.Tensor] = []
         self.count = 0
 
+    def msg_site(self):
+        i = self.count
+        self.count += 1
+        return _ChunkSite(self, i)
+
     def _relu(self, x, *a, **k):
         i = self.count
         self.count += 1
         if self.keep:
             self.pre.append(x.detach().clone())
         if i in self.forced:
-            mask = self.forced[i]
+            forced = self.forced[i]
+            mask = _forced_rows(forced, torch.arange(x.shape[0]), x) if callable(forced) else forced
             assert mask.shape == x.shape, (i, tuple(mask.shape), tuple(x.shape))
+            mask = mask.to(x.device)
             self.disagree[i] = int((mask != (x.detach() > 0)).sum())
             return x * mask.to(x.dtype)
         if i not in self.flips:
@@ -70,7 +133,7 @@ class ReluProbe:
 
     def __enter__(self):
         self._saved = vae_cpu.F
-        vae_cpu.F = _FProxy(self._relu)
+        vae_cpu.F = _FProxy(self._relu, self.msg_site)
         return self
 
     def __exit__(self, *exc):

@@ -18,6 +18,9 @@ checks every output, loss, gradient, buffer and Adam-updated parameter.  The
 real torch_geometric 2.0.2 is not installable here, so the residual risk is the
 shim's fidelity to PyG — stated in DESIGN.md.
 
+`chunked_aggregation` (off by default) runs the GCL message + scatter-mean edge-chunked in bounded memory, for graphs whose
+per-edge tensors would not fit (one GPU's configs[4] shard); tests/test_oracle_chunked.py pins it to the default path.
+
 Every function cites the reference lines it follows (`/root/reference/...`).
 """
 from __future__ import annotations
@@ -100,16 +103,149 @@ def gcl_forward(x, edge_index, edge_type, edge_attr, P: Params, key: str, traini
     return out
 
 
+# ---- the same aggregation in bounded memory (off by default: `chunked_aggregation`) ---------------------------------------
+# `gcl_forward` builds per-edge tensors (x_j, w, msg, the dropout mask and autograd's copies of them): E_r x d each, 8.5 GB
+# in fp64 at the 2.08 M edges of one GPU's configs[4] shard.  With EDGE_CHUNK set, `gcn_forward` runs the message +
+# scatter-mean of every relation through `_MsgMean`, which keeps only x, the per-distance table T and the index vectors and
+# evaluates the edges EDGE_CHUNK at a time (the backward recomputes each chunk) on EDGE_DEVICE; everything else — the
+# products with W_r, root, bias, the norms — stays on the caller's device as above.
+EDGE_CHUNK: Optional[int] = None
+EDGE_DEVICE: Optional[torch.device] = None
+
+
+class chunked_aggregation:
+    """Context manager: GCL aggregations of `gcn_forward` edge-chunked (`chunk` edges at a time, on `device`)."""
+
+    def __init__(self, chunk: int, device=None):
+        assert chunk >= 1
+        self.chunk, self.device = int(chunk), device
+
+    def __enter__(self):
+        global EDGE_CHUNK, EDGE_DEVICE
+        self._saved = (EDGE_CHUNK, EDGE_DEVICE)
+        EDGE_CHUNK, EDGE_DEVICE = self.chunk, self.device
+        return self
+
+    def __exit__(self, *exc):
+        global EDGE_CHUNK, EDGE_DEVICE
+        EDGE_CHUNK, EDGE_DEVICE = self._saved
+        return False
+
+
+def _msg_site():
+    """The ReLU decisions of one message site: None = relu's own; under oracle/kinks.ReluProbe a per-chunk decider
+    (`ReluProbe.msg_site`), created here so that the site takes its place in the probe's call order."""
+    site = getattr(F, "msg_relu_site", None)
+    return site() if site is not None else None
+
+
+class _MsgMean(torch.autograd.Function):
+    """h[n] = sum_{e: dst_e = n} keep_e * relu(x[src_e] * T[dist_e]) / (1 - p)  /  clamp(count_n, 1)   (model.py:123-135),
+    over the edges of one relation in chunks of `chunk`; T is F.linear(onehot, nn.weight, nn.bias)[:, :d], i.e. row dist_e
+    of it is w_e.  Saves x, T and the index vectors only: the backward recomputes every chunk and scatters dx onto the
+    sources, dT onto the distance ids."""
+
+    @staticmethod
+    def forward(ctx, x, T, e, drop_p, keep_fn, site, chunk, device):
+        ctx.save_for_backward(x, T)
+        ctx.e, ctx.drop_p, ctx.keep_fn, ctx.site, ctx.chunk, ctx.device = e, drop_p, keep_fn, site, chunk, device
+        xd, Td = x.to(device), T.to(device)
+        h = torch.zeros(x.shape[0], x.shape[1], dtype=x.dtype, device=device)
+        for r0, msg, _ in _MsgMean._chunks(ctx, xd, Td, record=True):
+            h.index_add_(0, e["dst"][r0:r0 + msg.shape[0]], msg)             # scatter-sum onto dst
+        if site is not None:
+            site.finish()
+        return (h / e["cnt"].clamp(min=1).unsqueeze(1)).to(x.device)        # reduce='mean'
+
+    @staticmethod
+    def _chunks(ctx, xd, Td, record):
+        """(first row, message, d message / d pre-activation) of every chunk, recomputed identically on every call"""
+        e, p = ctx.e, ctx.drop_p
+        for r0 in range(0, e["src"].shape[0], ctx.chunk):
+            r1 = min(r0 + ctx.chunk, e["src"].shape[0])
+            pre = xd.index_select(0, e["src"][r0:r1]) * Td.index_select(0, e["dist"][r0:r1])
+            mask = pre > 0 if ctx.site is None else ctx.site(pre, r0, record)
+            msg = pre * mask.to(pre.dtype)                                     # relu (or the decisions imposed on it)
+            scale = mask.to(pre.dtype)
+            if p > 0:
+                keep = ctx.keep_fn(e["eids"][r0:r1], pre.shape[1]).to(device=pre.device, dtype=pre.dtype)
+                msg = msg * keep / (1.0 - p)
+                scale = scale * keep / (1.0 - p)
+            yield r0, msg, scale
+
+    @staticmethod
+    def backward(ctx, gh):
+        x, T = ctx.saved_tensors
+        e, dev = ctx.e, ctx.device
+        xd, Td = x.to(dev), T.to(dev)
+        gm = gh.to(dev) / e["cnt"].clamp(min=1).unsqueeze(1)
+        dx, dT = torch.zeros_like(xd), torch.zeros_like(Td)
+        for r0, msg, scale in _MsgMean._chunks(ctx, xd, Td, record=False):
+            r1 = r0 + msg.shape[0]
+            src, dist = e["src"][r0:r1], e["dist"][r0:r1]
+            gpre = gm.index_select(0, e["dst"][r0:r1]) * scale
+            dx.index_add_(0, src, gpre * Td.index_select(0, dist))
+            # dT onto the (<= 32) distance ids as a one-hot product: index_add_ onto 32 rows serialises on a GPU's atomics
+            onehot = F.one_hot(dist, Td.shape[0]).to(gpre.dtype)
+            dT.addmm_(onehot.T, gpre * xd.index_select(0, src))
+        return dx.to(x.device), dT.to(T.device), None, None, None, None, None, None
+
+
+def gcl_edges(edge_index, edge_type, edge_attr, N: int, dtype, device=None):
+    """Per relation the index vectors `_MsgMean` works from (source, destination, distance id, global edge id, in the edge
+    order of `gcl_forward`'s boolean selection) and the in-degree, on `device`.  The table form of w relies on exactly
+    one-hot distance attributes: asserted."""
+    assert edge_attr.dim() == 2 and bool(((edge_attr == 0) | (edge_attr == 1)).all()) and bool((edge_attr.sum(1) == 1).all()), \
+        "edge_attr is not one-hot"
+    dist = edge_attr.argmax(1)
+    eids = torch.arange(edge_index.shape[1])
+    out = []
+    for r in range(N_REL):
+        m = edge_type == r
+        e = {"src": edge_index[0, m], "dst": edge_index[1, m], "dist": dist[m], "eids": eids[m]}
+        e = {k: v.to(device) for k, v in e.items()}
+        e["cnt"] = torch.zeros(N, dtype=dtype, device=device).index_add_(
+            0, e["dst"], torch.ones(e["dst"].shape[0], dtype=dtype, device=device))
+        out.append(e)
+    return out
+
+
+def gcl_forward_chunked(x, edges, n_dist: int, P: Params, key: str, training: bool, msg_dropout: float,
+                        keep_mask: Optional[Callable] = None, chunk: int = 65536, device=None):
+    """`gcl_forward` with each relation's aggregation through `_MsgMean` (edges from `gcl_edges`); same quantity, the
+    per-relation products, root and bias unchanged (model.py:103-119)."""
+    N, d = x.shape
+    device = x.device if device is None else torch.device(device)
+    T = F.linear(torch.eye(n_dist, dtype=x.dtype), P[key + ".nn.weight"], P[key + ".nn.bias"])[:, :d]  # w_e = T[dist_e]
+    drop = msg_dropout if training else 0.0
+    if drop > 0:
+        assert keep_mask is not None, "the chunked aggregation replays message dropout from keep_mask only"
+    keep_fn = (lambda eids, dd: keep_mask(key, eids, dd)) if drop > 0 else None
+    out = torch.zeros(N, P[key + ".weight"].shape[2], dtype=x.dtype)
+    for r in range(N_REL):
+        h = _MsgMean.apply(x, T, edges[r], drop, keep_fn, _msg_site(), chunk, device)
+        out = out + h @ P[key + ".weight"][r]                              # model.py:112
+    out = out + x @ P[key + ".root"]                                       # model.py:116
+    out = out + P[key + ".bias"]                                           # model.py:119
+    return out
+
+
 def gcn_forward(x, graph, P: Params, key: str, cfg, training: bool, msg_dropout: float,
                 keep_mask=None):
     """`GCN.forward` (model.py:190-208)."""
     edge_index, edge_attrs = graph.edge_index, graph.edge_attrs
     edge_type, edge_attr = edge_attrs[:, 0], edge_attrs[:, 1:]             # model.py:193-194
+    if EDGE_CHUNK is not None:
+        edges = gcl_edges(edge_index, edge_type, edge_attr, x.shape[0], x.dtype, EDGE_DEVICE)
     for i in range(cfg["gnn_n_layers"]):
         residual = x
         x = _drop(x, cfg["dropout"], training, f"{key.split('.')[0][:3]}_gcn.{i}")     # model.py:199
-        x = gcl_forward(x, edge_index, edge_type, edge_attr, P, f"{key}.layers.{i}", training,
-                        msg_dropout, keep_mask)
+        if EDGE_CHUNK is not None:
+            x = gcl_forward_chunked(x, edges, edge_attr.shape[1], P, f"{key}.layers.{i}", training, msg_dropout,
+                                    keep_mask, EDGE_CHUNK, EDGE_DEVICE)
+        else:
+            x = gcl_forward(x, edge_index, edge_type, edge_attr, P, f"{key}.layers.{i}", training,
+                            msg_dropout, keep_mask)
         if cfg["batch_norm"]:
             x = _bn(x, P, f"{key}.norm_layers.{i}.module", training)       # model.py:203
         x = F.relu(x)

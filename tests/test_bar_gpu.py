@@ -162,11 +162,11 @@ def test_bar_backward_matches_autograd_of_the_reference_op_chain():
 
 
 def test_bar_kernels_at_the_dense_shards_real_size():
-    """configs[4], one GPU's shard at its REAL size (B = 64: N = 16,384 nodes, E = 2.08 M edges, d = 512, message dropout on) —
-    too large for the CPU oracle's per-edge fp64 tensors, not for a kernel-level comparison: the bar-resident forward gives the
-    row-gather kernel's planes bit for bit, the pair-format planes decode to them within 2^-21 of |max|, and the backward (with the
-    norm sums of the layer below) agrees with `pm_segreduce_bwd_norm` to 2e-6 — the kernels tests/test_kernels_gpu.py pins to the
-    torch restatement of GCL.message + scatter-mean (model.py:110,123-135)."""
+    """configs[4], one GPU's shard at its REAL size (B = 64: N = 16,384 nodes, E = 2.08 M edges, d = 512, message dropout on),
+    kernel against kernel (the whole step against the fp64 oracle at this size: tests/test_fullsize_gpu.py): the bar-resident
+    forward gives the row-gather kernel's planes bit for bit, the pair-format planes decode to them within 2^-21 of |max|, and
+    the backward (with the norm sums of the layer below) agrees with `pm_segreduce_bwd_norm` to 2e-6 — the kernels
+    tests/test_kernels_gpu.py pins to the torch restatement of GCL.message + scatter-mean (model.py:110,123-135)."""
     b, plan = make_plan(synthetic_batch(64, 2, seed=1234, dense=True))
     N, d, p = plan.N, 512, 0.1
     assert N == 16384 and plan.E == 2080768

@@ -85,6 +85,42 @@ def dropout_keep_np(seed, layer_uid, eids, d, p):
     return ((h >> np.uint64(8)) >= thresh).astype(np.float32)
 
 
+def _mul32(x, k):
+    """(x * k) mod 2^32 for int64 x, k in [0, 2^32) (k an int or a tensor): in two 16-bit halves of k, so that no product
+    leaves int64"""
+    return (x * (k & 0xFFFF) + (((x * (k >> 16)) & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+
+def _mix32_t(x):
+    x = x ^ (x >> 16); x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15); x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+_LANE = (1, 0x9E3779B1, 0x85EBCA77, 0xC2B2AE3D)
+
+
+def dropout_hash_torch(seed, layer_uid, eids, d):
+    """pm_dropout_hash(seed, layer, eid, channel) (the top 24 bits of the element hash, csrc/common.h) for every edge id of
+    `eids` (int64, any device) and channel < d, in torch on int64 with 32-bit masking: [len(eids), d] int64."""
+    eids = torch.as_tensor(eids, dtype=torch.int64)
+    dev = eids.device
+    k0 = _mix32_t(torch.tensor([(seed & 0xFFFFFFFF) ^ (((layer_uid + 1) * 0x9E3779B9) & 0xFFFFFFFF)], dtype=torch.int64, device=dev))
+    ek = _mix32_t(k0 ^ ((_mul32(eids & 0xFFFFFFFF, 0x85EBCA6B) + 0x27D4EB2F) & 0xFFFFFFFF))
+    ch = torch.arange(d, dtype=torch.int64, device=dev)
+    grp = _mul32(ch >> 2, 0xC2B2AE35)                                               # one mix per 4 channels,
+    lane = torch.tensor(_LANE, dtype=torch.int64, device=dev)[ch & 3]               # times a per-lane odd constant
+    return _mul32(_mix32_t((ek[:, None] + grp[None, :]) & 0xFFFFFFFF), lane[None, :]) >> 8
+
+
+def dropout_keep_torch(seed, layer_uid, eids, d, p):
+    """`dropout_keep_np` from `dropout_hash_torch`, on the device of `eids`: float32 0/1 [len(eids), d], bit for bit the same
+    mask.  What the edge-chunked oracle evaluates per chunk, where numpy's single thread over 1e9 elements per layer would
+    dominate the test."""
+    thresh = int(np.float32(p) * np.float32(16777216.0))
+    return (dropout_hash_torch(seed, layer_uid, eids, d) >= thresh).to(torch.float32)
+
+
 def layer_uid_of(key: str) -> int:
     """GCL parameter prefix -> layer uid used by the HIP path (encoder GCN 0.., decoder GCN 1000..)."""
     base = 0 if key.startswith("encoder.") else 1000
@@ -250,8 +286,14 @@ FULLSIZE = {
 SMALLSIZE = {
     "small_b24_d128_l3": dict(B=24, nb=2, d=128, L=3, p=0.25, dense=False, msg_p=0.1, seed=31),
 }
-# one GPU's shard of configs[4] at its real size (B = 64: N = 16,384 nodes, 2.08 M edges): too large for the oracle's
-# per-edge fp64 tensors — property checks only (tests/test_fullsize_gpu.py)
+# configs[4]'s dense shard at B = 8 with message dropout on: the dense route's dropout stream against the oracle under the
+# step's ReLU decisions (test_gradient_is_the_fp64_oracles_under_the_relu_decisions_the_step_took only: no GRAD_CAPS entry)
+FORCED_ONLY = {
+    "configs4_dense_shard_b8_d512_msg_p01": dict(B=8, nb=2, d=512, L=8, p=1.0, dense=True, msg_p=0.1, seed=1234),
+}
+# one GPU's shard of configs[4] at its real size (B = 64: N = 16,384 nodes, 2.08 M edges): against the fp64 oracle through
+# its edge-chunked aggregation (vae_cpu.chunked_aggregation: the per-edge fp64 tensors of the default path take 8.5 GB each)
+# under the step's ReLU decisions, and property checks (tests/test_fullsize_gpu.py)
 DENSE_SHARD_B64 = dict(B=64, nb=2, d=512, L=8, p=1.0, dense=True, msg_p=0.1, seed=1234)
 
 
@@ -317,15 +359,20 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     return out
 
 
-def oracle_fullsize(spec, run, dtypes=(("o64", torch.float64), ("o32", torch.float32))):
+def oracle_fullsize(spec, run, dtypes=(("o64", torch.float64), ("o32", torch.float32)), chunk=None, device=None):
     """oracle/vae_cpu.py on what `hip_fullsize_step` ran (same weights, eps and — replayed from the counter hash — the
-    same message-dropout mask), per dtype: (outputs, losses, gradients), and the seconds each took."""
+    same message-dropout mask), per dtype: (outputs, losses, gradients), and the seconds each took.  With `chunk` the GCL
+    aggregations run edge-chunked on `device` (vae_cpu.chunked_aggregation) and the dropout masks are evaluated per chunk
+    there (`dropout_keep_torch`, nothing cached)."""
+    import contextlib
     import time
     from oracle import vae_cpu
     cfg, cpu, sd, names, eps, seeds = (run[k] for k in ("cfg", "cpu", "sd", "names", "eps", "seeds"))
     masks = {}
 
     def keep(key, eids, dd):
+        if chunk is not None:
+            return dropout_keep_torch(seeds[key.split(".")[0]], layer_uid_of(key), eids, dd, spec["msg_p"])
         k = (key, dd, eids.numel(), int(eids[0]) if eids.numel() else -1, int(eids[-1]) if eids.numel() else -1)
         if k not in masks:
             masks[k] = torch.from_numpy(dropout_keep_np(seeds[key.split(".")[0]], layer_uid_of(key), eids.numpy(), dd, spec["msg_p"]))
@@ -336,8 +383,10 @@ def oracle_fullsize(spec, run, dtypes=(("o64", torch.float64), ("o32", torch.flo
         t0 = time.time()
         P, _ = vae_cpu.split_state({k: (v.to(dt) if v.dtype.is_floating_point else v.clone()) for k, v in sd.items()}, names)
         opt = torch.optim.SGD([P[n] for n in names], lr=0.0)
-        outs, parts, grads = vae_cpu.train_step(_as_dtype(cpu, dt), P, names, cfg, opt, eps.to(dt), msg_dropout=spec["msg_p"],
-                                                keep_mask=(lambda key, eids, dd, _dt=dt: keep(key, eids, dd).to(_dt)) if spec["msg_p"] > 0 else None)
+        keep_mask = (lambda key, eids, dd, _dt=dt: keep(key, eids, dd).to(_dt)) if spec["msg_p"] > 0 else None
+        with (vae_cpu.chunked_aggregation(chunk, device) if chunk is not None else contextlib.nullcontext()):
+            outs, parts, grads = vae_cpu.train_step(_as_dtype(cpu, dt), P, names, cfg, opt, eps.to(dt), msg_dropout=spec["msg_p"],
+                                                    keep_mask=keep_mask)
         res[tag] = (dict(zip(("s_logits", "c_logits", "mu", "log_var"), (o.detach() for o in outs))),
                     {k: float(v.detach()) for k, v in parts.items()}, grads)
         times[tag] = time.time() - t0
@@ -422,14 +471,30 @@ def saved_tensor(step, what: str, stack: int = 0, layer: int = 0) -> torch.Tenso
     return step.ws[off.value:off.value + 4 * n.value].view(torch.float32)
 
 
-def hip_relu_decisions(live, cfg):
+class LazyMsgDecisions:
+    """The decisions of one message ReLU site, evaluated on demand: (x[src] * T[dist]) > 0 over the rows (positions in the
+    relation's edge list) asked for, from the layer input and distance table the step saved (copied out of its arena) —
+    what oracle/kinks.ReluProbe.forced takes in place of a materialised [E_r, d] mask."""
+
+    def __init__(self, x, T, src, dist):
+        self.x, self.T, self.src, self.dist = x, T, src, dist
+        self.shape = torch.Size((src.shape[0], x.shape[1]))
+
+    def __call__(self, rows):
+        rows = rows.to(self.src.device)
+        return (self.x.index_select(0, self.src[rows]) * self.T.index_select(0, self.dist[rows])) > 0
+
+
+def hip_relu_decisions(live, cfg, lazy=False):
     """The ReLU decisions the BACKWARD of the native step just run on `live` (hip_fullsize_step(..., lr=0, keep=live)) took,
     keyed by the oracle's site index (oracle/kinks.relu_sites): per GCL layer the six per-relation message ReLUs
     (x[src] * T[dist] > 0 from the saved layer input and distance table: segreduce.hip k_segreduce_bwd) and the ReLU behind the
     norm (pm_bn_relu_decisions = the expression of pm_bn_bwd_elem on the saved pre-norm rows and batch statistics), the chord
     encoder's ReLU (its saved output > 0: pm_relu_bwd), the two head norms, CNNEncoder.lin[1].  Not imposed: the two
     BatchNorm2d ReLUs and the max-pool of the structure encoder's convolutions (0.8 M elements against 67 M), the structure
-    decoder (the reference's loss sends no gradient there)."""
+    decoder (the reference's loss sends no gradient there).  lazy=True: the message sites as LazyMsgDecisions over copies
+    (on the device) of each layer's saved input and of the distance tables — 32 MB per layer at N = 16,384, d = 512, where
+    the materialised masks would take 1 GB per layer."""
     import ctypes
     from oracle import kinks
     from polyphemus_amd._lib import call, ptr, stream
@@ -449,11 +514,16 @@ def hip_relu_decisions(live, cfg):
     et, ed, src = g.edge_type.long(), g.edge_dist.long(), g.edge_index[0].long()
     for stack, (tag, key) in enumerate((("enc_gcn", "encoder.c_encoder.graph_encoder"), ("dec_gcn", "decoder.c_decoder.graph_decoder"))):
         T = saved_tensor(step, "GCN_T", stack).view(32, d)
+        if lazy:
+            T = T.clone()
         for i in range(L):
             x = saved_tensor(step, "GCN_XIN", stack, i).view(N, d)
+            if lazy:
+                x = x.clone()
             for r in range(6):
                 m = et == r
-                forced[sites.index(f"{tag}.{i}.msg.{r}")] = ((x[src[m]] * T[ed[m]]) > 0).cpu()
+                forced[sites.index(f"{tag}.{i}.msg.{r}")] = (LazyMsgDecisions(x, T, src[m], ed[m]) if lazy else
+                                                             ((x[src[m]] * T[ed[m]]) > 0).cpu())
             forced[sites.index(f"{tag}.{i}.norm")] = bn_mask(saved_tensor(step, "GCN_H", stack, i), saved_tensor(step, "GCN_MEAN", stack, i),
                                                              saved_tensor(step, "GCN_VAR", stack, i), f"{key}.norm_layers.{i}.module", N, d)
     x0 = saved_tensor(step, "X0").view(N, d) > 0
