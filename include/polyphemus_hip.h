@@ -58,8 +58,10 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   route's product in the fp16 pair format; pm_h2_clamp_events: saturation counter of the pair format; PmBatch.flags bit 3 and
  *   pm_vae_step_output_views: the drop-in module's outputs and gradients as views of the arena;
  *   pm_unembed_row_lists / pm_unembed_ce_rows / pm_unembed_dh_rows: the decoder head without its PAD-target rows;
- *   pm_unembed_dw: the three un-embedding weight gradients in one launch). */
-#define PM_ABI_VERSION 8
+ *   pm_unembed_dw: the three un-embedding weight gradients in one launch).
+ *   9: the guarded optimizer step (pm_h2_clamp_init, pm_overflow_snapshot, pm_overflow_poison, pm_grad_nonfinite_check,
+ *   pm_adam_step_guarded, pm_adam_bias_scalars; the PM_OVF_* status layout). */
+#define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
 
@@ -85,6 +87,10 @@ int pm_deterministic_faults(void);
  * library was loaded or since the last call with reset != 0 (synchronises the device; < 0: could not be read).  0 = no gradient
  * was clipped; the parity tests assert it. */
 int pm_h2_clamp_events(int32_t reset);
+/* Creates the device word of pm_h2_clamp_events (hipMalloc + a synchronous hipMemset) if this device has none yet.  A host
+ * calls it once when it sets a model up, so that no launch path is the first to touch the word (the guarded step's
+ * pm_overflow_snapshot / pm_overflow_poison refuse to run without it).  0 = the word exists. */
+int pm_h2_clamp_init(void);
 
 /* ------------------------------------------------------------------ graph plan
  * Replaces the per-layer boolean-mask edge selection `edge_index[:, edge_type == i]`
@@ -780,6 +786,59 @@ int pm_structure_metrics(const float* s_logits, const float* s_target, int64_t n
  * torch.optim.Adam (no weight decay, no amsgrad) over one flat fp32 buffer. */
 int pm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                  float beta1, float beta2, float eps, int32_t step, float grad_scale, pm_stream_t stream);
+
+/* ------------------------------------------------------------------ guarded optimizer step (training.py:123,160-162)
+ * The reference steps Adam through torch.cuda.amp.GradScaler: `scaler.step(optimizer)` skips the update of a step whose
+ * gradient holds an inf or NaN — parameters, both moments and Adam's step count stay as they were — and the LR scheduler
+ * steps regardless (training.py:168-172).  The entries below give the fused Adam the same skip, decided on the device with
+ * no host read; a second cause of a skip is a saturated split of the fp16 pair format (pm_h2_clamp_events) anywhere in the
+ * step.  Order of one step on the caller's stream:
+ *   pm_overflow_snapshot   before the step's first pair-format launch (the weight planes of the prologue);
+ *   pm_overflow_poison     where the gradient travels (a data-parallel exchange, an accumulation over micro-batches): after
+ *                          every producer of the gradient has joined, before the exchange (its first element is bucket 0's:
+ *                          the all-reduce carries the +inf to every rank, which all decide alike; an accumulation keeps it);
+ *   pm_grad_nonfinite_check on the gradient Adam consumes (the reduced one, or the accumulated one), deciding the step;
+ *   pm_adam_step_guarded.
+ * status: PM_OVF_WORDS uint32 words laid out as below, zeroed by the host once. */
+enum {
+  PM_OVF_PENDING = 0,    /* causes found since the last guarded step: PM_OVF_NONFINITE_BIT | PM_OVF_SATURATED_BIT */
+  PM_OVF_LAST = 1,       /* the causes the last guarded step was skipped for; 0 = it was applied */
+  PM_OVF_SNAP = 2,       /* the pair-format saturation counter at the snapshot */
+  PM_OVF_N_NONFINITE = 3,/* skipped steps without a saturation on this rank (a non-finite gradient, or another rank's) */
+  PM_OVF_N_SATURATED = 4,/* skipped steps with a saturated split on this rank */
+  PM_OVF_STEP_SIZE = 5,  /* float bits: lr / (1 - beta1^t) of the last applied step */
+  PM_OVF_INV_BC2 = 6,    /* float bits: 1 / sqrt(1 - beta2^t) of the last applied step */
+  PM_OVF_TICKET = 7,     /* pm_grad_nonfinite_check's decision word: finished workgroups (bits 0-15), those that saw a
+                            non-finite value (bits 16-31); back to 0 when the launch ends */
+  PM_OVF_WORDS = 8
+};
+enum { PM_OVF_NONFINITE_BIT = 1, PM_OVF_SATURATED_BIT = 2 };
+/* status[PM_OVF_SNAP] = the saturation counter (one thread).  The counter itself is not changed: pm_h2_clamp_events keeps
+ * counting since load / reset.  PM_E_INVALID before pm_h2_clamp_init. */
+int pm_overflow_snapshot(uint32_t* status, pm_stream_t stream);
+/* If the saturation counter moved since the snapshot: grads[0] = +inf and status[PM_OVF_PENDING] |= PM_OVF_SATURATED_BIT
+ * (one thread).  The +inf is what makes an all-reduced (sum: inf + x = inf) or accumulated gradient carry the decision. */
+int pm_overflow_poison(float* grads, uint32_t* status, pm_stream_t stream);
+/* status[PM_OVF_PENDING] |= PM_OVF_NONFINITE_BIT if any of grads[0..n) is an inf or a NaN — GradScaler's found_inf
+ * (training.py:160-162).  Decided on the exponent bits, immune to fast-math flags; one atomic per workgroup.
+ * window != 0: a move of the saturation counter since pm_overflow_snapshot sets PM_OVF_SATURATED_BIT too (what
+ * pm_overflow_poison records where the gradient travels; a single-rank step without accumulation needs no poison).
+ * step == NULL: the flag only.  Otherwise the launch's last workgroup (ticket in status[PM_OVF_TICKET]) DECIDES the optimizer
+ * step: it moves status[PM_OVF_PENDING] to status[PM_OVF_LAST] and clears it; no cause: *step += 1 and the bias-correction
+ * scalars of the new t into status[PM_OVF_STEP_SIZE / _INV_BC2] (in double, as pm_adam_step forms them on the host); a
+ * cause: *skipped += 1 and the cause's counter.  step / skipped: int64 device words. */
+int pm_grad_nonfinite_check(const float* grads, int64_t n, uint32_t* status, int64_t* step, int64_t* skipped, float lr,
+                            float beta1, float beta2, int32_t window, pm_stream_t stream);
+/* pm_adam_step behind the decision of pm_grad_nonfinite_check: every workgroup reads status[PM_OVF_LAST] and the scalars once
+ * and stores nothing when a cause is set — what `scaler.step(optimizer)` does on found_inf (training.py:160-162).  Adam's t
+ * comes from the device word the decision advanced, never from the host (which cannot know whether the previous step was
+ * skipped).  An applied step equals pm_adam_step at the same t bit for bit. */
+int pm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                         float beta2, float eps, float grad_scale, const uint32_t* status, pm_stream_t stream);
+/* out[2i], out[2i+1] = the scalars the decision forms for step steps[i] >= 1: lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)
+ * (the same device function; for parity checks against the host formula). */
+int pm_adam_bias_scalars(const int64_t* steps, int64_t n, float lr, float beta1, float beta2, float* out,
+                         pm_stream_t stream);
 
 /* Gradient accumulation over `iters_to_accumulate` micro-batches (training.py:149,158: backward of tot_loss / k, optimizer
  * step every k-th batch): accum = (first ? 0 : accum) + scale * grads, scale = 1 / k. */

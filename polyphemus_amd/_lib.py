@@ -154,11 +154,17 @@ _SIGS = {
     "pm_get_deterministic": "",
     "pm_deterministic_faults": "",
     "pm_h2_clamp_events": "i",
+    "pm_h2_clamp_init": "",
+    "pm_overflow_snapshot": "ps",
+    "pm_overflow_poison": "pps",
+    "pm_grad_nonfinite_check": "plpppfffis",
+    "pm_adam_step_guarded": "pppplffffps",
+    "pm_adam_bias_scalars": "plfffps",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",
           "pm_unembed_dh_scratch_bytes", "pm_unembed_row_counts_len"}
-ABI_VERSION = 8          # PM_ABI_VERSION of include/polyphemus_hip.h this table was written against
+ABI_VERSION = 9          # PM_ABI_VERSION of include/polyphemus_hip.h this table was written against
 EXPORTED = sorted(list(_SIGS) + ["pm_abi_version", "pm_build_info", "pm_dropout_hash", "pm_vae_layout_bytes",
                                  "pm_vae_step_state_bytes"])
 
@@ -254,6 +260,12 @@ def h2_clamp_events(reset: bool = False) -> int:
     """Threads of the fp16-pair split kernels whose scaled value saturated at +-65504 (a gradient was clipped) since the library
     was loaded / the last reset; 0 = every operand fitted its scale (synchronises the device)."""
     return int(lib().pm_h2_clamp_events(1 if reset else 0))
+
+
+def h2_clamp_init() -> None:
+    """Create the saturation counter of h2_clamp_events (hipMalloc + a synchronous memset) if this device has none: done when a
+    model's step is set up, so that no launch of a step is the first to touch it."""
+    call("pm_h2_clamp_init")
 
 
 class deterministic:

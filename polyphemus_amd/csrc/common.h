@@ -87,6 +87,8 @@ unsigned* pm_det_gate(hipStream_t st);
 int pm_det_on();
 // device word counting the threads whose fp16-pair split saturated (pm_clamp_f16 above); nullptr if it could not be set up
 unsigned* pm_h2_clamp_word();
+// ... only if pm_h2_clamp_init made it (per-step launches must never be the first to touch it); nullptr otherwise
+unsigned* pm_h2_clamp_word_ready();
 
 #ifdef __HIPCC__
 __device__ static inline unsigned pm_linear_block() {

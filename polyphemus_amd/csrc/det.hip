@@ -1,4 +1,5 @@
-// det.hip — host side of the deterministic mode (common.h, "deterministic mode"): the switch and the pool of gates.
+// det.hip — host side of the deterministic mode (common.h, "deterministic mode"): the switch and the pool of gates; the
+// saturation counter of the fp16 pair format and the two one-thread kernels that bracket a guarded step's window on it.
 //
 // Reference: the reference's CPU step is reproducible for a fixed thread count (training.py:137-166 on ATen's CPU
 // kernels); the HIP step is not by default because its reductions across workgroups use float atomics.  With
@@ -93,4 +94,36 @@ extern "C" int pm_h2_clamp_events(int32_t reset) {
   if (hipMemcpy(&v, w, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (reset && hipMemset(w, 0, sizeof(v)) != hipSuccess) return -1;
   return (int)(v > 0x7fffffffu ? 0x7fffffffu : v);
+}
+extern "C" int pm_h2_clamp_init(void) { return pm_h2_clamp_word() ? PM_OK : PM_E_INVALID; }
+
+// ---- the saturation window of one guarded step (include/polyphemus_hip.h, "guarded optimizer step")
+// the word if pm_h2_clamp_init made it: these launches run every step and must never be the first to touch it (the lazy
+// set-up of pm_h2_clamp_word() is a hipMalloc and a synchronous hipMemset)
+unsigned* pm_h2_clamp_word_ready() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  std::lock_guard<std::mutex> lock(g_mu);
+  return g_clamp_word[dev];
+}
+__global__ void k_overflow_snapshot(const unsigned* __restrict__ clamp, unsigned* __restrict__ status) {
+  status[PM_OVF_SNAP] = *clamp;
+}
+__global__ void k_overflow_poison(const unsigned* __restrict__ clamp, float* __restrict__ grads, unsigned* __restrict__ status) {
+  if (*clamp != status[PM_OVF_SNAP]) {             // (any change: a pm_h2_clamp_events reset inside the window counts too)
+    grads[0] = __uint_as_float(0x7f800000u);
+    status[PM_OVF_PENDING] |= PM_OVF_SATURATED_BIT;
+  }
+}
+extern "C" int pm_overflow_snapshot(uint32_t* status, pm_stream_t stream) {
+  unsigned* w = pm_h2_clamp_word_ready();
+  if (!w || !status) return PM_E_INVALID;
+  hipLaunchKernelGGL(k_overflow_snapshot, dim3(1), dim3(1), 0, (hipStream_t)stream, w, status);
+  return pm_check_launch();
+}
+extern "C" int pm_overflow_poison(float* grads, uint32_t* status, pm_stream_t stream) {
+  unsigned* w = pm_h2_clamp_word_ready();
+  if (!w || !grads || !status) return PM_E_INVALID;
+  hipLaunchKernelGGL(k_overflow_poison, dim3(1), dim3(1), 0, (hipStream_t)stream, w, grads, status);
+  return pm_check_launch();
 }

@@ -79,5 +79,174 @@ extern "C" int pm_adam_step(float* params, const float* grads, float* exp_avg, f
   return pm_check_launch();
 }
 
+// ---- guarded step (include/polyphemus_hip.h, "guarded optimizer step"; GradScaler, training.py:160-162)
+// Adam's bias-correction scalars at step t, in double as pm_adam_step forms them on the host
+__device__ static inline void adam_bias_scalars(int64_t t, float lr, float beta1, float beta2, float& step_size,
+                                                float& inv_bc2_sqrt) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)t);
+  const double bc2 = 1.0 - pow((double)beta2, (double)t);
+  step_size = (float)((double)lr / bc1);
+  inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+}
+// non-finite = exponent bits all ones (inf or NaN); a bit test no fast-math flag can fold away, unlike isfinite
+__device__ static inline bool nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u; }
+// the workgroup's verdict, one atomic per workgroup.  With a decision to make it goes into the ticket word itself — the count of
+// finished workgroups in the low 16 bits, of workgroups that saw a non-finite value from bit 16 on — so the last workgroup
+// (the one that takes ticket gridDim.x - 1) reads every other verdict from the value its own add returns: read-modify-writes of
+// one word are totally ordered, and no fence (an L2 write-back per workgroup: 2048 of them cost 47 us) is needed
+struct NonfiniteDecision { int64_t* step; int64_t* skipped; const unsigned* clamp; float lr, beta1, beta2; };
+__device__ static inline void check_epilogue(bool bad, unsigned* __restrict__ status, const NonfiniteDecision& d) {
+  const bool wg_bad = __syncthreads_or(bad);
+  if (threadIdx.x != 0) return;
+  if (!d.step) {
+    if (wg_bad) atomicOr(status + PM_OVF_PENDING, (unsigned)PM_OVF_NONFINITE_BIT);
+    return;
+  }
+  const unsigned mine = 1u + (wg_bad ? 1u << 16 : 0u);
+  const unsigned total = atomicAdd(status + PM_OVF_TICKET, mine) + mine;
+  if ((total & 0xffffu) != gridDim.x) return;
+  atomicExch(status + PM_OVF_TICKET, 0u);                       // (for the next launch)
+  unsigned why = status[PM_OVF_PENDING] | ((total >> 16) ? (unsigned)PM_OVF_NONFINITE_BIT : 0u);
+  if (d.clamp && __hip_atomic_load(d.clamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != status[PM_OVF_SNAP])
+    why |= PM_OVF_SATURATED_BIT;                               // (any change: a pm_h2_clamp_events reset inside the window too)
+  status[PM_OVF_PENDING] = 0;
+  status[PM_OVF_LAST] = why;
+  if (why) {
+    *d.skipped += 1;
+    status[(why & PM_OVF_SATURATED_BIT) ? PM_OVF_N_SATURATED : PM_OVF_N_NONFINITE] += 1;
+    return;
+  }
+  const int64_t t = *d.step + 1;
+  *d.step = t;
+  float step_size, inv_bc2_sqrt;
+  adam_bias_scalars(t, d.lr, d.beta1, d.beta2, step_size, inv_bc2_sqrt);
+  status[PM_OVF_STEP_SIZE] = __float_as_uint(step_size);
+  status[PM_OVF_INV_BC2] = __float_as_uint(inv_bc2_sqrt);
+}
+// one workgroup of 1024 threads per CU, four loads in flight per thread: the pass runs at the HBM rate with 256 workgroups, so the
+// decision word takes 256 same-address atomics, not 2048 (serialised, those cost 26 us)
+constexpr int kCheckThreads = 1024, kCheckBlocks = 256;
+__global__ void __launch_bounds__(kCheckThreads) k_nonfinite4(const uint4* __restrict__ g, int64_t n4,
+                                                              unsigned* __restrict__ status, NonfiniteDecision d) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    const uint4 u0 = g[i], u1 = g[i + stride], u2 = g[i + 2 * stride], u3 = g[i + 3 * stride];
+    bad |= nonfinite_bits(u0.x) | nonfinite_bits(u0.y) | nonfinite_bits(u0.z) | nonfinite_bits(u0.w) |
+           nonfinite_bits(u1.x) | nonfinite_bits(u1.y) | nonfinite_bits(u1.z) | nonfinite_bits(u1.w) |
+           nonfinite_bits(u2.x) | nonfinite_bits(u2.y) | nonfinite_bits(u2.z) | nonfinite_bits(u2.w) |
+           nonfinite_bits(u3.x) | nonfinite_bits(u3.y) | nonfinite_bits(u3.z) | nonfinite_bits(u3.w);
+  }
+  for (; i < n4; i += stride) {
+    const uint4 u = g[i];
+    bad |= nonfinite_bits(u.x) | nonfinite_bits(u.y) | nonfinite_bits(u.z) | nonfinite_bits(u.w);
+  }
+  check_epilogue(bad, status, d);
+}
+__global__ void __launch_bounds__(kCheckThreads) k_nonfinite1(const unsigned* __restrict__ g, int64_t n,
+                                                              unsigned* __restrict__ status, NonfiniteDecision d) {
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    bad |= nonfinite_bits(g[i]);
+  check_epilogue(bad, status, d);
+}
+// the workgroup reads the decision and the scalars once; a skipped step stores nothing
+#define PM_ADAM_GUARD(status)                                                                         \
+  __shared__ unsigned sh[3];                                                                          \
+  if (threadIdx.x == 0) {                                                                             \
+    sh[0] = status[PM_OVF_LAST]; sh[1] = status[PM_OVF_STEP_SIZE]; sh[2] = status[PM_OVF_INV_BC2];    \
+  }                                                                                                   \
+  __syncthreads();                                                                                    \
+  if (sh[0]) return;                                                                                  \
+  const float step_size = __uint_as_float(sh[1]), inv_bc2_sqrt = __uint_as_float(sh[2]);
+__global__ void __launch_bounds__(256) k_adam4_guarded(float4* __restrict__ p, const float4* __restrict__ g,
+                                                       float4* __restrict__ m, float4* __restrict__ v, int64_t n4, float b1,
+                                                       float b2, const unsigned* __restrict__ status, float eps,
+                                                       float gscale) {
+  PM_ADAM_GUARD(status)
+  // (the loop of k_adam4, expression for expression: an applied step is bit-identical to pm_adam_step)
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
+    float* P = reinterpret_cast<float*>(&pv); float* Gd = reinterpret_cast<float*>(&gv);
+    float* M = reinterpret_cast<float*>(&mv); float* V = reinterpret_cast<float*>(&vv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gr = Gd[j] * gscale;
+      M[j] = b1 * M[j] + (1.f - b1) * gr;
+      V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
+      P[j] -= step_size * (M[j] / (sqrtf(V[j]) * inv_bc2_sqrt + eps));
+    }
+    p[i] = pv; m[i] = mv; v[i] = vv;
+  }
+}
+__global__ void __launch_bounds__(256) k_adam1_guarded(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n, float b1,
+                                                       float b2, const unsigned* __restrict__ status, float eps,
+                                                       float gscale) {
+  PM_ADAM_GUARD(status)
+  // (the loop of k_adam1)
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float gr = g[i] * gscale;
+    const float mm = b1 * m[i] + (1.f - b1) * gr;
+    const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
+    m[i] = mm; v[i] = vv;
+    p[i] -= step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps));
+  }
+}
+#undef PM_ADAM_GUARD
+__global__ void k_adam_bias_scalars(const int64_t* __restrict__ steps, int64_t n, float lr, float beta1, float beta2,
+                                    float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    adam_bias_scalars(steps[i], lr, beta1, beta2, out[2 * i], out[2 * i + 1]);
+}
+extern "C" int pm_grad_nonfinite_check(const float* grads, int64_t n, uint32_t* status, int64_t* step, int64_t* skipped,
+                                       float lr, float beta1, float beta2, int32_t window, pm_stream_t stream) {
+  if (!grads || !status || n <= 0 || (step && !skipped)) return PM_E_INVALID;
+  NonfiniteDecision d{step, skipped, nullptr, lr, beta1, beta2};
+  if (step && window) {
+    d.clamp = pm_h2_clamp_word_ready();
+    if (!d.clamp) return PM_E_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // (grid <= 256 < 2^16: the two counts of the decision word cannot overflow into each other)
+  if (!((uintptr_t)grads & 15) && (n % 4) == 0) {
+    int64_t nb = pm_cdiv(n / 4, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
+    hipLaunchKernelGGL(k_nonfinite4, dim3((unsigned)nb), dim3(kCheckThreads), 0, st, reinterpret_cast<const uint4*>(grads),
+                       n / 4, status, d);
+  } else {
+    int64_t nb = pm_cdiv(n, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
+    hipLaunchKernelGGL(k_nonfinite1, dim3((unsigned)nb), dim3(kCheckThreads), 0, st, reinterpret_cast<const unsigned*>(grads),
+                       n, status, d);
+  }
+  return pm_check_launch();
+}
+extern "C" int pm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                    float beta1, float beta2, float eps, float grad_scale, const uint32_t* status,
+                                    pm_stream_t stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !status || n <= 0) return PM_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const bool al = !(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15);
+  if (al && (n % 4) == 0) {
+    int64_t nb = pm_cdiv(n / 4, 256); if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(k_adam4_guarded, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<float4*>(params),
+                       reinterpret_cast<const float4*>(grads), reinterpret_cast<float4*>(exp_avg),
+                       reinterpret_cast<float4*>(exp_avg_sq), n / 4, beta1, beta2, status, eps, grad_scale);
+  } else {
+    int64_t nb = pm_cdiv(n, 256); if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(k_adam1_guarded, dim3((unsigned)nb), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n,
+                       beta1, beta2, status, eps, grad_scale);
+  }
+  return pm_check_launch();
+}
+extern "C" int pm_adam_bias_scalars(const int64_t* steps, int64_t n, float lr, float beta1, float beta2, float* out,
+                                    pm_stream_t stream) {
+  if (!steps || !out || n <= 0) return PM_E_INVALID;
+  int64_t nb = pm_cdiv(n, 256); if (nb > 1024) nb = 1024;
+  hipLaunchKernelGGL(k_adam_bias_scalars, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, steps, n, lr, beta1,
+                     beta2, out);
+  return pm_check_launch();
+}
+
 extern "C" int pm_abi_version(void) { return PM_ABI_VERSION; }
 extern "C" const char* pm_build_info(void) { return "polyphemus_hip gfx950 (CDNA4) fp32-MFMA build " __DATE__; }

@@ -274,6 +274,10 @@ class _VaeStepFn(torch.autograd.Function):
         # (a fresh zeroed gradient buffer per call, 10 us of memset at d = 256: autograd may keep the returned views as
         #  `p.grad` — with gradient accumulation beyond this step — so the buffer cannot be the previous call's)
         grads = torch.zeros_like(vae.flat_params)
+        status = None
+        if vae.poison_on_saturation:                         # the saturation window opens before the prologue's splits
+            status = ops.overflow_status(grads.device)
+            ops.overflow_snapshot(status)
         # ext_loss: the caller computes the loss — the forward stores the logits and runs none of its own loss kernels
         step.forward(graph, eps, grads, keep_logits=True, n_slots=n_slots, ext_loss=True)
         # outputs as views of the step's arena (no 224 MB copy of the logits); vae.outputs_as_views = False: fresh copies, for a
@@ -285,7 +289,7 @@ class _VaeStepFn(torch.autograd.Function):
             full[:, :S] = c_logits
             c_logits = full
         step.bump_counters()
-        ctx.vae, ctx.step, ctx.grads, ctx.S = vae, step, grads, S
+        ctx.vae, ctx.step, ctx.grads, ctx.S, ctx.status = vae, step, grads, S, status
         ctx.ticket = vae._step_ticket = vae._step_ticket + 1
         ctx.set_materialize_grads(False)
         return s_logits, c_logits, mu, lv
@@ -305,6 +309,8 @@ class _VaeStepFn(torch.autograd.Function):
         step.backward_encoder_heads()
         step.backward_encoder()
         step.backward_encoder_tail()
+        if ctx.status is not None:                           # ... and closes behind the last producer of the gradient
+            ops.overflow_poison(ctx.grads, ctx.status)
         vae._step_ticket += 1                                # (a second backward through the same forward has nothing to read)
         g, P = ctx.grads, dict(vae.named_parameters())
         return (None, None, None) + tuple(g[vae._offsets[n]:vae._offsets[n] + P[n].numel()].view(P[n].shape)
@@ -420,6 +426,9 @@ class VAE(nn.Module):
         # come back as zeros (the reference's loss ignores them: same loss, same gradients); default: all 15, as the reference
         self.active_slots_only = False
         self.outputs_as_views = True                         # model(graph) in training mode returns views of the native step's arena
+        # True: a step whose fp16 pair-format split saturated returns a gradient with +inf in its first element, so that the
+        # caller's GradScaler skips the update as it skips one with an inf gradient (training.py:160-162)
+        self.poison_on_saturation = False
         self._step_ticket = 0
         self._flatten()
 

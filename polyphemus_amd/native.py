@@ -179,6 +179,7 @@ class NativeStep:
         self._call, self._plan_layout, self._ptr, self._stream, self._fields = call, plan_layout, ptr, stream, PLAN_FIELDS
         self.vae = vae
         self.layout = build_layout(vae)
+        call("pm_h2_clamp_init")          # the pair format's saturation counter: set up here, never by a launch of the step
         self.flat_ptr = vae.flat_params.data_ptr()
         self.state = C.create_string_buffer(int(lib().pm_vae_step_state_bytes()))
         self.ws = None

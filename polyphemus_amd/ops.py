@@ -639,3 +639,64 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, g
         _chk(t, F32, n)
     call("pm_adam_step", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), lr, beta1, beta2,
          eps, step, grad_scale, stream())
+
+
+# ---- guarded optimizer step (include/polyphemus_hip.h, "guarded optimizer step"; GradScaler, training.py:160-162)
+OVF_WORDS = 8                                   # PM_OVF_WORDS
+OVF_PENDING, OVF_LAST, OVF_SNAP, OVF_N_NONFINITE, OVF_N_SATURATED, OVF_STEP_SIZE, OVF_INV_BC2, OVF_TICKET = range(8)
+OVF_NONFINITE_BIT, OVF_SATURATED_BIT = 1, 2
+
+
+def overflow_status(device) -> torch.Tensor:
+    """A zeroed status block of the guarded step (int32 [PM_OVF_WORDS], the words read as uint32 by the kernels)."""
+    return torch.zeros(OVF_WORDS, dtype=I32, device=device)
+
+
+def _chk_status(status):
+    _chk(status, I32, "status")
+    if status.numel() < OVF_WORDS:
+        raise ValueError(f"status needs {OVF_WORDS} words")
+
+
+def overflow_snapshot(status):
+    """status[OVF_SNAP] = the pair-format saturation counter, on the current stream (before the step's first split)."""
+    _chk_status(status)
+    call("pm_overflow_snapshot", ptr(status), stream())
+
+
+def overflow_poison(grads, status):
+    """grads[0] = +inf and the saturation bit in status[OVF_PENDING] if a pair-format split saturated since the snapshot."""
+    _chk(grads, F32, "grads"); _chk_status(status)
+    call("pm_overflow_poison", ptr(grads), ptr(status), stream())
+
+
+def grad_nonfinite_check(grads, status, step=None, skipped=None, lr=0.0, beta1=0.0, beta2=0.0, window=False):
+    """The non-finite bit in status[OVF_PENDING] if grads holds an inf or a NaN (GradScaler's found_inf).  With the int64
+    device words `step` / `skipped` the launch also DECIDES the optimizer step (t + 1 and its Adam scalars, or a skip);
+    `window`: a move of the saturation counter since `overflow_snapshot` is a cause too."""
+    _chk(grads, F32, "grads"); _chk_status(status)
+    if (step is None) != (skipped is None):
+        raise ValueError("step and skipped go together")
+    if step is not None:
+        _chk(step, I64, "step"); _chk(skipped, I64, "skipped")
+    call("pm_grad_nonfinite_check", ptr(grads), grads.numel(), ptr(status), ptr(step), ptr(skipped), lr, beta1, beta2,
+         int(bool(window)), stream())
+
+
+def adam_step_guarded(params, grads, exp_avg, exp_avg_sq, beta1, beta2, eps, status, grad_scale=1.0):
+    """`adam_step` at the t and with the scalars `grad_nonfinite_check` decided, unless it decided a skip: then nothing is
+    stored.  An applied step equals `adam_step` at that t bit for bit."""
+    for t, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, F32, n)
+    _chk_status(status)
+    call("pm_adam_step_guarded", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), beta1, beta2,
+         eps, grad_scale, ptr(status), stream())
+
+
+def adam_bias_scalars(steps, lr, beta1, beta2):
+    """[n, 2] float32: (lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) for each t of the int64 device tensor `steps`, from the
+    device function the step's decision uses."""
+    _chk(steps, I64, "steps")
+    out = torch.empty(steps.numel(), 2, dtype=F32, device=steps.device)
+    call("pm_adam_bias_scalars", ptr(steps), steps.numel(), lr, beta1, beta2, ptr(out), stream())
+    return out

@@ -24,12 +24,13 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import warnings
 from typing import Dict, Optional
 
 import torch
 
 from . import ops
-from ._lib import call, lib, ptr, stream
+from ._lib import call, h2_clamp_init, lib, ptr, stream
 from .model import VAE, prepare_graph
 from .native import NativeStep, prepare_inputs
 from .parallel import GradBuckets, broadcast_
@@ -67,7 +68,10 @@ def bucket_boundaries(vae: VAE):
 class HipTrainer:
     def __init__(self, vae: VAE, lr=5e-6, betas=(0.9, 0.98), eps=1e-9, lr_scheduler: Optional[dict] = None,
                  structure_loss_on_logits: bool = False, beta: float = 0.0, process_group=None, native: bool = True,
-                 iters_to_accumulate: int = 1, global_token_mean: bool = False, sync_bn: bool = False):
+                 iters_to_accumulate: int = 1, global_token_mean: bool = False, sync_bn: bool = False,
+                 overflow: str = "ignore"):
+        if overflow not in ("ignore", "skip"):
+            raise ValueError(f"overflow must be 'ignore' or 'skip', not {overflow!r}")
         self.vae = vae
         self.lr, self.betas, self.eps = lr, betas, eps
         self.sched = ExpDecayLR(**lr_scheduler) if lr_scheduler else None
@@ -104,6 +108,21 @@ class HipTrainer:
         self.grads = torch.zeros_like(flat)
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
+        # Overflow policy of the optimizer step.  "ignore": Adam applies whatever gradient it gets (no extra launch).
+        # "skip": the reference's GradScaler semantics (training.py:123,152-162) — an update whose gradient holds an inf or
+        # a NaN, or whose step saturated a split of the fp16 pair format on any rank, is skipped ON THE DEVICE (parameters,
+        # moments and Adam's step count unchanged; the LR schedule still steps): a snapshot of the saturation counter, one read
+        # of the gradient that also decides, no host sync.
+        self.overflow = overflow
+        self._guard = overflow == "skip"
+        h2_clamp_init()                          # the saturation counter exists before any step reads it
+        if self._guard:
+            self._ovf_status = ops.overflow_status(flat.device)
+            self._ovf_counts = torch.zeros(2, dtype=torch.int64, device=flat.device)     # [Adam's step count t, skipped]
+            self._ovf_host = torch.zeros(1, dtype=torch.int64).pin_memory()             # skipped, copied without a sync
+            self._ovf_event = torch.cuda.Event()
+            self._ovf_copied = False
+            self._ovf_warned = 0
         self.step_count = 0
         self.loss_buf = torch.zeros(4, dtype=torch.float64, device=flat.device)
         P = dict(vae.named_parameters())
@@ -118,6 +137,9 @@ class HipTrainer:
                     self._G[f"{head}.layers.{i}.nn.{tail}"] = self._G[k]
         self.buckets = GradBuckets(self.grads, bucket_boundaries(vae), process_group)
         self.world = self.buckets.world
+        # the +inf that carries a saturation is needed only where the gradient travels (an exchange, an accumulation); a
+        # single-rank step gets the verdict from the check itself, which compares the counter with the snapshot
+        self._poison = self._guard and (self.world > 1 or self.iters_to_accumulate > 1)
         # gradient accumulation: running sum of grads / k; all-reduced (one bucket) and consumed by Adam every k-th batch
         self.grad_accum = torch.zeros_like(flat) if self.iters_to_accumulate > 1 else None
         self._accum_bucket = GradBuckets(self.grad_accum, [], process_group) if self.grad_accum is not None else None
@@ -141,6 +163,52 @@ class HipTrainer:
     def _plan_buf(self):
         return self.step.plan_buf
 
+    @property
+    def step_count(self) -> int:
+        """Adam's step count t.  With overflow="skip" it lives on the device (a skipped step does not advance it): reading
+        it then synchronises."""
+        return int(self._ovf_counts[0]) if self._guard else self._step_count
+
+    @step_count.setter
+    def step_count(self, t: int) -> None:
+        self._step_count = int(t)
+        if self._guard:
+            self._ovf_counts[0].fill_(int(t))
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """Device int64 count of the optimizer steps skipped on a non-finite or saturated gradient (overflow="skip")."""
+        return self._ovf_counts[1] if self._guard else torch.zeros((), dtype=torch.int64, device=self.grads.device)
+
+    @property
+    def last_update_skipped(self) -> torch.Tensor:
+        """Device bool: the last optimizer step was skipped (overflow="skip")."""
+        if not self._guard:
+            return torch.zeros((), dtype=torch.bool, device=self.grads.device)
+        return self._ovf_status[ops.OVF_LAST] != 0
+
+    def overflow_stats(self) -> dict:
+        """Host dict of the guard's counters (this DOES sync): skipped optimizer steps, and of them those with a saturated
+        pair-format split on this rank (`saturated`) and the others (`non_finite`: an inf / NaN gradient, or a saturation on
+        another rank that reached this one through the all-reduce)."""
+        if not self._guard:
+            return {"skipped": 0, "non_finite": 0, "saturated": 0}
+        st = self._ovf_status.tolist()
+        return {"skipped": int(self._ovf_counts[1]), "non_finite": st[ops.OVF_N_NONFINITE],
+                "saturated": st[ops.OVF_N_SATURATED]}
+
+    def _warn_skips(self) -> None:
+        """RuntimeWarning for steps skipped since the last warning, read from the copy the previous step made — only if it
+        has arrived (event query, never a wait)."""
+        if not (self._ovf_copied and self._ovf_event.query()):
+            return
+        self._ovf_copied = False
+        n = int(self._ovf_host[0])
+        if n > self._ovf_warned:
+            warnings.warn(f"{n - self._ovf_warned} optimizer step(s) skipped on a non-finite or saturated gradient ({n} so "
+                          "far; trainer.overflow_stats() has the causes)", RuntimeWarning, stacklevel=3)
+            self._ovf_warned = n
+
     def _native_forward_backward(self, graph, eps):
         vae, step = self.vae, self.step
         ce_scale = None
@@ -151,6 +219,8 @@ class HipTrainer:
             tot = inputs[9].clone()
             dist.all_reduce(tot, group=self.pg)
             ce_scale = (inputs[9] * float(self.world) / tot).contiguous()      # stays on the device
+        if self._guard:                                      # in front of the prologue's weight-plane splits
+            call("pm_overflow_snapshot", self._ovf_status.data_ptr(), stream())
         step.forward(graph, eps, self.grads, keep_logits=self.keep_logits, beta=self.beta,
                      fix_structure=self.fix_structure_loss, ce_scale=ce_scale, want_token_counts=gtm)
         if prepare_inputs(graph)[8] and os.environ.get("PM_DEBUG", "0") not in ("", "0"):
@@ -169,6 +239,8 @@ class HipTrainer:
         step.backward_encoder()
         self.buckets.launch(1)                               # graph encoder .. encoder head: overlapped with the tail
         step.backward_encoder_tail()
+        if self._poison:                                     # every producer has joined: a saturation becomes +inf in bucket 0
+            ops.overflow_poison(self.grads, self._ovf_status)
         self.buckets.launch(0)                               # chord encoder, embeddings, structure encoder
         step.bump_counters()
         return step.loss_buf
@@ -191,6 +263,8 @@ class HipTrainer:
 
     def _python_forward_backward(self, graph, eps):
         vae, eng = self.vae, self.vae.engine
+        if self._guard:
+            ops.overflow_snapshot(self._ovf_status)
         eng.msg_dropout = vae.msg_dropout
         graph.__dict__.pop("_pm_plan", None)                 # the plan is part of the step (new batch every step)
         plan = prepare_graph(graph, vae.cfg["n_bars"])
@@ -223,6 +297,8 @@ class HipTrainer:
         ops.reparam_bwd(dz, lv, eps, dmu, dlv)
         eng.encoder_backward(esv, dmu, dlv, G)
         self.buckets.launch(1)
+        if self._poison:
+            ops.overflow_poison(self.grads, self._ovf_status)
         self.buckets.launch(0)
         return out
 
@@ -235,6 +311,8 @@ class HipTrainer:
             raise RuntimeError("train_step needs vae.train()")
         if vae.flat_params.data_ptr() != self._flat_ptr:
             raise RuntimeError("the model's flat parameter buffer moved after the trainer was built; rebuild it")
+        if self._guard:
+            self._warn_skips()
         self.grads.zero_()
         k = self.iters_to_accumulate
         self.buckets.hold = k > 1                      # micro-batches of an accumulation are not all-reduced one by one
@@ -252,9 +330,20 @@ class HipTrainer:
         else:
             mean_scale = self.buckets.wait()
         # ---- optimizer (training.py:160-172)
-        self.step_count += 1
-        ops.adam_step(vae.flat_params, grads, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0],
-                      self.betas[1], self.eps, self.step_count, grad_scale=mean_scale)
+        if self._guard:                                # scaler.step(optimizer): no update on found_inf (training.py:160-162)
+            st, sp = stream(), self._ovf_status.data_ptr()
+            cp = self._ovf_counts.data_ptr()
+            call("pm_grad_nonfinite_check", grads.data_ptr(), grads.numel(), sp, cp, cp + 8, self.lr, self.betas[0],
+                 self.betas[1], 1, st)
+            call("pm_adam_step_guarded", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
+                 self.exp_avg_sq.data_ptr(), grads.numel(), self.betas[0], self.betas[1], self.eps, mean_scale, sp, st)
+            self._ovf_host.copy_(self._ovf_counts[1:2], non_blocking=True)
+            self._ovf_event.record()
+            self._ovf_copied = True
+        else:
+            self.step_count += 1
+            ops.adam_step(vae.flat_params, grads, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0],
+                          self.betas[1], self.eps, self.step_count, grad_scale=mean_scale)
         if self.sched is not None:
             self.lr = self.sched.step()
         return out
@@ -321,9 +410,10 @@ class HipTrainer:
         vae = self.vae
         P = dict(vae.named_parameters())
         state = {}
+        t = float(self.step_count)                      # (overflow="skip": the device count, read once)
         for i, n in enumerate(vae._param_names):
             o, k = vae._offsets[n], P[n].numel()
-            state[i] = {"step": torch.tensor(float(self.step_count)),
+            state[i] = {"step": torch.tensor(t),
                         "exp_avg": self.exp_avg[o:o + k].view(P[n].shape).clone(),
                         "exp_avg_sq": self.exp_avg_sq[o:o + k].view(P[n].shape).clone()}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
@@ -377,7 +467,9 @@ class HipTrainer:
         if ds is not None:                              # continues with fresh masks instead of replaying the old ones
             self.vae.seed, self.vae._step = int(ds["seed"]), int(ds["step"])
         if self.sched is not None:
-            self.sched.update_steps = self.step_count
+            # (overflow="skip": the schedule also stepped on skipped updates, so its position is the number of update
+            #  attempts, not t)
+            self.sched.update_steps = self.micro_batches // self.iters_to_accumulate if self._guard else self.step_count
         return ckpt
 
     def losses_dict(self, out: torch.Tensor) -> dict:
