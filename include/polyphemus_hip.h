@@ -60,7 +60,9 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   pm_unembed_row_lists / pm_unembed_ce_rows / pm_unembed_dh_rows: the decoder head without its PAD-target rows;
  *   pm_unembed_dw: the three un-embedding weight gradients in one launch).
  *   9: the guarded optimizer step (pm_h2_clamp_init, pm_overflow_snapshot, pm_overflow_poison, pm_grad_nonfinite_check,
- *   pm_adam_step_guarded, pm_adam_bias_scalars; the PM_OVF_* status layout). */
+ *   pm_adam_step_guarded, pm_adam_bias_scalars; the PM_OVF_* status layout).  Additive, same version: the training
+ *   accuracies (pm_vae_step_set_metrics, pm_unembed_ce_metrics, pm_unembed_ce_rows_metrics, pm_content_accuracy_slots,
+ *   pm_train_metric_counts; no existing struct or argument list changed). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -782,6 +784,38 @@ int pm_content_accuracy(const float* c_logits /* [N,15,230] */, const int32_t* t
 int pm_structure_metrics(const float* s_logits, const float* s_target, int64_t n, int64_t* counts /* [4] */,
                          pm_stream_t stream);
 
+/* ------------------------------------------------------------------ training accuracies (training.py:174-179)
+ * The reference's per-batch `_accuracies` on the training-mode logits, as one int64 counts row [16] per batch:
+ *   [0..7] as pm_content_accuracy, [8..11] as pm_structure_metrics, [12] structure cells (G * 128), [13..15] 0.
+ * Arg-max over the raw fp32 logits of the pitch (131) and duration (99) blocks, the lowest index on ties (the reference
+ * arg-maxes softmax(x): the two differ only where two soft-max values round to the same float).  Two parts: a producer writes
+ * one verdict byte per (node, active slot) row r and block — verdict[r] pitch, verdict[N S + r] duration, 1 = arg-max is
+ * the target, written for every row whose target is not PAD — and clears counts[0..15]; pm_train_metric_counts then joins the
+ * two verdicts of each row (note = pitch and duration) into counts[0..6] and adds the structure counts and [12].
+ * pm_unembed_ce_metrics / pm_unembed_ce_rows_metrics: pm_unembed_ce / pm_unembed_ce_rows (loss, d_logits, bias gradients
+ * bit-identical) that also produce the verdicts of the rows they cover, then the join (is_drum NULL: no join, the caller
+ * issues pm_train_metric_counts).  pm_content_accuracy_slots: the same from materialised logits [N, S, 230]. */
+int pm_unembed_ce_metrics(const float* H, const float* w_pitch_drum, const float* b_pitch_drum, const float* w_pitch_nd,
+                          const float* b_pitch_nd, const float* w_dur, const float* b_dur, const int32_t* tokens,
+                          const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d, int32_t n_slots,
+                          float grad_scale, const float* dev_scale, float* logits, float* d_logits,
+                          float* db_pitch_drum, float* db_pitch_nd, float* db_dur, double* out, uint16_t* w_planes,
+                          const uint8_t* is_drum /* [N] or NULL */, uint8_t* verdict /* [2 N n_slots] */,
+                          int64_t* counts /* [16] */, pm_stream_t stream);
+int pm_unembed_ce_rows_metrics(const float* H, const float* w_pitch_drum, const float* b_pitch_drum, const float* w_pitch_nd,
+                               const float* b_pitch_nd, const float* w_dur, const float* b_dur, const int32_t* tokens,
+                               const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d, int32_t n_slots,
+                               float grad_scale, const float* dev_scale, float* logits, float* d_logits,
+                               float* db_pitch_drum, float* db_pitch_nd, float* db_dur, double* out, uint16_t* w_planes,
+                               const int32_t* row_lists, const int32_t* row_counts, const uint8_t* is_drum /* [N] or NULL */,
+                               uint8_t* verdict /* [2 N n_slots] */, int64_t* counts /* [16] */, pm_stream_t stream);
+int pm_content_accuracy_slots(const float* c_logits /* [N,S,230] */, const int32_t* tokens /* [N,16,2] */,
+                              const uint8_t* is_drum /* [N] or NULL */, int32_t N, int32_t n_slots,
+                              uint8_t* verdict /* [2 N S] */, int64_t* counts /* [16] */, pm_stream_t stream);
+int pm_train_metric_counts(const int32_t* tokens, const uint8_t* is_drum, const uint8_t* verdict, int32_t N, int32_t n_slots,
+                           const float* s_logits /* or NULL */, const float* s_target, int64_t n_cells,
+                           int64_t* counts /* [16] */, pm_stream_t stream);
+
 /* ------------------------------------------------------------------ optimiser (train.py:181, training.py:160-166)
  * torch.optim.Adam (no weight decay, no amsgrad) over one flat fp32 buffer. */
 int pm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -979,6 +1013,12 @@ int pm_bn_relu_decisions(const float* x /* [rows,C] */, const float* mean, const
  * four backward calls the caller hands in the gradients of the four outputs (any may be NULL = zero; d_c_logits covers the
  * step's S slots, [N, S, 230]; d_s_logits != NULL switches the structure decoder's backward on).  They replace the
  * gradients of the step's own loss kernels. */
+/* Training accuracies of the step (host only, no GPU work): every following pm_vae_step_forward on `state` (until the next call)
+ * writes the counts row of its batch into `counts` (device int64 [16], the layout of pm_train_metric_counts; NULL = off, the
+ * default).  The fused head's metrics instantiation writes the verdicts (the unfused head: pm_content_accuracy_slots), one
+ * count launch behind the structure loss joins them; no host synchronisation.  The verdicts take 2 N S bytes at the end of the
+ * workspace (pm_vae_step_workspace_bytes includes them).  A forward with PmBatch.flags bit 3 (the caller's loss) counts nothing. */
+int pm_vae_step_set_metrics(void* state, int64_t* counts);
 int pm_vae_step_set_output_grads(void* state, const float* d_s_logits /* [G,4,32] */, const float* d_c_logits /* [N,S,230] */,
                                  const float* d_mu /* [B,d] */, const float* d_log_var /* [B,d] */, pm_stream_t stream);
 /* The outputs of the last forward and the buffers their gradients are read from, as byte offsets into the workspace given to

@@ -160,6 +160,11 @@ _SIGS = {
     "pm_grad_nonfinite_check": "plpppfffis",
     "pm_adam_step_guarded": "pppplffffps",
     "pm_adam_bias_scalars": "plfffps",
+    "pm_vae_step_set_metrics": "pp",
+    "pm_unembed_ce_metrics": "pppppppppiiiiifppppppppppps",
+    "pm_unembed_ce_rows_metrics": "pppppppppiiiiifppppppppppppps",
+    "pm_content_accuracy_slots": "pppiipps",
+    "pm_train_metric_counts": "pppiipplps",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",

@@ -348,3 +348,111 @@ extern "C" int pm_structure_metrics(const float* s_logits, const float* s_target
                      reinterpret_cast<unsigned long long*>(counts));
   return pm_check_launch();
 }
+
+// ---------------------------------------------------------------- training accuracies (training.py:174-179)
+// The step's accuracies are counted on the logits it trains on, in two parts.  A producer writes one VERDICT byte per
+// (node, active slot) row r and vocabulary: verdict[r] (pitch), verdict[R + r] (duration), R = N S, = 1 where the row's arg-max
+// is its target, for every row whose target is not PAD (0 or 1: nothing of an earlier step survives in a byte that is read), and
+// clears counts[0..15].  Producers: the metrics instantiations of the fused un-embedding + CE (unembed.hip), and k_content_verdict
+// below on materialised logits.  Then k_metric_counts joins the two verdicts of a row (note = pitch AND duration) with the
+// targets and `is_drum`, and adds the structure counts of pm_structure_metrics on the same launch.
+// counts[0..7]: the layout of pm_content_accuracy; [8..11]: of pm_structure_metrics; [12]: structure cells; [13..15]: 0.
+//
+// one wave per row, the arg-max rule of k_content_accuracy; logits [N, S, 230] (the S active slots)
+__global__ void __launch_bounds__(256) k_content_verdict(const float* __restrict__ logits, const int* __restrict__ tok, int64_t rows,
+                                                         int S, uint8_t* __restrict__ verdict, unsigned long long* __restrict__ counts) {
+  if (blockIdx.x == 0 && threadIdx.x < 16) counts[threadIdx.x] = 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t n = row / S;
+    const int s = (int)(row - n * S) + 1;
+    const float* x = logits + row * PM_N_TOK;
+    float bp = -INFINITY, bd = -INFINITY;
+    int ip = 0x7fffffff, id = 0x7fffffff;
+    for (int i = lane; i < PM_N_TOK; i += 64) {
+      const float v = x[i];
+      if (i < PM_N_PITCH) { if (v > bp) { bp = v; ip = i; } }
+      else if (v > bd) { bd = v; id = i - PM_N_PITCH; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float op = __shfl_xor(bp, o, 64), od = __shfl_xor(bd, o, 64);
+      const int jp = __shfl_xor(ip, o, 64), jd = __shfl_xor(id, o, 64);
+      if (op > bp || (op == bp && jp < ip)) { bp = op; ip = jp; }
+      if (od > bd || (od == bd && jd < id)) { bd = od; id = jd; }
+    }
+    if (lane == 0) {
+      const int tp = tok[(n * 16 + s) * 2], td = tok[(n * 16 + s) * 2 + 1];
+      if (tp != PM_N_PITCH - 1) verdict[row] = ip == tp;
+      if (td != PM_N_DUR - 1) verdict[rows + row] = id == td;
+    }
+  }
+}
+// counts[0..6] += the joined verdicts of the R rows, counts[8..11] += the structure counts of n_cells cells (s_logits NULL: none),
+// counts[12] += n_cells (all of them cleared by the producer)
+__global__ void __launch_bounds__(256) k_metric_counts(const int* __restrict__ tok, const uint8_t* __restrict__ is_drum,
+                                                       const uint8_t* __restrict__ verdict, int64_t R, int S,
+                                                       const float* __restrict__ s_logits, const float* __restrict__ s_target,
+                                                       int64_t n_cells, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int sh[4][11];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned int c[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t g0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gs = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t r = g0; r < R; r += gs) {
+    const int64_t n = r / S;
+    const int s = (int)(r - n * S) + 1;
+    const int tp = tok[(n * 16 + s) * 2], td = tok[(n * 16 + s) * 2 + 1];
+    const bool np_ = tp != PM_N_PITCH - 1, nd_ = td != PM_N_DUR - 1;     // (a byte is read only where the producer wrote it)
+    const bool cp = np_ && verdict[r] != 0, cd = nd_ && verdict[R + r] != 0;
+    const bool drum = is_drum[n] != 0;
+    c[0] += cp; c[1] += np_; c[2] += cp && drum; c[3] += np_ && drum; c[4] += cd; c[5] += nd_; c[6] += cp && cd;
+  }
+  if (s_logits)
+    for (int64_t i = g0; i < n_cells; i += gs) {                        // k_structure_metrics
+      const float p = 1.0f / (1.0f + expf(-s_logits[i]));
+      const bool pred = p >= 0.5f, t = s_target[i] != 0.f;
+      c[7] += pred == t; c[8] += pred && t; c[9] += pred; c[10] += t;
+    }
+#pragma unroll
+  for (int k = 0; k < 11; ++k) {
+    unsigned int v = c[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) sh[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 11) {
+    const unsigned int v = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (v) atomicAdd(&counts[threadIdx.x < 7 ? threadIdx.x : threadIdx.x + 1], (unsigned long long)v);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && s_logits && n_cells) atomicAdd(&counts[12], (unsigned long long)n_cells);
+}
+extern "C" int pm_train_metric_counts(const int32_t* tokens, const uint8_t* is_drum, const uint8_t* verdict, int32_t N,
+                                      int32_t n_slots, const float* s_logits, const float* s_target, int64_t n_cells,
+                                      int64_t* counts, pm_stream_t stream) {
+  if (!tokens || !is_drum || !verdict || !counts || N <= 0 || n_slots < 1 || n_slots > PM_N_SLOTS || n_cells < 0 ||
+      (s_logits != nullptr) != (s_target != nullptr) || (s_logits && n_cells == 0))
+    return PM_E_INVALID;
+  const int64_t R = (int64_t)N * n_slots;
+  // (256 workgroups: 11 us at configs[1]; 64 workgroups with 4x the rows per thread took 30 us — the loop's loads are
+  //  latency-bound — so the partial counts are left to meet in 11 atomics per workgroup)
+  int nb = (int)pm_cdiv(R > n_cells ? R : n_cells, 256 * 4);
+  if (nb > 256) nb = 256;
+  hipLaunchKernelGGL(k_metric_counts, dim3(nb), dim3(256), 0, (hipStream_t)stream, tokens, is_drum, verdict, R, n_slots, s_logits,
+                     s_target, n_cells, reinterpret_cast<unsigned long long*>(counts));
+  return pm_check_launch();
+}
+// pm_content_accuracy for logits of the S active slots, [N, S, 230] (the step's unfused head; pm_vae_step_outputs): the
+// verdicts of k_content_verdict, then (is_drum != NULL) the join into counts[0..6]; counts [16], verdict [2 N S] bytes
+extern "C" int pm_content_accuracy_slots(const float* c_logits, const int32_t* tokens, const uint8_t* is_drum, int32_t N,
+                                         int32_t n_slots, uint8_t* verdict, int64_t* counts, pm_stream_t stream) {
+  if (!c_logits || !tokens || !verdict || !counts || N <= 0 || n_slots < 1 || n_slots > PM_N_SLOTS) return PM_E_INVALID;
+  const int64_t rows = (int64_t)N * n_slots;
+  int nb = (int)pm_cdiv(rows, 4);
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(k_content_verdict, dim3(nb), dim3(256), 0, (hipStream_t)stream, c_logits, tokens, rows, n_slots, verdict,
+                     reinterpret_cast<unsigned long long*>(counts));
+  const int rc = pm_check_launch();
+  if (rc != PM_OK || !is_drum) return rc;
+  return pm_train_metric_counts(tokens, is_drum, verdict, N, n_slots, nullptr, nullptr, 0, counts, stream);
+}

@@ -37,11 +37,17 @@ struct UnembedArgs {
   float* logits; float* dlogits; double* out;
   int R, S, d, dh; float grad_scale;
   unsigned* gate;                                      // deterministic mode (common.h): workgroups add bias gradients / losses in turn
+  // training accuracies (the MET instantiations only): verdict[r] / verdict[R + r] = 1 where the arg-max of row r's pitch /
+  // duration logits is its target (written for every row with rg >= 0 and a non-PAD target, 0 or 1); mcounts [16] cleared
+  uint8_t* verdict; unsigned long long* mcounts;
 };
 
 #ifndef PM_UNEMBED_WAVES
 #define PM_UNEMBED_WAVES 3
 #endif
+// MET: also the arg-max verdict of every counted row (training accuracies, pm_unembed_ce_metrics); MET = false is the step's
+// default code, unchanged
+template <bool MET>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PM_UNEMBED_WAVES, PM_UNEMBED_WAVES)))
     k_unembed_ce(UnembedArgs a) {
   // one LDS buffer: the two k-major operand images during the k loop, then the tile's logits [64][ULDB] for the row-wise
@@ -55,6 +61,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PM_UNE
   const UnembedJob jb = a.job[blockIdx.y];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
   const int wr = wave >> 1, wc = wave & 1;
+  if constexpr (MET)                                               // (the count launch behind this one adds into them)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < 16) a.mcounts[tid] = 0;
   const int M = jb.dyn_rows ? *jb.dyn_rows : a.R;
   const int nblk = (jb.V + 31) >> 5, c0 = (nblk + 1) >> 1;
   const int cb0 = wc ? c0 : 0, ncb = wc ? nblk - c0 : c0;          // this wave's 32-column blocks [cb0, cb0 + ncb)
@@ -176,6 +184,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PM_UNE
       for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
         for (int u = 0; u < 4; ++u) mx[u] = fmaxf(mx[u], __shfl_xor(mx[u], o, 64));
+      if constexpr (MET) {
+        // arg-max beside the soft-max, with the rule of k_content_accuracy (loss.hip): strict compare in column order inside a
+        // lane, then the lower index among equal values across lanes
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          float bv = -INFINITY;
+          int bi = 0x7fffffff;
+#pragma unroll
+          for (int q = 0; q < 3; ++q)
+            if (v[u][q] > bv) { bv = v[u][q]; bi = lane + 64 * q; }
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+          }
+          if (lane == 0 && rg[u] >= 0 && tg[u] != jb.pad) a.verdict[(jb.kind ? (int64_t)a.R : 0) + rg[u]] = bi == tg[u];
+        }
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float m2 = mx[u] * LOG2E;
@@ -270,7 +297,7 @@ __global__ void __launch_bounds__(256) k_unembed_wplanes(UnembedArgs a, uint16_t
 constexpr int UBD = 2;                                  // k-steps of weight fragments in flight per MFMA wave
 constexpr int PNW = 5;                                  // MFMA waves = 32-column blocks of the widest vocabulary (131 -> 160)
 constexpr int PLDL = PNW * 32 + 4;                      // row pitch of the logits tile
-template <int DH>
+template <int DH, bool MET>
 __global__ void __launch_bounds__(PNW * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) k_unembed_ce_planes(UnembedArgs a, const char* __restrict__ wplanes, int o1, int o2,
                                                                 float* __restrict__ dbrep, double* __restrict__ lossrep) {
   constexpr int RB = DH * 2, PL = UBM * RB, KS = DH / 16, SWZ = (DH / 8 - 1) < 15 ? (DH / 8 - 1) : 15;
@@ -282,6 +309,7 @@ __global__ void __launch_bounds__(PNW * 64) __attribute__((amdgpu_waves_per_eu(3
   int* const s_tgt = s_row + UBM;
   double* const s_loss = reinterpret_cast<double*>(s_tgt + UBM);     // [PNW] (all of it dynamic: the image may take 96 KB)
   float* const s_red = reinterpret_cast<float*>(s_loss + PNW);       // [UBM][PNW][2]: per (row, 32-column segment) max and sum
+  int* const s_idx = reinterpret_cast<int*>(s_red + UBM * PNW * 2);   // [UBM][PNW] (MET only): first column of the segment's max
   const UnembedJob jb = a.job[blockIdx.y];
   const char* const wf = wplanes + 2 * (int64_t)(blockIdx.y == 0 ? 0 : (blockIdx.y == 1 ? o1 : o2));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
@@ -291,6 +319,8 @@ __global__ void __launch_bounds__(PNW * 64) __attribute__((amdgpu_waves_per_eu(3
   const double nval = rows15 - (double)(jb.kind == 0 ? a.hist[0 * PM_N_PITCH + 130] + a.hist[1 * PM_N_PITCH + 130]
                                                      : a.hist[2 * PM_N_PITCH + 98] + a.hist[3 * PM_N_PITCH + 98]);
   const float gk = a.grad_scale * (float)(1.0 / nval) * (a.dev_scale ? a.dev_scale[jb.kind] : 1.f);
+  if constexpr (MET)                                               // (the count launch behind this one adds into them)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < 16) a.mcounts[tid] = 0;
   const int mycol = wave * 32 + li;
   const float bcol = (wave < nblk && mycol < jb.V) ? jb.bias[mycol] : 0.f;
   float dbacc[3] = {0.f, 0.f, 0.f};                              // bias gradient of columns lane + 64 q (store phase)
@@ -414,6 +444,24 @@ __global__ void __launch_bounds__(PNW * 64) __attribute__((amdgpu_waves_per_eu(3
       }
       __syncthreads();
     }
+    if constexpr (MET) {
+      // arg-max of thread (row = lane, segment = wave)'s 32 logits, read from the tile before the soft-max loads them (beside
+      // it, the extra registers spilled): strict compare in column order = the first column of the segment's max
+      const float* const lrow = sL + lane * PLDL + wave * 32;
+      float bv = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float4 t = *reinterpret_cast<const float4*>(lrow + 4 * i);
+        const float x[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int cc = wave * 32 + 4 * i + k;
+          if (cc < jb.V && x[k] > bv) { bv = x[k]; bi = cc; }
+        }
+      }
+      s_idx[lane * PNW + wave] = bi;                              // (read behind the barrier of the segments' max / sum)
+    }
     {
       const int r = lane, c0 = wave * 32;
       const int rg = s_row[r], tg = s_tgt[r];
@@ -462,6 +510,17 @@ __global__ void __launch_bounds__(PNW * 64) __attribute__((amdgpu_waves_per_eu(3
         *reinterpret_cast<float4*>(lrow + 4 * i) = t;
       }
       if (vrow && tg >= c0 && tg < c0 + 32) lloss += __logf(ssum) + mx - vt;
+      if constexpr (MET) {
+        // the row's prediction: the lowest first-index among the segments whose max is the row's (= k_content_accuracy's first
+        // index on ties); one thread per row writes the verdict (s_red / s_idx stay until the next tile)
+        if (wave == 0 && vrow) {
+          int p = 0x7fffffff;
+#pragma unroll
+          for (int w = 0; w < PNW; ++w)
+            if (s_red[(r * PNW + w) * 2] == mx) p = min(p, s_idx[r * PNW + w]);
+          a.verdict[(jb.kind ? (int64_t)a.R : 0) + rg] = p == tg;
+        }
+      }
     }
     __syncthreads();
     for (int r = wave; r < UBM; r += PNW) {
@@ -538,7 +597,8 @@ static int unembed_ce_impl(const float* H, const float* w_pitch_drum, const floa
                            const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d, int32_t n_slots,
                            float grad_scale, const float* dev_scale, float* logits, float* d_logits,
                            float* db_pitch_drum, float* db_pitch_nd, float* db_dur, double* out, uint16_t* w_planes,
-                           const int32_t* row_lists, const int32_t* row_counts, pm_stream_t stream) {
+                           const int32_t* row_lists, const int32_t* row_counts, pm_stream_t stream,
+                           uint8_t* verdict = nullptr, int64_t* mcounts = nullptr) {
   if (!H || !w_pitch_drum || !b_pitch_drum || !w_pitch_nd || !b_pitch_nd || !w_dur || !b_dur || !tokens || !plan ||
       !d_logits || !out || N <= 0 || d <= 0 || (d & 7) || n_slots < 1 || n_slots > PM_N_SLOTS)
     return PM_E_INVALID;
@@ -559,6 +619,8 @@ static int unembed_ce_impl(const float* H, const float* w_pitch_drum, const floa
   a.H = H; a.tok = tokens; a.hist = pv.tok_hist; a.dev_scale = dev_scale; a.logits = logits; a.dlogits = d_logits; a.out = out;
   a.R = (int)R; a.S = n_slots; a.d = d; a.dh = dh; a.grad_scale = grad_scale;
   a.gate = nullptr;
+  a.verdict = verdict; a.mcounts = reinterpret_cast<unsigned long long*>(mcounts);
+  const bool met = mcounts != nullptr;
   int nb = (int)pm_cdiv(R, UBM);
   if (w_planes && (dh == 64 || dh == 128 || dh == 256) && !((uintptr_t)w_planes % 16) && !((uintptr_t)H % 16) &&
       R * (int64_t)d * 4 < 0x7fffffffLL) {
@@ -570,18 +632,23 @@ static int unembed_ce_impl(const float* H, const float* w_pitch_drum, const floa
     a.gate = pm_det_gate(st);
     if (nb > 512) nb = 512;
     const size_t img = (size_t)3 * UBM * dh * 2, tile = (size_t)UBM * PLDL * 4;
-    const size_t lds = (img > tile ? img : tile) + 2 * UBM * sizeof(int) + PNW * sizeof(double) + (size_t)UBM * PNW * 2 * sizeof(float);
-#define LAUNCH(DHV)                                                                                                    \
+    const size_t lds = (img > tile ? img : tile) + 2 * UBM * sizeof(int) + PNW * sizeof(double) + (size_t)UBM * PNW * 2 * sizeof(float) +
+                       (met ? (size_t)UBM * PNW * sizeof(int) : 0);          // (MET: the segments' arg-max columns)
+#define LAUNCH(DHV, MV)                                                                                                \
   do {                                                                                                                 \
     static bool once_dev[16] = {}; bool& once = once_dev[pm_device_slot()];                                                                                          \
     if (!once) {                                                                                                       \
-      hipFuncSetAttribute((const void*)k_unembed_ce_planes<DHV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      hipFuncSetAttribute((const void*)k_unembed_ce_planes<DHV, MV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       once = true;                                                                                                     \
     }                                                                                                                  \
-    hipLaunchKernelGGL((k_unembed_ce_planes<DHV>), dim3(nb, 3), dim3(PNW * 64), lds, st, a,                            \
+    hipLaunchKernelGGL((k_unembed_ce_planes<DHV, MV>), dim3(nb, 3), dim3(PNW * 64), lds, st, a,                        \
                        reinterpret_cast<const char*>(w_planes), o1, o2, dbrep, lossrep);                               \
   } while (0)
-    if (dh == 256) LAUNCH(256); else if (dh == 128) LAUNCH(128); else LAUNCH(64);
+    if (met) {
+      if (dh == 256) LAUNCH(256, true); else if (dh == 128) LAUNCH(128, true); else LAUNCH(64, true);
+    } else {
+      if (dh == 256) LAUNCH(256, false); else if (dh == 128) LAUNCH(128, false); else LAUNCH(64, false);
+    }
 #undef LAUNCH
     hipLaunchKernelGGL(k_unembed_fold, dim3(1), dim3(512), 0, st, a, dbrep, lossrep);
     return pm_check_launch();
@@ -589,7 +656,8 @@ static int unembed_ce_impl(const float* H, const float* w_pitch_drum, const floa
   hipMemsetAsync(out, 0, 2 * sizeof(double), st);
   if (nb > 768) nb = 768;                              // persistent: ~3 resident workgroups per CU and job
   a.gate = pm_det_gate(st);
-  hipLaunchKernelGGL(k_unembed_ce, dim3(nb, 3), dim3(256), 0, st, a);
+  if (met) hipLaunchKernelGGL(k_unembed_ce<true>, dim3(nb, 3), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_unembed_ce<false>, dim3(nb, 3), dim3(256), 0, st, a);
   return pm_check_launch();
 }
 extern "C" int pm_unembed_ce(const float* H, const float* w_pitch_drum, const float* b_pitch_drum, const float* w_pitch_nd,
@@ -615,6 +683,41 @@ extern "C" int pm_unembed_ce_rows(const float* H, const float* w_pitch_drum, con
   return unembed_ce_impl(H, w_pitch_drum, b_pitch_drum, w_pitch_nd, b_pitch_nd, w_dur, b_dur, tokens, plan, N, E, G, d, n_slots,
                          grad_scale, dev_scale, logits, d_logits, db_pitch_drum, db_pitch_nd, db_dur, out, w_planes, row_lists,
                          row_counts, stream);
+}
+// ... and the training accuracies of the same launch (the reference's `_accuracies` on the logits the step trains on): the
+// metrics instantiation of the kernel writes one verdict byte per counted row and job into `verdict` [2 N n_slots] (pitch rows,
+// then duration rows) and clears counts[0..15]; then pm_train_metric_counts (loss.hip) joins the pitch and duration verdicts of
+// every row into counts[0..6] (the layout of pm_content_accuracy).  is_drum NULL: the verdicts and the cleared counts only —
+// the caller issues pm_train_metric_counts itself (the training step, which adds the structure counts to the same launch).
+static int unembed_ce_metrics_tail(const int32_t* tokens, const uint8_t* is_drum, uint8_t* verdict, int32_t N, int32_t n_slots,
+                                   int64_t* counts, pm_stream_t stream) {
+  if (!is_drum) return PM_OK;
+  return pm_train_metric_counts(tokens, is_drum, verdict, N, n_slots, nullptr, nullptr, 0, counts, stream);
+}
+extern "C" int pm_unembed_ce_metrics(const float* H, const float* w_pitch_drum, const float* b_pitch_drum, const float* w_pitch_nd,
+                                     const float* b_pitch_nd, const float* w_dur, const float* b_dur, const int32_t* tokens,
+                                     const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d, int32_t n_slots,
+                                     float grad_scale, const float* dev_scale, float* logits, float* d_logits,
+                                     float* db_pitch_drum, float* db_pitch_nd, float* db_dur, double* out, uint16_t* w_planes,
+                                     const uint8_t* is_drum, uint8_t* verdict, int64_t* counts, pm_stream_t stream) {
+  if (!verdict || !counts) return PM_E_INVALID;
+  const int rc = unembed_ce_impl(H, w_pitch_drum, b_pitch_drum, w_pitch_nd, b_pitch_nd, w_dur, b_dur, tokens, plan, N, E, G, d,
+                                 n_slots, grad_scale, dev_scale, logits, d_logits, db_pitch_drum, db_pitch_nd, db_dur, out, w_planes,
+                                 nullptr, nullptr, stream, verdict, counts);
+  return rc != PM_OK ? rc : unembed_ce_metrics_tail(tokens, is_drum, verdict, N, n_slots, counts, stream);
+}
+extern "C" int pm_unembed_ce_rows_metrics(const float* H, const float* w_pitch_drum, const float* b_pitch_drum,
+                                          const float* w_pitch_nd, const float* b_pitch_nd, const float* w_dur, const float* b_dur,
+                                          const int32_t* tokens, const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d,
+                                          int32_t n_slots, float grad_scale, const float* dev_scale, float* logits, float* d_logits,
+                                          float* db_pitch_drum, float* db_pitch_nd, float* db_dur, double* out, uint16_t* w_planes,
+                                          const int32_t* row_lists, const int32_t* row_counts, const uint8_t* is_drum,
+                                          uint8_t* verdict, int64_t* counts, pm_stream_t stream) {
+  if (!row_lists || !row_counts || !verdict || !counts) return PM_E_INVALID;
+  const int rc = unembed_ce_impl(H, w_pitch_drum, b_pitch_drum, w_pitch_nd, b_pitch_nd, w_dur, b_dur, tokens, plan, N, E, G, d,
+                                 n_slots, grad_scale, dev_scale, logits, d_logits, db_pitch_drum, db_pitch_nd, db_dur, out, w_planes,
+                                 row_lists, row_counts, stream, verdict, counts);
+  return rc != PM_OK ? rc : unembed_ce_metrics_tail(tokens, is_drum, verdict, N, n_slots, counts, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

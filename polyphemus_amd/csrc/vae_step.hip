@@ -185,6 +185,8 @@ struct StepState {
   int rc;
   unsigned br_open;                       // branches issued on the second stream and not yet joined (bit = site)
   int ext_loss;                           // pm_vae_step_set_output_grads: the gradients of the outputs came from the caller's loss
+  int64_t* metrics;                       // pm_vae_step_set_metrics: the counts row of the training accuracies (kept across forwards)
+  uint8_t* verdict;                       // ... and their verdict bytes [2 N S], at the end of the workspace
 };
 constexpr uint64_t kMagic = 0x504d5354455031ULL;
 
@@ -1012,7 +1014,25 @@ void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
     // PmBatch.flags bit 3 (the drop-in module: the CALLER computes the loss): the logits only — three fp32 products, no
     // cross-entropy, no d(logits) (224 MB at 15 slots that pm_vae_step_set_output_grads would overwrite), no KLD / BCE
     const bool logits_only = (s.bt.flags & 8) != 0;
-    if (fused_ce && !logits_only && s.pad_skip) {
+    // training accuracies (pm_vae_step_set_metrics): the head's metrics form writes the verdict bytes and clears the counts row,
+    // one count launch behind the structure loss joins them — the default head's launches are the ones above when off
+    int64_t* const met = logits_only ? nullptr : s.metrics;
+    if (fused_ce && !logits_only && s.pad_skip && met) {
+      RUN(pm_unembed_ce_rows_metrics(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
+                                       c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
+                                       (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
+                                       c.G + Y.dec_dur.b, s.losses, w_unembed, s.ue_lists, s.ue_counts, nullptr, s.verdict, met, c.st));
+      if (s.bt.flags & 4)            // (the rows left out have PAD targets: no verdict)
+        RUN(pm_unembed_ce_rows(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
+                                 c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
+                                 s.c_logits, s.dc_logits, nullptr, nullptr, nullptr, pad_losses, w_unembed, s.ue_lists + 3 * R,
+                                 s.ue_counts + 4, c.st));
+    } else if (fused_ce && !logits_only && met) {
+      RUN(pm_unembed_ce_metrics(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
+                                  c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
+                                  (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
+                                  c.G + Y.dec_dur.b, s.losses, w_unembed, nullptr, s.verdict, met, c.st));
+    } else if (fused_ce && !logits_only && s.pad_skip) {
       RUN(pm_unembed_ce_rows(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
                                c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
                                (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
@@ -1037,11 +1057,17 @@ void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
     if (!logits_only)
     RUN(pm_content_ce_scaled(s.c_logits, s.bt.tokens, pv.tok_hist, s.bt.is_drum, N, S, 1.0f, s.bt.ce_scale, s.dc_logits,
                                c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, s.losses, c.st));
+    if (met) RUN(pm_content_accuracy_slots(s.c_logits, s.bt.tokens, nullptr, N, S, s.verdict, met, c.st));
     }
     branch_join(c, BR_LOSSES);                     // (the KL term and the constant structure loss, issued behind the reparametrisation)
     branch_join(c, BR_DEC_FWD);
     if (!logits_only && s.fix_structure)
       RUN(pm_bce_logits_acc(s.s_logits, s.bt.s_tensor, (int64_t)Gn * 128, 1.0f, s.ds_logits, s.losses, c.st));
+    // the join of the verdicts + the structure counts, on the structure loss's input (the target itself unless
+    // structure_loss_on_logits: SURVEY B-1, as evaluate_batch)
+    if (met)
+      RUN(pm_train_metric_counts(s.bt.tokens, s.bt.is_drum, s.verdict, N, S, s.fix_structure ? s.s_logits : s.bt.s_tensor,
+                                 s.bt.s_tensor, (int64_t)Gn * 128, met, c.st));
   }
 }
 
@@ -1347,6 +1373,10 @@ static void measure_step(const PmVaeLayout* lay, const PmBatch& bt, size_t* zero
   *main_bytes = s.ar.used;
 }
 
+// the training accuracies' verdict bytes [2 N S] at the end of the workspace (behind everything the step carves: the offsets of
+// the arena do not depend on whether the metrics are armed)
+static size_t metrics_tail_bytes(int32_t N, int32_t S) { return ((size_t)2 * N * S + 255) & ~size_t(255); }
+
 extern "C" int64_t pm_vae_step_workspace_bytes(const PmVaeLayout* lay, int32_t N, int32_t E, int32_t G, int32_t B,
                                                int32_t n_slots) {      // sized for the non-compact (7d) aggregates
   if (!lay || N <= 0 || E <= 0 || G <= 0 || B <= 0 || lay->n_layers > PM_MAX_LAYERS || n_slots < 1 ||
@@ -1362,7 +1392,7 @@ extern "C" int64_t pm_vae_step_workspace_bytes(const PmVaeLayout* lay, int32_t N
     measure_step(lay, bt, &zb, &mb);
     if (zb + mb > need) need = zb + mb;
   }
-  return (int64_t)need + 4096;
+  return (int64_t)need + 4096 + metrics_tail_bytes(N, n_slots);
 }
 
 extern "C" int pm_vae_step_forward(const PmVaeLayout* lay, const float* params, float* buffers, float* grads,
@@ -1376,7 +1406,9 @@ extern "C" int pm_vae_step_forward(const PmVaeLayout* lay, const float* params, 
       batch->n_slots < 1 || batch->n_slots > PM_N_SLOTS)
     return PM_E_INVALID;
   StepState* s = (StepState*)state;
+  int64_t* const metrics = s->metrics;                 // (pm_vae_step_set_metrics: armed until called again)
   memset(s, 0, sizeof(*s));
+  s->metrics = metrics;
   s->magic = kMagic; s->lay = *lay; s->P = params; s->Bf = buffers; s->G = grads; s->bt = *batch; s->plan = plan;
   s->eps = eps; s->losses = losses; s->beta = beta; s->fix_structure = structure_loss_on_logits;
   s->ar.base = (char*)workspace; s->ar.cap = (size_t)workspace_bytes; s->ar.used = 0; s->ar.overflow = false;
@@ -1386,6 +1418,11 @@ extern "C" int pm_vae_step_forward(const PmVaeLayout* lay, const float* params, 
   size_t zb, mb;
   measure_step(lay, *batch, &zb, &mb);
   if (zb + mb > (size_t)workspace_bytes) return PM_E_INVALID;
+  if (metrics) {
+    const size_t tail = metrics_tail_bytes(batch->N, batch->n_slots);
+    if (zb + mb + tail + 256 > (size_t)workspace_bytes) return PM_E_INVALID;     // (+ the alignment below)
+    s->verdict = (uint8_t*)workspace + (((size_t)workspace_bytes - tail) & ~size_t(255));
+  }
   s->ar.zcap = zb; s->ar.zused = 0;
   // A previous step that was abandoned between two of its calls (an exception in the caller) may have left a branch
   // running on the second stream that still reads and writes the arena: this step's first write waits for whatever
@@ -1400,6 +1437,11 @@ extern "C" int pm_vae_step_forward(const PmVaeLayout* lay, const float* params, 
   if (s->ar.overflow) return PM_E_INVALID;
   s->rc = c.rc;
   return c.rc;
+}
+extern "C" int pm_vae_step_set_metrics(void* state, int64_t* counts) {
+  if (!state) return PM_E_INVALID;
+  ((StepState*)state)->metrics = counts;
+  return PM_OK;
 }
 // Which variant of the step the last pm_vae_step_forward selected (host only): the parity tests assert that the path
 // they pin to the reference goldens is the path bench.py measures.

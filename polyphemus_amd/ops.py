@@ -626,6 +626,35 @@ def content_accuracy(c_logits, tokens, is_drum):
     return out
 
 
+def content_accuracy_slots(c_logits, tokens, is_drum):
+    """`content_accuracy` for logits of the S active slots, [N, S, 230] (`pm_content_accuracy_slots`): int64 [16] in the layout
+    of the training-accuracy counts row ([0..7] as `content_accuracy`, the rest 0)."""
+    _chk(c_logits, F32, "c_logits"); _chk(tokens, I32, "tokens")
+    drum = is_drum.view(U8) if is_drum.dtype == torch.bool else is_drum
+    N, S = c_logits.shape[0], c_logits.shape[1]
+    verdict = torch.empty(2 * N * S, dtype=U8, device=c_logits.device)
+    out = torch.empty(16, dtype=I64, device=c_logits.device)
+    call("pm_content_accuracy_slots", ptr(c_logits), ptr(tokens), ptr(drum.contiguous()), N, S, ptr(verdict), ptr(out), stream())
+    return out
+
+
+ACCURACY_KEYS = ("note", "pitch", "pitch_drums", "pitch_non_drums", "dur", "s_acc", "s_precision", "s_recall", "s_f1")
+
+
+def accuracies_from_counts(c) -> dict:
+    """The reference's 9 accuracies (`_accuracies`, training.py:349-497) from one counts row (16 numbers: [0..7] of
+    `content_accuracy`, [8..11] of `structure_metrics`, [12] the structure cells).  A zero denominator gives NaN, as the
+    reference's 0 / 0; `s_acc` divides by max(cells, 1)."""
+    c = [float(v) for v in c]
+    m, cells = c[8:12], c[12]
+    div = lambda a, b: a / b if b else float("nan")
+    prec, rec = div(m[1], m[2]), div(m[1], m[3])
+    return {"note": div(c[6], c[1]), "pitch": div(c[0], c[1]), "pitch_drums": div(c[2], c[3]),
+            "pitch_non_drums": div(c[0] - c[2], c[1] - c[3]), "dur": div(c[4], c[5]),
+            "s_acc": m[0] / max(cells, 1), "s_precision": prec, "s_recall": rec,
+            "s_f1": div(2 * rec * prec, rec + prec)}
+
+
 def structure_metrics(s_logits, s_target):
     """int64 [4] = {prediction == target, true positives, predicted positives, target positives} (training.py:470-497)."""
     _chk(s_logits, F32, "s_logits"); _chk(s_target, F32, "s_target")

@@ -69,9 +69,13 @@ class HipTrainer:
     def __init__(self, vae: VAE, lr=5e-6, betas=(0.9, 0.98), eps=1e-9, lr_scheduler: Optional[dict] = None,
                  structure_loss_on_logits: bool = False, beta: float = 0.0, process_group=None, native: bool = True,
                  iters_to_accumulate: int = 1, global_token_mean: bool = False, sync_bn: bool = False,
-                 overflow: str = "ignore"):
+                 overflow: str = "ignore", train_metrics: bool = False, metrics_capacity: int = 1024):
         if overflow not in ("ignore", "skip"):
             raise ValueError(f"overflow must be 'ignore' or 'skip', not {overflow!r}")
+        if not isinstance(train_metrics, bool):
+            raise ValueError(f"train_metrics must be True or False, not {train_metrics!r}")
+        if train_metrics and (not isinstance(metrics_capacity, int) or metrics_capacity < 1):
+            raise ValueError(f"metrics_capacity must be a positive int, not {metrics_capacity!r}")
         self.vae = vae
         self.lr, self.betas, self.eps = lr, betas, eps
         self.sched = ExpDecayLR(**lr_scheduler) if lr_scheduler else None
@@ -125,6 +129,12 @@ class HipTrainer:
             self._ovf_warned = 0
         self.step_count = 0
         self.loss_buf = torch.zeros(4, dtype=torch.float64, device=flat.device)
+        # Training accuracies (the reference's `_accuracies` after every batch, training.py:174-179): one int64 counts row per
+        # batch (ops.accuracies_from_counts has the layout), written by the step on the device into a history of
+        # `metrics_capacity` rows; `read_train_accuracies` takes them with one sync.  Off: nothing of it runs.
+        self.train_metrics = train_metrics
+        self._mhist = torch.zeros(metrics_capacity, 16, dtype=torch.int64, device=flat.device) if train_metrics else None
+        self._mrows = 0                           # rows written since the last read (host count: no sync decides anything)
         P = dict(vae.named_parameters())
         self._G: Dict[str, torch.Tensor] = {}
         for n in vae._param_names:
@@ -221,6 +231,8 @@ class HipTrainer:
             ce_scale = (inputs[9] * float(self.world) / tot).contiguous()      # stays on the device
         if self._guard:                                      # in front of the prologue's weight-plane splits
             call("pm_overflow_snapshot", self._ovf_status.data_ptr(), stream())
+        if self.train_metrics:                               # arm the step on this batch's row (host pointer arithmetic)
+            call("pm_vae_step_set_metrics", step.addr, self._mhist[self._mrows].data_ptr())
         step.forward(graph, eps, self.grads, keep_logits=self.keep_logits, beta=self.beta,
                      fix_structure=self.fix_structure_loss, ce_scale=ce_scale, want_token_counts=gtm)
         if prepare_inputs(graph)[8] and os.environ.get("PM_DEBUG", "0") not in ("", "0"):
@@ -244,6 +256,32 @@ class HipTrainer:
         self.buckets.launch(0)                               # chord encoder, embeddings, structure encoder
         step.bump_counters()
         return step.loss_buf
+
+    @property
+    def last_train_counts(self) -> torch.Tensor:
+        """Device int64 [16] view of the latest batch's training-accuracy counts (layout: `ops.accuracies_from_counts`)."""
+        if not self.train_metrics:
+            raise RuntimeError("last_train_counts needs HipTrainer(..., train_metrics=True)")
+        if self._mrows == 0:
+            raise RuntimeError("no training-accuracy counts since the last read_train_accuracies()")
+        return self._mhist[self._mrows - 1]
+
+    def read_train_accuracies(self, reduce: bool = False) -> list:
+        """One dict of the reference's 9 training accuracies (note, pitch, pitch_drums, pitch_non_drums, dur, s_acc,
+        s_precision, s_recall, s_f1) per `train_step` since the last read, in order — what the reference appends to
+        `tr_accuracies` after every batch (training.py:174-179).  Arg-max over the raw logits, the lowest index on ties.
+        `reduce=True` first sums the counts over the trainer's process group: the accuracies one device would report on the
+        concatenated batch.  One host sync; empties the history."""
+        if not self.train_metrics:
+            raise RuntimeError("read_train_accuracies needs HipTrainer(..., train_metrics=True)")
+        rows = self._mhist[:self._mrows]
+        if reduce and self.world > 1:
+            import torch.distributed as dist
+            rows = rows.clone()
+            dist.all_reduce(rows, group=self.pg)
+        host = rows.tolist()                               # the one sync
+        self._mrows = 0
+        return [ops.accuracies_from_counts(r) for r in host]
 
     def step_info(self) -> dict:
         """Which variant of the native step the last `train_step` ran (`pm_vae_step_info`): compact GCL (K = 4d),
@@ -292,6 +330,15 @@ class HipTrainer:
         else:                                                # training.py:307: BCE of the target against itself
             ops.bce_logits(s_tensor.reshape(-1), s_tensor.reshape(-1), out, 1.0, want_grad=False)
             ds = None
+        if self.train_metrics:                               # the same counts from this orchestration's own logits
+            row = self._mhist[self._mrows]
+            cl = c_logits.contiguous()
+            row[:8].copy_(ops.content_accuracy(cl, plan.tokens, plan.is_drum) if cl.shape[1] == 15 else
+                          ops.content_accuracy_slots(cl, plan.tokens, plan.is_drum)[:8])
+            s_in = s_logits.reshape(-1).contiguous() if self.fix_structure_loss else s_tensor.reshape(-1)
+            row[8:12].copy_(ops.structure_metrics(s_in, s_tensor.reshape(-1)))
+            row[12].fill_(s_tensor.numel())
+            row[13:].zero_()
         dz = eng.decoder_backward(dsv, ds, dc, G)
         self.buckets.launch(2)
         ops.reparam_bwd(dz, lv, eps, dmu, dlv)
@@ -313,10 +360,15 @@ class HipTrainer:
             raise RuntimeError("the model's flat parameter buffer moved after the trainer was built; rebuild it")
         if self._guard:
             self._warn_skips()
+        if self.train_metrics and self._mrows >= self._mhist.shape[0]:
+            raise RuntimeError(f"the training-accuracy history is full ({self._mhist.shape[0]} unread batches): call "
+                               "read_train_accuracies() first, or build the trainer with a larger metrics_capacity")
         self.grads.zero_()
         k = self.iters_to_accumulate
         self.buckets.hold = k > 1                      # micro-batches of an accumulation are not all-reduced one by one
         out = (self._native_forward_backward if self.native else self._python_forward_backward)(graph, eps)
+        if self.train_metrics:
+            self._mrows += 1                               # (the forward ran: a batch whose update is skipped is recorded too)
         self.micro_batches += 1
         grads = self.grads
         if k > 1:
@@ -376,15 +428,9 @@ class HipTrainer:
         finally:
             vae.train(was_training)
         p, d, s, k = host[:4]
-        c, m = host[4:12], host[12:16]
-        div = lambda a, b: a / b if b else float("nan")
-        prec, rec = div(m[1], m[2]), div(m[1], m[3])
         losses = {"tot": p + d + s + self.beta * k, "pitch": p, "dur": d, "structure": s, "reconstruction": p + d + s,
                   "kld": k, "beta*kld": self.beta * k}
-        accs = {"note": div(c[6], c[1]), "pitch": div(c[0], c[1]), "pitch_drums": div(c[2], c[3]),
-                "pitch_non_drums": div(c[0] - c[2], c[1] - c[3]), "dur": div(c[4], c[5]),
-                "s_acc": m[0] / max(s_t.numel(), 1), "s_precision": prec, "s_recall": rec,
-                "s_f1": div(2 * rec * prec, rec + prec)}
+        accs = ops.accuracies_from_counts(host[4:16] + [s_t.numel(), 0, 0, 0])
         return losses, accs
 
     def evaluate(self, loader):
