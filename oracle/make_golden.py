@@ -31,8 +31,11 @@ What is captured:
                   ahead of BatchNorm, the attention gate's bias), which Adam turns into full-size steps
                   (tests/test_oracle_golden.py, two train steps).
 
-Usage:  python oracle/make_golden.py [generate|d128|bnoff|digests]     (from the repo root; `generate` rewrites only
-        <case>_generate.npz, `d128` only the slim d = 128 case, `digests` only train_digests_mkl_compatible.json)
+  <case>_evalstate.npz  eval mode, metrics and generation under a trained-like BatchNorm state (`capture_evalstate`)
+
+Usage:  python oracle/make_golden.py [generate|d128|bnoff|digests|evalstate]     (from the repo root; `generate` rewrites
+        only <case>_generate.npz, `d128` only the slim d = 128 case, `digests` only train_digests_mkl_compatible.json,
+        `evalstate` only the four <case>_evalstate.npz)
 """
 import hashlib
 import json
@@ -248,22 +251,31 @@ def capture_generation(name):
               `_binary_from_logits` (model.py:609-623) and the resulting mtp.
     The [.,4,32,15,230] pianorolls are stored as a sha256 of their bytes plus per-cell sums; c_logits of the gen path as
     per-node sums, arg-max tokens and the first nodes' rows."""
-    import hashlib
-    os.chdir(REF)
-    import utils as ref_utils
-    os.chdir(_cwd)
     z0 = np.load(os.path.join(REPO, "tests", "golden", f"{name}.npz"))
     cfg = json.loads(str(z0["cfg"]))
     vae = ref_model.VAE(**cfg, device=torch.device("cpu"))
     vae.load_state_dict({k[3:]: torch.from_numpy(z0[k]) for k in z0.files if k.startswith("sd/")})
+    out = generation_captures(vae, cfg, z0["in/eps"], z0["in/s_tensor"], torch.from_numpy(z0["eval/c_logits"]))
+    np.savez_compressed(os.path.join(OUT, f"{name}_generate.npz"), **out)
+    print(f"{name}_generate.npz: gen nodes={int(out['gen/num_nodes'])} active={int(out['gen/s_binary'].sum())} "
+          f"corner on={int(out['corner/s_binary'].sum())}")
+
+
+def generation_captures(vae, cfg, eps, s_tensor, c_logits_eval, write_corner=True):
+    """The cond/*, gen/* (and corner/*) captures of `capture_generation` for the reference model `vae` (put in eval
+    mode here), the case's eps and batch structure, and the eval-mode c_logits of the case's batch."""
+    import hashlib
+    os.chdir(REF)
+    import utils as ref_utils
+    os.chdir(_cwd)
     vae.eval()
     out = {}
-    B, nb = z0["in/eps"].shape[0], cfg["n_bars"]
-    s_cond = torch.from_numpy(z0["in/s_tensor"]).view(B, nb, 4, 32).float()
-    mtp = ref_utils.mtp_from_logits(torch.from_numpy(z0["eval/c_logits"]), s_cond)
+    B, nb = eps.shape[0], cfg["n_bars"]
+    s_cond = torch.from_numpy(s_tensor).view(B, nb, 4, 32).float()
+    mtp = ref_utils.mtp_from_logits(c_logits_eval, s_cond)
     out["cond/mtp_sha256"] = np.array(hashlib.sha256(mtp.numpy().tobytes()).hexdigest())
     out["cond/mtp_cellsum"] = mtp.double().sum(dim=(-1, -2)).numpy()
-    zs = torch.from_numpy(z0["in/eps"]) * 3.0                       # a wider latent sample: more varied structures
+    zs = torch.from_numpy(eps) * 3.0                      # a wider latent sample: more varied structures
     with torch.no_grad():
         s_logits, c_logits = vae.decoder(zs, None)
         s_bin = vae.decoder._binary_from_logits(s_logits)
@@ -276,6 +288,8 @@ def capture_generation(name):
     out["gen/c_argmax"] = np.stack([c_logits[..., :C.N_PITCH_TOKENS].argmax(-1).numpy(),
                                     c_logits[..., C.N_PITCH_TOKENS:].argmax(-1).numpy()], -1).astype(np.int16)
     out["gen/mtp_cellsum"] = mtp.double().sum(dim=(-1, -2)).numpy()
+    if not write_corner:
+        return out
     # threshold corner cases: logits around 0 (sigmoid rounds to exactly 0.5 for tiny negative logits), +-inf, an empty bar
     corner = torch.zeros(1, 4, 4, 32)
     corner[0, 0] = torch.linspace(-2e-7, 2e-7, 128).view(4, 32)
@@ -284,9 +298,7 @@ def capture_generation(name):
     corner[0, 3, 0, :4] = torch.tensor([float("inf"), float("-inf"), 88.0, -104.0])
     out["corner/s_logits"] = corner.numpy()
     out["corner/s_binary"] = vae.decoder._binary_from_logits(corner).numpy().astype(np.uint8)
-    np.savez_compressed(os.path.join(OUT, f"{name}_generate.npz"), **out)
-    print(f"{name}_generate.npz: gen nodes={int(c_logits.shape[0])} active={int(s_bin.sum())} "
-          f"corner on={int(out['corner/s_binary'].sum())}")
+    return out
 
 
 CASES = {
@@ -312,6 +324,104 @@ def capture_bnoff():
 
 def capture_d128():
     capture_case("d128_l2", **CASES["d128_l2"])
+
+
+EVALSTATE_CASES = ["lmd2_tiny", "nb3_tiny", "bnoff_tiny", "d128_l2"]
+# the full [N, 15, 230] eval c_logits of a tiny case are 1.5 MB of incompressible floats: the fixture keeps every node's
+# logits of the first EVALSTATE_C_SLOTS token slots for these cases, and per (node, slot) sums and L2 norms for all
+EVALSTATE_C_SLOT_CASES = ("lmd2_tiny", "bnoff_tiny")
+EVALSTATE_C_SLOTS = 2
+
+
+def capture_evalstate(name):
+    """<case>_evalstate.npz: the eval-mode forward, metrics and generation of the reference under a trained-like
+    BatchNorm state (every other capture runs its norms at their initial state, where eval BN is x * 0.999995).
+    The recipe, deterministic:
+      1. the case's initial state: sd/ of tests/golden/<case>.npz, or for the slim d128_l2 the default init under
+         torch.manual_seed(0); GCL message dropout 0;
+      2. on every _BatchNorm: reset_running_stats(), momentum = None (cumulative average); 3 training-mode forwards
+         under no_grad on the batch of seed `seed + 100` (the case's batch size and density), so the running statistics
+         are realistic and not the eval batch's own; momentum = 0.1 again;
+      3. in named_modules() order, every _BatchNorm's weight = 1 + 0.5 U(-1, 1) and bias = 0.3 N(0, 1) from
+         torch.Generator().manual_seed(seed + 200).
+    Stored: bn/<key> for weight, bias, running_mean, running_var, num_batches_tracked of every norm (the only tensors that
+    change); eval/* outputs (s_logits, mu, log_var; c_logits as per (node, slot) sums and L2 norms, per-node sums and
+    arg-max tokens, plus every node's logits of the first EVALSTATE_C_SLOTS slots for lmd2_tiny / bnoff_tiny); the
+    reference's eval-mode `_losses` / `_accuracies` (metrics/*); cond/z (the eval pass's latent) and the cond/*, gen/*
+    captures of `capture_generation` under this state."""
+    from torch.nn.modules.batchnorm import _BatchNorm
+    args = CASES[name]
+    cfg, seed = args["cfg"], args["seed"]
+    z0 = np.load(os.path.join(REPO, "tests", "golden", f"{name}.npz"))
+    B, nb = z0["in/eps"].shape[0], cfg["n_bars"]
+    disk = [(z0[f"disk/{i}/c_tensor"], z0[f"disk/{i}/s_tensor"]) for i in range(B)]
+    with tempfile.TemporaryDirectory() as td:
+        graph = build_batch(td, disk, nb)
+    assert np.array_equal(graph.edge_index.numpy(), z0["in/edge_index"])
+    rng = np.random.default_rng(seed + 100)
+    with tempfile.TemporaryDirectory() as td:
+        warm = build_batch(td, [disk_sample(rng, nb, args["p"]) for _ in range(args["batch_size"])], nb)
+
+    torch.manual_seed(0)
+    vae = ref_model.VAE(**cfg, device=torch.device("cpu"))
+    if "sd_sha256" not in z0.files:
+        vae.load_state_dict({k[3:]: torch.from_numpy(z0[k]) for k in z0.files if k.startswith("sd/")})
+    for m in vae.modules():
+        if isinstance(m, ref_model.GCL):
+            m.dropout = 0.0
+    bns = [(n, m) for n, m in vae.named_modules() if isinstance(m, _BatchNorm)]
+    for _, m in bns:
+        m.reset_running_stats()
+        m.momentum = None
+    eps = torch.from_numpy(z0["in/eps"])
+    eps_warm = torch.from_numpy(np.random.default_rng(seed + 101).standard_normal((args["batch_size"], cfg["d"])).astype(np.float32))
+
+    def fwd(model, g, e):
+        mu, lv = model.encoder(g)                        # == model.py:668-676 with eps injected
+        z = torch.exp(0.5 * lv) * e + mu
+        s_logits, c_logits = model.decoder(z, g)
+        return s_logits, c_logits, mu, lv, z
+
+    vae.train()
+    with torch.no_grad():
+        for _ in range(3):
+            fwd(vae, warm, eps_warm)
+    gen = torch.Generator().manual_seed(seed + 200)
+    out = {}
+    for n, m in bns:
+        m.momentum = 0.1
+        with torch.no_grad():
+            m.weight.copy_(1 + 0.5 * (2 * torch.rand(m.weight.shape, generator=gen) - 1))
+            m.bias.copy_(0.3 * torch.randn(m.bias.shape, generator=gen))
+        for t in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked"):
+            out[f"bn/{n}.{t}"] = getattr(m, t).detach().numpy().copy()
+
+    vae.eval()
+    with torch.no_grad():
+        s_logits, c_logits, mu, lv, z = fwd(vae, graph, eps)
+    out["eval/s_logits"], out["eval/mu"], out["eval/log_var"] = s_logits.numpy(), mu.numpy(), lv.numpy()
+    if name in EVALSTATE_C_SLOT_CASES:
+        out["eval/c_logits_slots"] = c_logits[:, :EVALSTATE_C_SLOTS].numpy()
+    out["eval/c_logits_slotsum"] = c_logits.double().sum(dim=-1).numpy()
+    out["eval/c_logits_slotnorm"] = c_logits.double().norm(dim=-1).numpy()
+    out["eval/c_logits_nodesum"] = c_logits.double().sum(dim=(-1, -2)).numpy()
+    out["eval/c_argmax"] = np.stack([c_logits[..., :C.N_PITCH_TOKENS].argmax(-1).numpy(),
+                                     c_logits[..., C.N_PITCH_TOKENS:].argmax(-1).numpy()], -1).astype(np.int16)
+    opt = torch.optim.Adam(vae.parameters())
+    trainer = ref_training.PolyphemusTrainer("unused", vae, opt)
+    trainer.beta = 0                                                     # training.py:116
+    with torch.no_grad():
+        _, ev_losses = trainer._losses(graph.s_tensor, s_logits, graph.c_tensor, c_logits, mu, lv)
+        accs = trainer._accuracies(graph.s_tensor, s_logits, graph.c_tensor, c_logits, graph.is_drum)
+    out["metrics/losses"] = np.array(json.dumps({k: float(v) for k, v in ev_losses.items()}))
+    out["metrics/accs"] = np.array(json.dumps(accs))
+    out["cond/z"] = z.numpy()
+    out.update(generation_captures(vae, cfg, z0["in/eps"], z0["in/s_tensor"], c_logits, write_corner=False))
+    path = os.path.join(OUT, f"{name}_evalstate.npz")
+    np.savez_compressed(path, **out)
+    rv = min(float(m.running_var.min()) for _, m in bns) if bns else float("nan")
+    print(f"{name}_evalstate.npz: {len(bns)} norms, min running_var {rv:.3g}, {os.path.getsize(path)} bytes, "
+          f"losses {ev_losses}")
 
 
 def capture_digests():
@@ -347,6 +457,10 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["digests"]:
         capture_digests()
+        sys.exit(0)
+    if sys.argv[1:] == ["evalstate"]:
+        for case in EVALSTATE_CASES:
+            capture_evalstate(case)
         sys.exit(0)
     make_graphs()
     capture_case("lmd2_tiny", **CASES["lmd2_tiny"])

@@ -359,11 +359,12 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     return out
 
 
-def oracle_fullsize(spec, run, dtypes=(("o64", torch.float64), ("o32", torch.float32)), chunk=None, device=None):
+def oracle_fullsize(spec, run, dtypes=(("o64", torch.float64), ("o32", torch.float32)), chunk=None, device=None, states=None):
     """oracle/vae_cpu.py on what `hip_fullsize_step` ran (same weights, eps and — replayed from the counter hash — the
     same message-dropout mask), per dtype: (outputs, losses, gradients), and the seconds each took.  With `chunk` the GCL
     aggregations run edge-chunked on `device` (vae_cpu.chunked_aggregation) and the dropout masks are evaluated per chunk
-    there (`dropout_keep_torch`, nothing cached)."""
+    there (`dropout_keep_torch`, nothing cached).  With a dict `states`, states[tag] receives the buffers (running
+    statistics, num_batches_tracked) the oracle's step left in its state."""
     import contextlib
     import time
     from oracle import vae_cpu
@@ -389,6 +390,8 @@ def oracle_fullsize(spec, run, dtypes=(("o64", torch.float64), ("o32", torch.flo
                                                     keep_mask=keep_mask)
         res[tag] = (dict(zip(("s_logits", "c_logits", "mu", "log_var"), (o.detach() for o in outs))),
                     {k: float(v.detach()) for k, v in parts.items()}, grads)
+        if states is not None:
+            states[tag] = {k: v.detach().clone() for k, v in P.items() if k not in names and ".nn." not in k}
         times[tag] = time.time() - t0
     return res, times
 
@@ -538,3 +541,131 @@ def hip_relu_decisions(live, cfg, lazy=False):
     forced[sites.index("enc_cnn.lin1")] = (saved_tensor(step, "ENC_CNN_LIN1").view(-1, d) > 0).cpu()
     torch.cuda.synchronize()
     return forced
+
+
+# ---- eval mode under a trained-like BatchNorm state (tests/golden/<case>_evalstate.npz, oracle/make_golden.py evalstate) ----
+def load_evalstate(case):
+    """(golden case, cfg, evalstate fixture, state dict): the case's initial state with the fixture's BatchNorm tensors
+    (weight, bias, running statistics, num_batches_tracked of every norm) in place."""
+    z, cfg = load_case(case)
+    ze = np.load(os.path.join(GOLDEN, f"{case}_evalstate.npz"), allow_pickle=False)
+    sd = state_dict_from_golden(z)
+    for k in ze.files:
+        if k.startswith("bn/"):
+            assert k[3:] in sd, k
+            sd[k[3:]] = torch.from_numpy(ze[k].copy())
+    return z, cfg, ze, sd
+
+
+def bn_keys(sd):
+    """The prefixes of every BatchNorm of a state dict, in key order."""
+    return [k[:-len(".running_mean")] for k in sd if k.endswith(".running_mean")]
+
+
+def oracle_structure_logits(z, P, cfg):
+    """The structure half of `Decoder.forward` in eval mode (model.py:634-645) through oracle/vae_cpu.py: what the
+    generation path thresholds before any graph exists."""
+    import torch.nn.functional as F
+    from oracle import vae_cpu
+    h = F.relu(vae_cpu._bn(vae_cpu._lin(z, P, "decoder.lin_decoder"), P, "decoder.batch_norm", False))
+    return vae_cpu.structure_decoder(h[:, :cfg["d"]], P, cfg, False)
+
+
+def host_graph_from_binary(s_bin, n_bars):
+    """The batch of bar graphs of a binary structure [B, n_bars, 4, 32], built by the host builder
+    (polyphemus_amd/graphs.py, the reference's `graph_from_tensor` per sample) on the CPU."""
+    from polyphemus_amd.graphs import collate_samples, graph_from_structure
+    s_np = s_bin.detach().cpu().numpy().astype(bool)
+    samples = []
+    for i in range(s_np.shape[0]):
+        g = graph_from_structure(s_np[i])
+        g["tokens"] = np.zeros((g["num_nodes"], 16, 2), np.int32)
+        g["s_tensor"] = s_np[i].astype(np.float32)
+        samples.append(g)
+    return collate_samples(samples, n_bars)
+
+
+def trained_like_state(spec, dev="cuda", n_fill=20, seed=4321):
+    """A trained-like state of the `spec` model (its FULLSIZE configuration): the default init under manual_seed(0), running
+    statistics filled by `n_fill` training-mode no_grad forwards of the Python path on synthetic batches of seeds
+    seed, seed + 1, ... (momentum 0.1: 1 - 0.9^20 = 88 % of the batch statistics), then every norm's weight
+    = 1 + 0.5 U(-1, 1) and bias = 0.3 N(0, 1) from torch.Generator().manual_seed(seed).  Returns (cfg, state dict on the
+    CPU).  What the forwards compute does not matter to a comparison: the oracle is given the same state dict."""
+    from polyphemus_amd.model import VAE
+    from polyphemus_amd.synthetic import synthetic_batch
+    cfg = dict(dropout=0, batch_norm=True, gnn_n_layers=spec["L"], d=spec["d"], n_bars=spec["nb"], resolution=8)
+    torch.manual_seed(0)
+    vae = VAE(**cfg, device=dev).to(dev)
+    vae.train()
+    with torch.no_grad():
+        for i in range(n_fill):
+            vae(synthetic_batch(spec["B"], spec["nb"], p=spec["p"], seed=seed + i, dense=spec["dense"]).to(dev))
+    sd = {k: v.detach().cpu().clone() for k, v in vae.state_dict().items()}
+    del vae
+    gen = torch.Generator().manual_seed(seed)
+    for k in bn_keys(sd):
+        w = sd[k + ".weight"]
+        sd[k + ".weight"] = 1 + 0.5 * (2 * torch.rand(w.shape, generator=gen) - 1)
+        sd[k + ".bias"] = 0.3 * torch.randn(w.shape, generator=gen)
+    return cfg, sd
+
+
+def content_correct(c_logits, tokens):
+    """Per (node, slot 1..15) row: (pitch arg-max == target, duration arg-max == target, pitch target not PAD, duration
+    target not PAD) — the element-wise terms of `_accuracies` (training.py:349-468), bool [N, 15] each."""
+    from polyphemus_amd import constants as C
+    c = c_logits.detach().cpu()
+    t = tokens.detach().cpu().long()[:, 1:]
+    p_ok = c[..., :C.N_PITCH_TOKENS].argmax(-1) == t[..., 0]
+    d_ok = c[..., C.N_PITCH_TOKENS:].argmax(-1) == t[..., 1]
+    return p_ok, d_ok, t[..., 0] != C.PITCH_PAD, t[..., 1] != C.DUR_PAD
+
+
+def top2_margin(c_logits):
+    """Per (node, slot) row: the smaller of the pitch and duration top-1 / top-2 logit margins (float64 [N, 15])."""
+    from polyphemus_amd import constants as C
+    c = c_logits.detach().double().cpu()
+    m = []
+    for part in (c[..., :C.N_PITCH_TOKENS], c[..., C.N_PITCH_TOKENS:]):
+        top = part.topk(2, dim=-1).values
+        m.append(top[..., 0] - top[..., 1])
+    return torch.minimum(*m)
+
+
+def oracle_eval_fullsize(cfg, cpu, sd, names, eps, dtypes=(("o64", torch.float64), ("o32", torch.float32))):
+    """The eval-mode entry of the full-size oracle: oracle/vae_cpu.py's forward with training=False (running statistics,
+    no dropout of any kind) on the CPU batch `cpu`, the state dict `sd` and `eps`, per dtype: (outputs, the 7 losses as
+    floats, the state the forward left), and the seconds each took."""
+    import time
+    from oracle import vae_cpu
+    res, times = {}, {}
+    for tag, dt in dtypes:
+        t0 = time.time()
+        P, _ = vae_cpu.split_state({k: (v.to(dt) if v.dtype.is_floating_point else v.clone()) for k, v in sd.items()}, names)
+        b = _as_dtype(cpu, dt)
+        with torch.no_grad():
+            (s_logits, c_logits), mu, lv = vae_cpu.vae_forward(b, P, cfg, False, eps.to(dt))
+            _, parts = vae_cpu.losses(b.s_tensor, s_logits, b.c_tensor, c_logits, mu, lv)
+        res[tag] = (dict(s_logits=s_logits, c_logits=c_logits, mu=mu, log_var=lv), {k: float(v) for k, v in parts.items()},
+                    {k: v.detach() for k, v in P.items()})
+        times[tag] = time.time() - t0
+    return res, times
+
+
+def assert_eval_c_logits_match(c_logits, ze, tol, argmax_mismatch):
+    """Eval c_logits [N, 15, 230] against an evalstate fixture, to `tol` of max|c_logits| per logit: every node's logits of
+    the stored slots (eval/c_logits_slots, where the fixture has them), per (node, slot) sums (|error| <= 230 tol max) and
+    L2 norms (<= sqrt(230) tol max), per-node sums; arg-max tokens differing at no more than `argmax_mismatch` of them."""
+    from polyphemus_amd import constants as C
+    c = c_logits.detach().cpu()
+    m = float(c.abs().max())
+    if "eval/c_logits_slots" in ze.files:
+        want = ze["eval/c_logits_slots"]
+        assert rel_err(c[:, :want.shape[1]], want) < tol, "c_logits slots"
+    cd = c.double()
+    assert float(np.abs(cd.sum(-1).numpy() - ze["eval/c_logits_slotsum"]).max()) < tol * m * C.D_TOKEN_PAIR, "slot sums"
+    assert float(np.abs(cd.norm(dim=-1).numpy() - ze["eval/c_logits_slotnorm"]).max()) < tol * m * C.D_TOKEN_PAIR ** 0.5, \
+        "slot norms"
+    assert float(np.abs(cd.sum(dim=(-1, -2)).numpy() - ze["eval/c_logits_nodesum"]).max()) < tol * m * C.N_SLOTS * C.D_TOKEN_PAIR
+    tok = torch.stack([c[..., :C.N_PITCH_TOKENS].argmax(-1), c[..., C.N_PITCH_TOKENS:].argmax(-1)], -1).numpy()
+    assert (tok != ze["eval/c_argmax"]).mean() <= argmax_mismatch, "arg-max tokens"
