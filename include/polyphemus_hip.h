@@ -62,7 +62,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   9: the guarded optimizer step (pm_h2_clamp_init, pm_overflow_snapshot, pm_overflow_poison, pm_grad_nonfinite_check,
  *   pm_adam_step_guarded, pm_adam_bias_scalars; the PM_OVF_* status layout).  Additive, same version: the training
  *   accuracies (pm_vae_step_set_metrics, pm_unembed_ce_metrics, pm_unembed_ce_rows_metrics, pm_content_accuracy_slots,
- *   pm_train_metric_counts; no existing struct or argument list changed). */
+ *   pm_train_metric_counts; no existing struct or argument list changed); gradient clipping by the global norm
+ *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -872,6 +873,50 @@ int pm_adam_step_guarded(float* params, const float* grads, float* exp_avg, floa
 /* out[2i], out[2i+1] = the scalars the decision forms for step steps[i] >= 1: lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)
  * (the same device function; for parity checks against the host formula). */
 int pm_adam_bias_scalars(const int64_t* steps, int64_t n, float lr, float beta1, float beta2, float* out,
+                         pm_stream_t stream);
+
+/* ------------------------------------------------------------------ gradient clipping by the global norm
+ * No line of training.py stands behind these entries: the reference loop does not clip.  They give the fused step what
+ * `torch.nn.utils.clip_grad_norm_(vae.parameters(), max_norm)` in front of `optimizer.step()` (training.py:160-166) would
+ * give the reference loop, with torch's formula (norm_type 2, error_if_nonfinite=False), decided on the device with no
+ * host read, and they record the norm.  Additive, same ABI version.  Order of one optimizer update on the caller's stream,
+ * on the gradient Adam consumes (the reduced one, or the accumulated one):
+ *   pm_grad_sumsq                  (or pm_grad_nonfinite_check_sumsq in the place of pm_grad_nonfinite_check: one read);
+ *   pm_grad_clip_finish;
+ *   pm_adam_step_clipped           (status = NULL, or the guarded step's status block).
+ * clip: PM_CLIP_WORDS doubles laid out as below; no word needs to be initialised.
+ *   sumsq  = sum of partials[0 .. PM_CLIP_PARTIALS), in slot order
+ *   norm   = fabs((double)grad_scale) * sqrt(sumsq)         the norm of grad_scale * grads, what Adam consumes
+ *   coef   = fmin(1.0, (double)max_norm / (norm + 1e-6))
+ *   gscale = (float)((double)grad_scale * coef)             coef == 1.0: gscale == grad_scale exactly
+ * A non-finite gradient follows the IEEE arithmetic of these lines and is not special-cased: norm = inf gives coef = 0
+ * (inf * 0 = NaN in Adam) or, with max_norm = inf, fmin(1.0, NaN) = 1.0; norm = NaN gives coef = 1.0.  Either way Adam
+ * consumes non-finite values, as after torch's clip; the guarded step skips such an update and still records its norm. */
+enum {
+  PM_CLIP_NORM = 0,        /* norm */
+  PM_CLIP_COEF = 1,        /* coef */
+  PM_CLIP_GSCALE = 2,      /* gscale, the float's value held in a double */
+  PM_CLIP_SUMSQ = 3,       /* sumsq */
+  PM_CLIP_PARTIALS_AT = 4, /* the first of the PM_CLIP_PARTIALS per-workgroup sums of squares */
+  PM_CLIP_PARTIALS = 256,
+  PM_CLIP_WORDS = 260
+};
+/* partials = per-workgroup sums of (double)g * (double)g over grads[0..n), each in a fixed order, each stored by its
+ * workgroup with a plain store; the slots past the launch's grid are zeroed.  Deterministic: the same gradient gives the same
+ * bits.  The launch shape of pm_grad_nonfinite_check. */
+int pm_grad_sumsq(const float* grads, int64_t n, double* clip, pm_stream_t stream);
+/* pm_grad_nonfinite_check and pm_grad_sumsq in one read of the gradient: the same flag and decision as the first, the same
+ * partials, bit for bit, as the second. */
+int pm_grad_nonfinite_check_sumsq(const float* grads, int64_t n, uint32_t* status, int64_t* step, int64_t* skipped, float lr,
+                                  float beta1, float beta2, int32_t window, double* clip, pm_stream_t stream);
+/* The formula above from the partials (one workgroup): clip[PM_CLIP_NORM / _COEF / _GSCALE / _SUMSQ], and (norm, coef) into
+ * row[0..2) unless row is NULL.  max_norm > 0; +inf measures only. */
+int pm_grad_clip_finish(double* clip, float grad_scale, float max_norm, double* row, pm_stream_t stream);
+/* pm_adam_step (status == NULL; lr and step as there) or pm_adam_step_guarded (status: the block pm_grad_nonfinite_check*
+ * decided in; lr and step ignored) with grad_scale read from clip[PM_CLIP_GSCALE].  The same loops: with coef == 1.0 the
+ * step equals pm_adam_step / pm_adam_step_guarded bit for bit; a skipped step stores nothing. */
+int pm_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                         float beta1, float beta2, float eps, int32_t step, const double* clip, const uint32_t* status,
                          pm_stream_t stream);
 
 /* Gradient accumulation over `iters_to_accumulate` micro-batches (training.py:149,158: backward of tot_loss / k, optimizer

@@ -729,3 +729,61 @@ def adam_bias_scalars(steps, lr, beta1, beta2):
     out = torch.empty(steps.numel(), 2, dtype=F32, device=steps.device)
     call("pm_adam_bias_scalars", ptr(steps), steps.numel(), lr, beta1, beta2, ptr(out), stream())
     return out
+
+
+# ---- gradient clipping by the global norm (include/polyphemus_hip.h, "gradient clipping by the global norm")
+CLIP_NORM, CLIP_COEF, CLIP_GSCALE, CLIP_SUMSQ, CLIP_PARTIALS_AT = range(5)   # PM_CLIP_*
+CLIP_PARTIALS = 256                             # PM_CLIP_PARTIALS
+CLIP_WORDS = 260                                # PM_CLIP_WORDS
+
+
+def clip_block(device) -> torch.Tensor:
+    """A clip block (float64 [PM_CLIP_WORDS]: norm, coef, gscale, sumsq, then the per-workgroup partials)."""
+    return torch.zeros(CLIP_WORDS, dtype=F64, device=device)
+
+
+def _chk_clip(clip):
+    _chk(clip, F64, "clip")
+    if clip.numel() < CLIP_WORDS:
+        raise ValueError(f"clip needs {CLIP_WORDS} doubles")
+
+
+def grad_sumsq(grads, clip):
+    """The per-workgroup sums of squares of `grads` (squared and added in double, a fixed order) into the partials of `clip`."""
+    _chk(grads, F32, "grads"); _chk_clip(clip)
+    call("pm_grad_sumsq", ptr(grads), grads.numel(), ptr(clip), stream())
+
+
+def grad_nonfinite_check_sumsq(grads, status, clip, step=None, skipped=None, lr=0.0, beta1=0.0, beta2=0.0, window=False):
+    """`grad_nonfinite_check` and `grad_sumsq` in one read of the gradient."""
+    _chk(grads, F32, "grads"); _chk_status(status); _chk_clip(clip)
+    if (step is None) != (skipped is None):
+        raise ValueError("step and skipped go together")
+    if step is not None:
+        _chk(step, I64, "step"); _chk(skipped, I64, "skipped")
+    call("pm_grad_nonfinite_check_sumsq", ptr(grads), grads.numel(), ptr(status), ptr(step), ptr(skipped), lr, beta1, beta2,
+         int(bool(window)), ptr(clip), stream())
+
+
+def grad_clip_finish(clip, max_norm, grad_scale=1.0, row=None):
+    """From the partials: norm = |grad_scale| * sqrt(sum), coef = min(1, max_norm / (norm + 1e-6)) — the formula of
+    `torch.nn.utils.clip_grad_norm_` — and gscale = float32(grad_scale * coef) into `clip`; (norm, coef) into the float64
+    pair `row` if given.  `max_norm` = inf measures only."""
+    _chk_clip(clip)
+    if row is not None:
+        _chk(row, F64, "row")
+        if row.numel() < 2:
+            raise ValueError("row needs 2 doubles")
+    call("pm_grad_clip_finish", ptr(clip), grad_scale, max_norm, ptr(row), stream())
+
+
+def adam_step_clipped(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, clip, status=None):
+    """`adam_step` (or, with the guarded step's `status`, `adam_step_guarded`: `lr` and `step` are then unused) with the
+    gradient scale `grad_clip_finish` left in `clip`.  Unclipped (coef == 1) it equals them bit for bit."""
+    for t, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, F32, n)
+    _chk_clip(clip)
+    if status is not None:
+        _chk_status(status)
+    call("pm_adam_step_clipped", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), lr, beta1, beta2,
+         eps, step, ptr(clip), ptr(status), stream())

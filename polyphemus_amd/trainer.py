@@ -69,9 +69,18 @@ class HipTrainer:
     def __init__(self, vae: VAE, lr=5e-6, betas=(0.9, 0.98), eps=1e-9, lr_scheduler: Optional[dict] = None,
                  structure_loss_on_logits: bool = False, beta: float = 0.0, process_group=None, native: bool = True,
                  iters_to_accumulate: int = 1, global_token_mean: bool = False, sync_bn: bool = False,
-                 overflow: str = "ignore", train_metrics: bool = False, metrics_capacity: int = 1024):
+                 overflow: str = "ignore", train_metrics: bool = False, metrics_capacity: int = 1024,
+                 max_grad_norm: Optional[float] = None, grad_norm_capacity: int = 1024):
         if overflow not in ("ignore", "skip"):
             raise ValueError(f"overflow must be 'ignore' or 'skip', not {overflow!r}")
+        if max_grad_norm is not None:
+            # (it crosses the C ABI as a float: a positive value that rounds to 0.0f is rejected here, not inside a step)
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or \
+                    not ctypes.c_float(max_grad_norm).value > 0:
+                raise ValueError(f"max_grad_norm must be None, a positive number (as a float32) or float('inf'), "
+                                 f"not {max_grad_norm!r}")
+        if isinstance(grad_norm_capacity, bool) or not isinstance(grad_norm_capacity, int) or grad_norm_capacity < 1:
+            raise ValueError(f"grad_norm_capacity must be a positive int, not {grad_norm_capacity!r}")
         if not isinstance(train_metrics, bool):
             raise ValueError(f"train_metrics must be True or False, not {train_metrics!r}")
         if train_metrics and (not isinstance(metrics_capacity, int) or metrics_capacity < 1):
@@ -128,6 +137,16 @@ class HipTrainer:
             self._ovf_copied = False
             self._ovf_warned = 0
         self.step_count = 0
+        # Clipping by the global norm (what `torch.nn.utils.clip_grad_norm_` in front of `optimizer.step()` gives the
+        # reference loop; the reference itself does not clip).  None: nothing of it runs.  A number: the gradient Adam
+        # consumes — the mean over ranks, or the accumulated one — is scaled by min(1, max / (norm + 1e-6)) on the device;
+        # inf: measured only.  One (norm, coef) row per optimizer update goes into a device history of `grad_norm_capacity`
+        # rows; `read_grad_norms` takes them with one sync.
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        if self.max_grad_norm is not None:
+            self._clip = ops.clip_block(flat.device)
+            self._nhist = torch.zeros(grad_norm_capacity, 2, dtype=torch.float64, device=flat.device)
+            self._nrows = 0                       # rows written since the last read (host count)
         self.loss_buf = torch.zeros(4, dtype=torch.float64, device=flat.device)
         # Training accuracies (the reference's `_accuracies` after every batch, training.py:174-179): one int64 counts row per
         # batch (ops.accuracies_from_counts has the layout), written by the step on the device into a history of
@@ -283,6 +302,23 @@ class HipTrainer:
         self._mrows = 0
         return [ops.accuracies_from_counts(r) for r in host]
 
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """Device float64 view of the norm of the gradient the last optimizer update consumed, before clipping (no sync)."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("last_grad_norm needs HipTrainer(..., max_grad_norm=...)")
+        return self._clip[ops.CLIP_NORM]
+
+    def read_grad_norms(self) -> list:
+        """`[(norm, coef), ...]`, one pair per optimizer update since the last read, in order: the global L2 norm of the
+        gradient Adam consumed (a skipped update's too, possibly inf or NaN) and the factor it was scaled by,
+        min(1, max_grad_norm / (norm + 1e-6)).  Every rank holds the same bits.  One host sync; empties the history."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("read_grad_norms needs HipTrainer(..., max_grad_norm=...)")
+        host = self._nhist[:self._nrows].tolist()          # the one sync
+        self._nrows = 0
+        return [(r[0], r[1]) for r in host]
+
     def step_info(self) -> dict:
         """Which variant of the native step the last `train_step` ran (`pm_vae_step_info`): compact GCL (K = 4d),
         bf16-planes GEMM operands, active token slots S, fragment-major weight planes (B-direct GEMM), batch sizes, the
@@ -363,6 +399,10 @@ class HipTrainer:
         if self.train_metrics and self._mrows >= self._mhist.shape[0]:
             raise RuntimeError(f"the training-accuracy history is full ({self._mhist.shape[0]} unread batches): call "
                                "read_train_accuracies() first, or build the trainer with a larger metrics_capacity")
+        clip = self.max_grad_norm is not None
+        if clip and self._nrows >= self._nhist.shape[0]:
+            raise RuntimeError(f"the gradient-norm history is full ({self._nhist.shape[0]} unread updates): call "
+                               "read_grad_norms() first, or build the trainer with a larger grad_norm_capacity")
         self.grads.zero_()
         k = self.iters_to_accumulate
         self.buckets.hold = k > 1                      # micro-batches of an accumulation are not all-reduced one by one
@@ -382,20 +422,39 @@ class HipTrainer:
         else:
             mean_scale = self.buckets.wait()
         # ---- optimizer (training.py:160-172)
+        if clip:                                       # this update's (norm, coef) row (host pointer arithmetic)
+            kp, rp = self._clip.data_ptr(), self._nhist[self._nrows].data_ptr()
         if self._guard:                                # scaler.step(optimizer): no update on found_inf (training.py:160-162)
             st, sp = stream(), self._ovf_status.data_ptr()
             cp = self._ovf_counts.data_ptr()
-            call("pm_grad_nonfinite_check", grads.data_ptr(), grads.numel(), sp, cp, cp + 8, self.lr, self.betas[0],
-                 self.betas[1], 1, st)
-            call("pm_adam_step_guarded", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
-                 self.exp_avg_sq.data_ptr(), grads.numel(), self.betas[0], self.betas[1], self.eps, mean_scale, sp, st)
+            if clip:                                   # the check's read of the gradient also takes the sum of squares
+                call("pm_grad_nonfinite_check_sumsq", grads.data_ptr(), grads.numel(), sp, cp, cp + 8, self.lr,
+                     self.betas[0], self.betas[1], 1, kp, st)
+                call("pm_grad_clip_finish", kp, mean_scale, self.max_grad_norm, rp, st)
+                call("pm_adam_step_clipped", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
+                     self.exp_avg_sq.data_ptr(), grads.numel(), 0.0, self.betas[0], self.betas[1], self.eps, 0, kp, sp, st)
+            else:
+                call("pm_grad_nonfinite_check", grads.data_ptr(), grads.numel(), sp, cp, cp + 8, self.lr, self.betas[0],
+                     self.betas[1], 1, st)
+                call("pm_adam_step_guarded", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
+                     self.exp_avg_sq.data_ptr(), grads.numel(), self.betas[0], self.betas[1], self.eps, mean_scale, sp, st)
             self._ovf_host.copy_(self._ovf_counts[1:2], non_blocking=True)
             self._ovf_event.record()
             self._ovf_copied = True
+        elif clip:
+            self.step_count += 1
+            st = stream()
+            call("pm_grad_sumsq", grads.data_ptr(), grads.numel(), kp, st)
+            call("pm_grad_clip_finish", kp, mean_scale, self.max_grad_norm, rp, st)
+            call("pm_adam_step_clipped", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
+                 self.exp_avg_sq.data_ptr(), grads.numel(), self.lr, self.betas[0], self.betas[1], self.eps,
+                 self.step_count, kp, None, st)
         else:
             self.step_count += 1
             ops.adam_step(vae.flat_params, grads, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0],
                           self.betas[1], self.eps, self.step_count, grad_scale=mean_scale)
+        if clip:
+            self._nrows += 1                               # (behind the launches: the count is of rows that were written)
         if self.sched is not None:
             self.lr = self.sched.step()
         return out
