@@ -12,39 +12,64 @@
 #include "common.h"
 #include <math.h>
 
-// The Adam update over the flat buffers, ONE text for the plain, the guarded and the clipped kernels: each names p, g, m, v, the
-// count (n4 / n), b1, b2, eps, step_size, inv_bc2_sqrt and gscale, so the three are expression for expression the same loop
-#define PM_ADAM4_LOOP \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) { \
-    float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i]; \
-    float* P = reinterpret_cast<float*>(&pv); float* Gd = reinterpret_cast<float*>(&gv); \
-    float* M = reinterpret_cast<float*>(&mv); float* V = reinterpret_cast<float*>(&vv); \
-    _Pragma("unroll") \
-    for (int j = 0; j < 4; ++j) { \
-      const float gr = Gd[j] * gscale; \
-      M[j] = b1 * M[j] + (1.f - b1) * gr; \
-      V[j] = b2 * V[j] + (1.f - b2) * gr * gr; \
-      P[j] -= step_size * (M[j] / (sqrtf(V[j]) * inv_bc2_sqrt + eps)); \
-    } \
-    p[i] = pv; m[i] = mv; v[i] = vv; \
-  }
-#define PM_ADAM1_LOOP \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) { \
-    const float gr = g[i] * gscale; \
-    const float mm = b1 * m[i] + (1.f - b1) * gr; \
-    const float vv = b2 * v[i] + (1.f - b2) * gr * gr; \
-    m[i] = mm; v[i] = vv; \
-    p[i] -= step_size * (mm / (sqrtf(vv) * inv_bc2_sqrt + eps)); \
-  }
-__global__ void __launch_bounds__(256) k_adam4(float4* __restrict__ p, const float4* __restrict__ g,
-                                               float4* __restrict__ m, float4* __restrict__ v, int64_t n4, float b1,
-                                               float b2, float step_size, float inv_bc2_sqrt, float eps, float gscale) {
-  PM_ADAM4_LOOP
+// Adam's bias-correction scalars at step t, in double: the one formula of the host entry points and of the check's decision
+__host__ __device__ static inline void adam_bias_scalars(int64_t t, float lr, float beta1, float beta2, float& step_size,
+                                                         float& inv_bc2_sqrt) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)t);
+  const double bc2 = 1.0 - pow((double)beta2, (double)t);
+  step_size = (float)((double)lr / bc1);
+  inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
 }
-__global__ void __launch_bounds__(256) k_adam1(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                               float* __restrict__ v, int64_t n, float b1, float b2, float step_size,
-                                               float inv_bc2_sqrt, float eps, float gscale) {
-  PM_ADAM1_LOOP
+// where the update's scalars come from: the host's values, or — read on the device — gscale from the clip block pm_grad_clip_finish
+// wrote (CLIP) and the decision with its step_size / inv_bc2_sqrt from the status block of the check (GUARD)
+struct AdamSources { float step_size, inv_bc2_sqrt, gscale; const double* clip; const unsigned* status; };
+// The Adam update over the flat buffers, VT = float4 or float; n counts VTs.  GUARD || CLIP: thread 0 reads the device sources once
+// per workgroup; a skipped step returns before any store.  The loop is one text, so with coef == 1 (gscale == grad_scale) and an
+// applied decision the plain, the guarded and the clipped steps are bit-identical.  The lanes index the buffers themselves (the
+// compiler still moves whole float4s) and the update is these three statements, no locals: which product of m's and of v's update
+// the compiler fuses into the FMA depends on such details of the text, and a last bit of m or v with it
+template <typename VT, bool GUARD, bool CLIP>
+__global__ void __launch_bounds__(256) k_adam(VT* __restrict__ p, const VT* __restrict__ g, VT* __restrict__ m,
+                                              VT* __restrict__ v, int64_t n, float b1, float b2, float eps, AdamSources a) {
+  float step_size = a.step_size, inv_bc2_sqrt = a.inv_bc2_sqrt, gscale = a.gscale;
+  if constexpr (GUARD || CLIP) {
+    __shared__ unsigned sh[4];
+    if (threadIdx.x == 0) {
+      if (CLIP) sh[3] = __float_as_uint((float)a.clip[PM_CLIP_GSCALE]);
+      if (GUARD) { sh[0] = a.status[PM_OVF_LAST]; sh[1] = a.status[PM_OVF_STEP_SIZE]; sh[2] = a.status[PM_OVF_INV_BC2]; }
+    }
+    __syncthreads();
+    if (GUARD && sh[0]) return;
+    if (GUARD) { step_size = __uint_as_float(sh[1]); inv_bc2_sqrt = __uint_as_float(sh[2]); }
+    if (CLIP) gscale = __uint_as_float(sh[3]);
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float* P = reinterpret_cast<float*>(p + i); const float* Gd = reinterpret_cast<const float*>(g + i);
+    float* M = reinterpret_cast<float*>(m + i); float* V = reinterpret_cast<float*>(v + i);
+#pragma unroll
+    for (int j = 0; j < (int)(sizeof(VT) / 4); ++j) {
+      const float gr = Gd[j] * gscale;
+      M[j] = b1 * M[j] + (1.f - b1) * gr;
+      V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
+      P[j] -= step_size * (M[j] / (sqrtf(V[j]) * inv_bc2_sqrt + eps));
+    }
+  }
+}
+// the float4 kernel for 16-byte-aligned buffers with n % 4 == 0, the scalar one otherwise; at most 4096 workgroups of 256
+template <bool GUARD, bool CLIP>
+static int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps,
+                       const AdamSources& a, pm_stream_t stream) {
+  const bool vec = !(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) && (n % 4) == 0;
+  const int64_t nv = vec ? n / 4 : n;
+  int64_t nb = pm_cdiv(nv, 256); if (nb > 4096) nb = 4096;
+  if (vec)
+    hipLaunchKernelGGL((k_adam<float4, GUARD, CLIP>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m),
+                       reinterpret_cast<float4*>(v), nv, b1, b2, eps, a);
+  else
+    hipLaunchKernelGGL((k_adam<float, GUARD, CLIP>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, nv, b1,
+                       b2, eps, a);
+  return pm_check_launch();
 }
 // acc = (first ? 0 : acc) + scale * g   (gradient accumulation over micro-batches, training.py:149,158)
 __global__ void __launch_bounds__(256) k_grad_accumulate(const float* __restrict__ g, float* __restrict__ acc, int64_t n,
@@ -65,35 +90,12 @@ extern "C" int pm_grad_accumulate(const float* grads, float* accum, int64_t n, f
 extern "C" int pm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                             float beta1, float beta2, float eps, int32_t step, float grad_scale, pm_stream_t stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || step <= 0) return PM_E_INVALID;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  hipStream_t st = (hipStream_t)stream;
-  const bool al = !(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15);
-  if (al && (n % 4) == 0) {
-    int64_t nb = pm_cdiv(n / 4, 256); if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_adam4, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<float4*>(params),
-                       reinterpret_cast<const float4*>(grads), reinterpret_cast<float4*>(exp_avg),
-                       reinterpret_cast<float4*>(exp_avg_sq), n / 4, beta1, beta2, step_size, inv_bc2_sqrt, eps,
-                       grad_scale);
-  } else {
-    int64_t nb = pm_cdiv(n, 256); if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_adam1, dim3((unsigned)nb), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, beta1,
-                       beta2, step_size, inv_bc2_sqrt, eps, grad_scale);
-  }
-  return pm_check_launch();
+  AdamSources a{0.f, 0.f, grad_scale, nullptr, nullptr};
+  adam_bias_scalars(step, lr, beta1, beta2, a.step_size, a.inv_bc2_sqrt);
+  return launch_adam<false, false>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream);
 }
 
 // ---- guarded step (include/polyphemus_hip.h, "guarded optimizer step"; GradScaler, training.py:160-162)
-// Adam's bias-correction scalars at step t, in double as pm_adam_step forms them on the host
-__device__ static inline void adam_bias_scalars(int64_t t, float lr, float beta1, float beta2, float& step_size,
-                                                float& inv_bc2_sqrt) {
-  const double bc1 = 1.0 - pow((double)beta1, (double)t);
-  const double bc2 = 1.0 - pow((double)beta2, (double)t);
-  step_size = (float)((double)lr / bc1);
-  inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-}
 // non-finite = exponent bits all ones (inf or NaN); a bit test no fast-math flag can fold away, unlike isfinite
 __device__ static inline bool nonfinite_bits(unsigned u) { return (u & 0x7f800000u) == 0x7f800000u; }
 // the workgroup's verdict, one atomic per workgroup.  With a decision to make it goes into the ticket word itself — the count of
@@ -133,6 +135,7 @@ __device__ static inline void check_epilogue(bool bad, unsigned* __restrict__ st
 // decision word takes 256 same-address atomics, not 2048 (serialised, those cost 26 us)
 constexpr int kCheckThreads = 1024, kCheckBlocks = 256;
 static_assert(kCheckBlocks <= PM_CLIP_PARTIALS, "one partial slot per workgroup of the check's launch shape");
+static_assert(kCheckBlocks < (1 << 16), "the two counts of the decision word must not overflow into each other");
 
 // ---- sum of squares of the gradient (include/polyphemus_hip.h, "gradient clipping by the global norm")
 // (double)g * (double)g is exact (24 x 24 significand bits) and cannot overflow or vanish (|g| <= 3.4e38 -> 1.2e77; the
@@ -159,10 +162,7 @@ __device__ static inline void sumsq_epilogue(double acc, double* __restrict__ cl
   if (blockIdx.x == 0)
     for (unsigned k = gridDim.x + threadIdx.x; k < (unsigned)PM_CLIP_PARTIALS; k += kCheckThreads) partials[k] = 0.0;
 }
-// (the kernels form the first index and the stride themselves: there the compiler reads blockDim.x from the dispatch packet
-// without the extra load a device function costs)
-#define PM_PASS_INDEX (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x
-// the read of the gradient, shared by the check (CHECK), the sum of squares (SUMSQ) and both in one pass
+// the strided loops of the read, four loads in flight per thread in the uint4 one
 template <bool CHECK, bool SUMSQ>
 __device__ static inline void grad_pass4(const uint4* __restrict__ g, int64_t n4, int64_t i, int64_t stride, bool& bad,
                                          double& acc) {
@@ -190,48 +190,42 @@ __device__ static inline void grad_pass1(const unsigned* __restrict__ g, int64_t
     if (SUMSQ) { const double x = (double)__uint_as_float(u); acc += x * x; }
   }
 }
-__global__ void __launch_bounds__(kCheckThreads) k_nonfinite4(const uint4* __restrict__ g, int64_t n4,
-                                                              unsigned* __restrict__ status, NonfiniteDecision d) {
+// one read of the gradient for the check (CHECK), the sum of squares (SUMSQ) or both: the sum first, the decision last.  VT = uint4
+// or unsigned; n counts VTs.  (The kernel forms the first index and the stride itself: there the compiler reads blockDim.x from the
+// dispatch packet without the extra load a device function costs)
+template <typename VT, bool CHECK, bool SUMSQ>
+__global__ void __launch_bounds__(kCheckThreads) k_grad_pass(const VT* __restrict__ g, int64_t n, unsigned* __restrict__ status,
+                                                             NonfiniteDecision d, double* __restrict__ clip) {
+  static_assert(CHECK || SUMSQ, "a pass that reads the gradient for nothing");
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
   bool bad = false; double acc = 0.0;
-  grad_pass4<true, false>(g, n4, PM_PASS_INDEX, bad, acc);
-  check_epilogue(bad, status, d);
+  if constexpr (sizeof(VT) == 16) grad_pass4<CHECK, SUMSQ>(g, n, i0, stride, bad, acc);
+  else grad_pass1<CHECK, SUMSQ>(g, n, i0, stride, bad, acc);
+  if constexpr (SUMSQ) sumsq_epilogue(acc, clip);
+  if constexpr (CHECK) check_epilogue(bad, status, d);
 }
-__global__ void __launch_bounds__(kCheckThreads) k_nonfinite1(const unsigned* __restrict__ g, int64_t n,
-                                                              unsigned* __restrict__ status, NonfiniteDecision d) {
-  bool bad = false; double acc = 0.0;
-  grad_pass1<true, false>(g, n, PM_PASS_INDEX, bad, acc);
-  check_epilogue(bad, status, d);
+// the uint4 kernel for a 16-byte-aligned gradient with n % 4 == 0, the scalar one otherwise, in the launch shape above
+template <bool CHECK, bool SUMSQ>
+static int launch_grad_pass(const float* grads, int64_t n, uint32_t* status, const NonfiniteDecision& d, double* clip,
+                            pm_stream_t stream) {
+  const bool vec = !((uintptr_t)grads & 15) && (n % 4) == 0;
+  const int64_t nv = vec ? n / 4 : n;
+  int64_t nb = pm_cdiv(nv, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
+  if (vec)
+    hipLaunchKernelGGL((k_grad_pass<uint4, CHECK, SUMSQ>), dim3((unsigned)nb), dim3(kCheckThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint4*>(grads), nv, status, d, clip);
+  else
+    hipLaunchKernelGGL((k_grad_pass<unsigned, CHECK, SUMSQ>), dim3((unsigned)nb), dim3(kCheckThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned*>(grads), nv, status, d, clip);
+  return pm_check_launch();
 }
-// the check and the sum of squares in one read of the gradient
-__global__ void __launch_bounds__(kCheckThreads) k_nonfinite4_sumsq(const uint4* __restrict__ g, int64_t n4,
-                                                                    unsigned* __restrict__ status, NonfiniteDecision d,
-                                                                    double* __restrict__ clip) {
-  bool bad = false; double acc = 0.0;
-  grad_pass4<true, true>(g, n4, PM_PASS_INDEX, bad, acc);
-  sumsq_epilogue(acc, clip);
-  check_epilogue(bad, status, d);
+// the decision the check is to make (none without `step`); false if `window` asks for a clamp word that is not there
+static bool make_decision(NonfiniteDecision& d, int64_t* step, int64_t* skipped, float lr, float beta1, float beta2,
+                          int32_t window) {
+  d = NonfiniteDecision{step, skipped, nullptr, lr, beta1, beta2};
+  if (step && window) d.clamp = pm_h2_clamp_word_ready();
+  return !(step && window) || d.clamp;
 }
-__global__ void __launch_bounds__(kCheckThreads) k_nonfinite1_sumsq(const unsigned* __restrict__ g, int64_t n,
-                                                                    unsigned* __restrict__ status, NonfiniteDecision d,
-                                                                    double* __restrict__ clip) {
-  bool bad = false; double acc = 0.0;
-  grad_pass1<true, true>(g, n, PM_PASS_INDEX, bad, acc);
-  sumsq_epilogue(acc, clip);
-  check_epilogue(bad, status, d);
-}
-__global__ void __launch_bounds__(kCheckThreads) k_grad_sumsq4(const uint4* __restrict__ g, int64_t n4,
-                                                               double* __restrict__ clip) {
-  bool bad = false; double acc = 0.0;
-  grad_pass4<false, true>(g, n4, PM_PASS_INDEX, bad, acc);
-  sumsq_epilogue(acc, clip);
-}
-__global__ void __launch_bounds__(kCheckThreads) k_grad_sumsq1(const unsigned* __restrict__ g, int64_t n,
-                                                               double* __restrict__ clip) {
-  bool bad = false; double acc = 0.0;
-  grad_pass1<false, true>(g, n, PM_PASS_INDEX, bad, acc);
-  sumsq_epilogue(acc, clip);
-}
-#undef PM_PASS_INDEX
 // the finish (one workgroup): the partials added in slot order by one thread, then the formula of the header
 __global__ void __launch_bounds__(PM_CLIP_PARTIALS) k_grad_clip_finish(double* __restrict__ clip, float grad_scale,
                                                                        float max_norm, double* __restrict__ row) {
@@ -247,64 +241,6 @@ __global__ void __launch_bounds__(PM_CLIP_PARTIALS) k_grad_clip_finish(double* _
   clip[PM_CLIP_NORM] = norm; clip[PM_CLIP_COEF] = coef; clip[PM_CLIP_GSCALE] = (double)gscale; clip[PM_CLIP_SUMSQ] = sumsq;
   if (row) { row[0] = norm; row[1] = coef; }
 }
-// the workgroup reads the decision and the scalars once; a skipped step stores nothing
-#define PM_ADAM_GUARD(status)                                                                         \
-  __shared__ unsigned sh[3];                                                                          \
-  if (threadIdx.x == 0) {                                                                             \
-    sh[0] = status[PM_OVF_LAST]; sh[1] = status[PM_OVF_STEP_SIZE]; sh[2] = status[PM_OVF_INV_BC2];    \
-  }                                                                                                   \
-  __syncthreads();                                                                                    \
-  if (sh[0]) return;                                                                                  \
-  const float step_size = __uint_as_float(sh[1]), inv_bc2_sqrt = __uint_as_float(sh[2]);
-__global__ void __launch_bounds__(256) k_adam4_guarded(float4* __restrict__ p, const float4* __restrict__ g,
-                                                       float4* __restrict__ m, float4* __restrict__ v, int64_t n4, float b1,
-                                                       float b2, const unsigned* __restrict__ status, float eps,
-                                                       float gscale) {
-  PM_ADAM_GUARD(status)
-  PM_ADAM4_LOOP
-}
-__global__ void __launch_bounds__(256) k_adam1_guarded(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, int64_t n, float b1,
-                                                       float b2, const unsigned* __restrict__ status, float eps,
-                                                       float gscale) {
-  PM_ADAM_GUARD(status)
-  PM_ADAM1_LOOP
-}
-#undef PM_ADAM_GUARD
-// ---- Adam with the gradient scale read from the clip block (pm_grad_clip_finish wrote it).  GUARD: behind the decision of the
-// check, as k_adam*_guarded; otherwise the scalars come from the host, as in k_adam*.  Thread 0 reads the block once
-// thread 0 reads gscale (with coef == 1 it is grad_scale: the step is then bit-identical to pm_adam_step / _guarded) and, GUARD, the
-// decision and its scalars once; a skipped step stores nothing
-#define PM_ADAM_CLIP_PROLOGUE(clip, status) \
-  __shared__ unsigned sh[4]; \
-  if (threadIdx.x == 0) { \
-    sh[3] = __float_as_uint((float)clip[PM_CLIP_GSCALE]); \
-    if (GUARD) { sh[0] = status[PM_OVF_LAST]; sh[1] = status[PM_OVF_STEP_SIZE]; sh[2] = status[PM_OVF_INV_BC2]; } \
-  } \
-  __syncthreads(); \
-  if (GUARD && sh[0]) return; \
-  const float step_size = GUARD ? __uint_as_float(sh[1]) : step_size_h; \
-  const float inv_bc2_sqrt = GUARD ? __uint_as_float(sh[2]) : inv_bc2_sqrt_h; \
-  const float gscale = __uint_as_float(sh[3]);
-template <bool GUARD>
-__global__ void __launch_bounds__(256) k_adam4_clipped(float4* __restrict__ p, const float4* __restrict__ g,
-                                                       float4* __restrict__ m, float4* __restrict__ v, int64_t n4, float b1,
-                                                       float b2, float step_size_h, float inv_bc2_sqrt_h, float eps,
-                                                       const double* __restrict__ clip, const unsigned* __restrict__ status) {
-  PM_ADAM_CLIP_PROLOGUE(clip, status)
-  PM_ADAM4_LOOP
-}
-template <bool GUARD>
-__global__ void __launch_bounds__(256) k_adam1_clipped(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, int64_t n, float b1,
-                                                       float b2, float step_size_h, float inv_bc2_sqrt_h, float eps,
-                                                       const double* __restrict__ clip, const unsigned* __restrict__ status) {
-  PM_ADAM_CLIP_PROLOGUE(clip, status)
-  PM_ADAM1_LOOP
-}
-#undef PM_ADAM_CLIP_PROLOGUE
-#undef PM_ADAM4_LOOP
-#undef PM_ADAM1_LOOP
 __global__ void k_adam_bias_scalars(const int64_t* __restrict__ steps, int64_t n, float lr, float beta1, float beta2,
                                     float* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -312,42 +248,17 @@ __global__ void k_adam_bias_scalars(const int64_t* __restrict__ steps, int64_t n
 }
 extern "C" int pm_grad_nonfinite_check(const float* grads, int64_t n, uint32_t* status, int64_t* step, int64_t* skipped,
                                        float lr, float beta1, float beta2, int32_t window, pm_stream_t stream) {
-  if (!grads || !status || n <= 0 || (step && !skipped)) return PM_E_INVALID;
-  NonfiniteDecision d{step, skipped, nullptr, lr, beta1, beta2};
-  if (step && window) {
-    d.clamp = pm_h2_clamp_word_ready();
-    if (!d.clamp) return PM_E_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // (grid <= 256 < 2^16: the two counts of the decision word cannot overflow into each other)
-  if (!((uintptr_t)grads & 15) && (n % 4) == 0) {
-    int64_t nb = pm_cdiv(n / 4, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
-    hipLaunchKernelGGL(k_nonfinite4, dim3((unsigned)nb), dim3(kCheckThreads), 0, st, reinterpret_cast<const uint4*>(grads),
-                       n / 4, status, d);
-  } else {
-    int64_t nb = pm_cdiv(n, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
-    hipLaunchKernelGGL(k_nonfinite1, dim3((unsigned)nb), dim3(kCheckThreads), 0, st, reinterpret_cast<const unsigned*>(grads),
-                       n, status, d);
-  }
-  return pm_check_launch();
+  NonfiniteDecision d;
+  if (!grads || !status || n <= 0 || (step && !skipped) || !make_decision(d, step, skipped, lr, beta1, beta2, window))
+    return PM_E_INVALID;
+  return launch_grad_pass<true, false>(grads, n, status, d, nullptr, stream);
 }
 extern "C" int pm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                                     float beta1, float beta2, float eps, float grad_scale, const uint32_t* status,
                                     pm_stream_t stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !status || n <= 0) return PM_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  const bool al = !(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15);
-  if (al && (n % 4) == 0) {
-    int64_t nb = pm_cdiv(n / 4, 256); if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_adam4_guarded, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<float4*>(params),
-                       reinterpret_cast<const float4*>(grads), reinterpret_cast<float4*>(exp_avg),
-                       reinterpret_cast<float4*>(exp_avg_sq), n / 4, beta1, beta2, status, eps, grad_scale);
-  } else {
-    int64_t nb = pm_cdiv(n, 256); if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_adam1_guarded, dim3((unsigned)nb), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n,
-                       beta1, beta2, status, eps, grad_scale);
-  }
-  return pm_check_launch();
+  const AdamSources a{0.f, 0.f, grad_scale, nullptr, status};
+  return launch_adam<true, false>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream);
 }
 extern "C" int pm_adam_bias_scalars(const int64_t* steps, int64_t n, float lr, float beta1, float beta2, float* out,
                                     pm_stream_t stream) {
@@ -359,32 +270,18 @@ extern "C" int pm_adam_bias_scalars(const int64_t* steps, int64_t n, float lr, f
 }
 
 // ---- gradient clipping by the global norm (include/polyphemus_hip.h)
-template <typename K4, typename K1, typename... A>
-static inline void launch_grad_pass(K4 k4, K1 k1, const float* grads, int64_t n, hipStream_t st, A... a) {
-  if (!((uintptr_t)grads & 15) && (n % 4) == 0) {
-    int64_t nb = pm_cdiv(n / 4, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
-    hipLaunchKernelGGL(k4, dim3((unsigned)nb), dim3(kCheckThreads), 0, st, reinterpret_cast<const uint4*>(grads), n / 4, a...);
-  } else {
-    int64_t nb = pm_cdiv(n, kCheckThreads); if (nb > kCheckBlocks) nb = kCheckBlocks;
-    hipLaunchKernelGGL(k1, dim3((unsigned)nb), dim3(kCheckThreads), 0, st, reinterpret_cast<const unsigned*>(grads), n, a...);
-  }
-}
 extern "C" int pm_grad_sumsq(const float* grads, int64_t n, double* clip, pm_stream_t stream) {
   if (!grads || !clip || n <= 0 || ((uintptr_t)clip & 7)) return PM_E_INVALID;
-  launch_grad_pass(k_grad_sumsq4, k_grad_sumsq1, grads, n, (hipStream_t)stream, clip);
-  return pm_check_launch();
+  return launch_grad_pass<false, true>(grads, n, nullptr, NonfiniteDecision{}, clip, stream);
 }
 extern "C" int pm_grad_nonfinite_check_sumsq(const float* grads, int64_t n, uint32_t* status, int64_t* step, int64_t* skipped,
                                              float lr, float beta1, float beta2, int32_t window, double* clip,
                                              pm_stream_t stream) {
-  if (!grads || !status || !clip || n <= 0 || (step && !skipped) || ((uintptr_t)clip & 7)) return PM_E_INVALID;
-  NonfiniteDecision d{step, skipped, nullptr, lr, beta1, beta2};
-  if (step && window) {
-    d.clamp = pm_h2_clamp_word_ready();
-    if (!d.clamp) return PM_E_INVALID;
-  }
-  launch_grad_pass(k_nonfinite4_sumsq, k_nonfinite1_sumsq, grads, n, (hipStream_t)stream, status, d, clip);
-  return pm_check_launch();
+  NonfiniteDecision d;
+  if (!grads || !status || !clip || n <= 0 || (step && !skipped) || ((uintptr_t)clip & 7) ||
+      !make_decision(d, step, skipped, lr, beta1, beta2, window))
+    return PM_E_INVALID;
+  return launch_grad_pass<true, true>(grads, n, status, d, clip, stream);
 }
 extern "C" int pm_grad_clip_finish(double* clip, float grad_scale, float max_norm, double* row, pm_stream_t stream) {
   if (!clip || ((uintptr_t)clip & 7) || ((uintptr_t)row & 7) || !(max_norm > 0.f)) return PM_E_INVALID;
@@ -397,28 +294,10 @@ extern "C" int pm_adam_step_clipped(float* params, const float* grads, float* ex
                                     const uint32_t* status, pm_stream_t stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !clip || ((uintptr_t)clip & 7) || n <= 0 || (!status && step <= 0))
     return PM_E_INVALID;
-  float step_size = 0.f, inv_bc2_sqrt = 0.f;
-  if (!status) {                                  // (pm_adam_step's host scalars; guarded: the decision's, from the device)
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    step_size = (float)((double)lr / bc1);
-    inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const bool al = !(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15);
-  if (al && (n % 4) == 0) {
-    int64_t nb = pm_cdiv(n / 4, 256); if (nb > 4096) nb = 4096;
-    auto k = status ? k_adam4_clipped<true> : k_adam4_clipped<false>;
-    hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<float4*>(params),
-                       reinterpret_cast<const float4*>(grads), reinterpret_cast<float4*>(exp_avg),
-                       reinterpret_cast<float4*>(exp_avg_sq), n / 4, beta1, beta2, step_size, inv_bc2_sqrt, eps, clip, status);
-  } else {
-    int64_t nb = pm_cdiv(n, 256); if (nb > 4096) nb = 4096;
-    auto k = status ? k_adam1_clipped<true> : k_adam1_clipped<false>;
-    hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, step_size,
-                       inv_bc2_sqrt, eps, clip, status);
-  }
-  return pm_check_launch();
+  AdamSources a{0.f, 0.f, 0.f, clip, status};
+  if (status) return launch_adam<true, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream);
+  adam_bias_scalars(step, lr, beta1, beta2, a.step_size, a.inv_bc2_sqrt);       // (unguarded: the host's scalars, as pm_adam_step)
+  return launch_adam<false, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream);
 }
 
 extern "C" int pm_abi_version(void) { return PM_ABI_VERSION; }

@@ -663,9 +663,13 @@ def structure_metrics(s_logits, s_target):
     return out
 
 
-def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0):
+def _chk_adam(params, grads, exp_avg, exp_avg_sq):
     for t, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _chk(t, F32, n)
+
+
+def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    _chk_adam(params, grads, exp_avg, exp_avg_sq)
     call("pm_adam_step", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), lr, beta1, beta2,
          eps, step, grad_scale, stream())
 
@@ -687,6 +691,13 @@ def _chk_status(status):
         raise ValueError(f"status needs {OVF_WORDS} words")
 
 
+def _chk_decision(step, skipped):
+    if (step is None) != (skipped is None):
+        raise ValueError("step and skipped go together")
+    if step is not None:
+        _chk(step, I64, "step"); _chk(skipped, I64, "skipped")
+
+
 def overflow_snapshot(status):
     """status[OVF_SNAP] = the pair-format saturation counter, on the current stream (before the step's first split)."""
     _chk_status(status)
@@ -703,11 +714,7 @@ def grad_nonfinite_check(grads, status, step=None, skipped=None, lr=0.0, beta1=0
     """The non-finite bit in status[OVF_PENDING] if grads holds an inf or a NaN (GradScaler's found_inf).  With the int64
     device words `step` / `skipped` the launch also DECIDES the optimizer step (t + 1 and its Adam scalars, or a skip);
     `window`: a move of the saturation counter since `overflow_snapshot` is a cause too."""
-    _chk(grads, F32, "grads"); _chk_status(status)
-    if (step is None) != (skipped is None):
-        raise ValueError("step and skipped go together")
-    if step is not None:
-        _chk(step, I64, "step"); _chk(skipped, I64, "skipped")
+    _chk(grads, F32, "grads"); _chk_status(status); _chk_decision(step, skipped)
     call("pm_grad_nonfinite_check", ptr(grads), grads.numel(), ptr(status), ptr(step), ptr(skipped), lr, beta1, beta2,
          int(bool(window)), stream())
 
@@ -715,8 +722,7 @@ def grad_nonfinite_check(grads, status, step=None, skipped=None, lr=0.0, beta1=0
 def adam_step_guarded(params, grads, exp_avg, exp_avg_sq, beta1, beta2, eps, status, grad_scale=1.0):
     """`adam_step` at the t and with the scalars `grad_nonfinite_check` decided, unless it decided a skip: then nothing is
     stored.  An applied step equals `adam_step` at that t bit for bit."""
-    for t, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _chk(t, F32, n)
+    _chk_adam(params, grads, exp_avg, exp_avg_sq)
     _chk_status(status)
     call("pm_adam_step_guarded", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), beta1, beta2,
          eps, grad_scale, ptr(status), stream())
@@ -756,11 +762,7 @@ def grad_sumsq(grads, clip):
 
 def grad_nonfinite_check_sumsq(grads, status, clip, step=None, skipped=None, lr=0.0, beta1=0.0, beta2=0.0, window=False):
     """`grad_nonfinite_check` and `grad_sumsq` in one read of the gradient."""
-    _chk(grads, F32, "grads"); _chk_status(status); _chk_clip(clip)
-    if (step is None) != (skipped is None):
-        raise ValueError("step and skipped go together")
-    if step is not None:
-        _chk(step, I64, "step"); _chk(skipped, I64, "skipped")
+    _chk(grads, F32, "grads"); _chk_status(status); _chk_clip(clip); _chk_decision(step, skipped)
     call("pm_grad_nonfinite_check_sumsq", ptr(grads), grads.numel(), ptr(status), ptr(step), ptr(skipped), lr, beta1, beta2,
          int(bool(window)), ptr(clip), stream())
 
@@ -780,8 +782,7 @@ def grad_clip_finish(clip, max_norm, grad_scale=1.0, row=None):
 def adam_step_clipped(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, clip, status=None):
     """`adam_step` (or, with the guarded step's `status`, `adam_step_guarded`: `lr` and `step` are then unused) with the
     gradient scale `grad_clip_finish` left in `clip`.  Unclipped (coef == 1) it equals them bit for bit."""
-    for t, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _chk(t, F32, n)
+    _chk_adam(params, grads, exp_avg, exp_avg_sq)
     _chk_clip(clip)
     if status is not None:
         _chk_status(status)

@@ -385,6 +385,47 @@ class HipTrainer:
         self.buckets.launch(0)
         return out
 
+    def _optimizer_update(self, grads, mean_scale):
+        """The optimizer part of a step (training.py:160-166) in three stages: the read of the gradient that the options
+        need, the finish of the clip, one Adam launch.  Raw `call`s throughout: the buffers are the trainer's own, made by
+        its constructor, and the checks of the `ops` wrappers would be host work on every step."""
+        guard, clip = self._guard, self.max_grad_norm is not None
+        st, gp, n = stream(), grads.data_ptr(), grads.numel()
+        b1, b2 = self.betas[0], self.betas[1]
+        if guard:                                      # scaler.step(optimizer): no update on found_inf (training.py:160-162);
+            sp, cp = self._ovf_status.data_ptr(), self._ovf_counts.data_ptr()      # the check decides t and its scalars
+            decide = (sp, cp, cp + 8, self.lr, b1, b2, 1)
+            lr, t = 0.0, 0
+        else:
+            self.step_count += 1
+            sp, lr, t = None, self.lr, self.step_count
+        if clip:                                       # this update's (norm, coef) row (host pointer arithmetic)
+            kp, rp = self._clip.data_ptr(), self._nhist[self._nrows].data_ptr()
+        # 1. the read of the gradient (with both options the check's read also takes the sum of squares)
+        if guard and clip:
+            call("pm_grad_nonfinite_check_sumsq", gp, n, *decide, kp, st)
+        elif guard:
+            call("pm_grad_nonfinite_check", gp, n, *decide, st)
+        elif clip:
+            call("pm_grad_sumsq", gp, n, kp, st)
+        # 2. norm, coef and the gradient scale from the partial sums
+        if clip:
+            call("pm_grad_clip_finish", kp, mean_scale, self.max_grad_norm, rp, st)
+        # 3. Adam: the scale from the clip block or `mean_scale`, t and its scalars from the decision or the host
+        bufs = (self.vae.flat_params.data_ptr(), gp, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n)
+        if clip:
+            call("pm_adam_step_clipped", *bufs, lr, b1, b2, self.eps, t, kp, sp, st)
+        elif guard:
+            call("pm_adam_step_guarded", *bufs, b1, b2, self.eps, mean_scale, sp, st)
+        else:
+            call("pm_adam_step", *bufs, lr, b1, b2, self.eps, t, mean_scale, st)
+        if guard:
+            self._ovf_host.copy_(self._ovf_counts[1:2], non_blocking=True)
+            self._ovf_event.record()
+            self._ovf_copied = True
+        if clip:
+            self._nrows += 1                               # (behind the launches: the count is of rows that were written)
+
     def train_step(self, graph, eps: Optional[torch.Tensor] = None):
         """One batch of the training loop (training.py:137-172) on `graph` (device batch): forward, losses, backward
         and — every `iters_to_accumulate`-th call — the Adam update and the LR-schedule step.  Returns the device
@@ -421,40 +462,7 @@ class HipTrainer:
             grads = self.grad_accum
         else:
             mean_scale = self.buckets.wait()
-        # ---- optimizer (training.py:160-172)
-        if clip:                                       # this update's (norm, coef) row (host pointer arithmetic)
-            kp, rp = self._clip.data_ptr(), self._nhist[self._nrows].data_ptr()
-        if self._guard:                                # scaler.step(optimizer): no update on found_inf (training.py:160-162)
-            st, sp = stream(), self._ovf_status.data_ptr()
-            cp = self._ovf_counts.data_ptr()
-            if clip:                                   # the check's read of the gradient also takes the sum of squares
-                call("pm_grad_nonfinite_check_sumsq", grads.data_ptr(), grads.numel(), sp, cp, cp + 8, self.lr,
-                     self.betas[0], self.betas[1], 1, kp, st)
-                call("pm_grad_clip_finish", kp, mean_scale, self.max_grad_norm, rp, st)
-                call("pm_adam_step_clipped", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
-                     self.exp_avg_sq.data_ptr(), grads.numel(), 0.0, self.betas[0], self.betas[1], self.eps, 0, kp, sp, st)
-            else:
-                call("pm_grad_nonfinite_check", grads.data_ptr(), grads.numel(), sp, cp, cp + 8, self.lr, self.betas[0],
-                     self.betas[1], 1, st)
-                call("pm_adam_step_guarded", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
-                     self.exp_avg_sq.data_ptr(), grads.numel(), self.betas[0], self.betas[1], self.eps, mean_scale, sp, st)
-            self._ovf_host.copy_(self._ovf_counts[1:2], non_blocking=True)
-            self._ovf_event.record()
-            self._ovf_copied = True
-        elif clip:
-            self.step_count += 1
-            st = stream()
-            call("pm_grad_sumsq", grads.data_ptr(), grads.numel(), kp, st)
-            call("pm_grad_clip_finish", kp, mean_scale, self.max_grad_norm, rp, st)
-            call("pm_adam_step_clipped", vae.flat_params.data_ptr(), grads.data_ptr(), self.exp_avg.data_ptr(),
-                 self.exp_avg_sq.data_ptr(), grads.numel(), self.lr, self.betas[0], self.betas[1], self.eps,
-                 self.step_count, kp, None, st)
-        else:
-            self.step_count += 1
-            ops.adam_step(vae.flat_params, grads, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0],
-                          self.betas[1], self.eps, self.step_count, grad_scale=mean_scale)
-        if clip:
-            self._nrows += 1                               # (behind the launches: the count is of rows that were written)
+        self._optimizer_update(grads, mean_scale)
         if self.sched is not None:
             self.lr = self.sched.step()
         return out

@@ -196,7 +196,7 @@ def _adam_buffers(n, offset, seed):
     return p, m, v, g
 
 
-@pytest.mark.parametrize("n,offset", [(8192, 0), (4099, 0), (4096, 1)])
+@pytest.mark.parametrize("n,offset", [(8192, 0), (4099, 0), (4096, 1), (1, 0), (3, 1), (4, 0)])
 @pytest.mark.parametrize("guard", [False, True])
 @pytest.mark.parametrize("mode", ["inf", "x10"])
 def test_unclipped_adam_equals_adam_step_bitwise(n, offset, guard, mode):

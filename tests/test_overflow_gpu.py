@@ -64,7 +64,7 @@ def _adam_buffers(n, offset, seed):
     return p, m, v, g
 
 
-@pytest.mark.parametrize("n,offset", [(8192, 0), (4099, 0), (4096, 1), (10_800_000, 0)])
+@pytest.mark.parametrize("n,offset", [(8192, 0), (4099, 0), (4096, 1), (10_800_000, 0), (1, 0), (3, 1), (4, 0)])
 def test_guarded_adam_applied_equals_adam_step_bitwise(n, offset):
     """No cause set: over several steps the parameters and both moments equal `ops.adam_step` at the same t bit for bit
     (float4 kernel and scalar kernel), the device t the check's last workgroup advances is the step number, nothing is
