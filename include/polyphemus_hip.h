@@ -63,7 +63,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   pm_adam_step_guarded, pm_adam_bias_scalars; the PM_OVF_* status layout).  Additive, same version: the training
  *   accuracies (pm_vae_step_set_metrics, pm_unembed_ce_metrics, pm_unembed_ce_rows_metrics, pm_content_accuracy_slots,
  *   pm_train_metric_counts; no existing struct or argument list changed); gradient clipping by the global norm
- *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout). */
+ *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout); the
+ *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -918,6 +919,35 @@ int pm_grad_clip_finish(double* clip, float grad_scale, float max_norm, double* 
 int pm_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                          float beta1, float beta2, float eps, int32_t step, const double* clip, const uint32_t* status,
                          pm_stream_t stream);
+
+/* ------------------------------------------------------------------ exponential moving average of the parameters
+ * No line of training.py stands behind these entries: the reference loop keeps no average.  They give the fused step what
+ * `torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay))` with `update_parameters` behind
+ * every `optimizer.step()` would give the reference loop, inside the Adam launch: the kernel holds the parameter it has just
+ * stored, so the average costs 4 bytes more read and 4 more written per parameter instead of a pass of its own, and an
+ * update the guarded step skips leaves the average where it was — a decision only the device knows.  Additive, same ABI
+ * version.
+ *   ema[i] = ema_weight == 1 ? params[i] : ema[i] + ema_weight * (params[i] - ema[i])      ema_weight = 1 - decay
+ * with params[i] the fp32 value the step stored (torch's lerp form; a weight of 1 copies, since e + (p - e) is not exactly
+ * p in fp32).  fp32 caveat: at decay = 0.9999 an increment below half an ulp of ema[i] is lost until |params[i] - ema[i]|
+ * has grown past ulp / (2 ema_weight): the average then lags the exact one; it does not drift away from it. */
+/* The superset of pm_adam_step, pm_adam_step_guarded and pm_adam_step_clipped, with the average: params, exp_avg and
+ * exp_avg_sq end up bit for bit as those entries leave them.
+ *   clip == NULL: the gradient scale is grad_scale; otherwise it is read from clip[PM_CLIP_GSCALE], grad_scale ignored.
+ *   status == NULL: step (> 0) and lr come from the host; otherwise the decision and its scalars come from the status
+ *   block pm_grad_nonfinite_check* decided in, step and lr ignored, and a skipped step stores nothing — not into ema either.
+ * ema: n floats that share no element with the four other buffers.  Its alignment never chooses between the float4 and the
+ * scalar kernel (the other four buffers and n do, as in the entries above: the two kernels differ in a last bit of exp_avg,
+ * and the average must not move it); the float4 kernel moves an average that is not 16-byte aligned as four floats.
+ * PM_E_INVALID: a NULL among the five buffers, such an overlap, a clip that is not 8-byte aligned, n <= 0, or an
+ * ema_weight outside (0, 1] (NaN included). */
+int pm_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                     float beta1, float beta2, float eps, int32_t step, float grad_scale, float ema_weight,
+                     const double* clip, const uint32_t* status, pm_stream_t stream);
+/* a[0..n) <-> b[0..n) in place (evaluating, generating and saving from the average without moving the model's parameter
+ * buffer): float4 when both are 16-byte aligned and n % 4 == 0, scalar otherwise.  PM_E_INVALID: NULL, n <= 0 or ranges
+ * that share an element. */
+int pm_buffer_swap(float* a, float* b, int64_t n, pm_stream_t stream);
 
 /* Gradient accumulation over `iters_to_accumulate` micro-batches (training.py:149,158: backward of tot_loss / k, optimizer
  * step every k-th batch): accum = (first ? 0 : accum) + scale * grads, scale = 1 / k. */

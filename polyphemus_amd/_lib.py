@@ -169,6 +169,8 @@ _SIGS = {
     "pm_grad_nonfinite_check_sumsq": "plpppfffips",
     "pm_grad_clip_finish": "pffps",
     "pm_adam_step_clipped": "pppplffffipps",
+    "pm_adam_step_ema": "ppppplffffiffpps",
+    "pm_buffer_swap": "ppls",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",

@@ -3,7 +3,8 @@
 // Reference: optim.Adam(vae.parameters(), betas=(0.9,0.98), eps=1e-9) (train.py:181,
 // training.json:11-18), stepped at training.py:160-166 as 152 per-tensor updates.  Here all
 // parameters, gradients and moments live in four flat buffers (also the unit of the data-parallel
-// gradient all-reduce), so the step is one HBM-bound pass: 16 B read + 12 B written per parameter.
+// gradient all-reduce), so the step is one HBM-bound pass: 16 B read + 12 B written per parameter (20 B + 16 B with the
+// parameter average riding in it).
 // Parameters whose gradient has been zero on EVERY step so far (the structure decoder under the
 // reference's loss quirk, SURVEY B-1) stay bit-identical: m = v = 0 gives an update of 0 / eps = 0,
 // the same end state as torch's `grad is None` skip.  This is not a general skip: a parameter with
@@ -21,16 +22,23 @@ __host__ __device__ static inline void adam_bias_scalars(int64_t t, float lr, fl
   inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
 }
 // where the update's scalars come from: the host's values, or — read on the device — gscale from the clip block pm_grad_clip_finish
-// wrote (CLIP) and the decision with its step_size / inv_bc2_sqrt from the status block of the check (GUARD)
-struct AdamSources { float step_size, inv_bc2_sqrt, gscale; const double* clip; const unsigned* status; };
+// wrote (CLIP) and the decision with its step_size / inv_bc2_sqrt from the status block of the check (GUARD); ema_w: the weight of
+// the fresh parameter in the average (EMA), 1 - decay
+struct AdamSources { float step_size, inv_bc2_sqrt, gscale; const double* clip; const unsigned* status; float ema_w; };
 // The Adam update over the flat buffers, VT = float4 or float; n counts VTs.  GUARD || CLIP: thread 0 reads the device sources once
 // per workgroup; a skipped step returns before any store.  The loop is one text, so with coef == 1 (gscale == grad_scale) and an
 // applied decision the plain, the guarded and the clipped steps are bit-identical.  The lanes index the buffers themselves (the
 // compiler still moves whole float4s) and the update is these three statements, no locals: which product of m's and of v's update
-// the compiler fuses into the FMA depends on such details of the text, and a last bit of m or v with it
-template <typename VT, bool GUARD, bool CLIP>
+// the compiler fuses into the FMA depends on such details of the text, and a last bit of m or v with it.  EMA: behind them the
+// average moves towards the parameter just stored (the lerp of torch.optim.swa_utils.get_ema_multi_avg_fn; a weight of 1 copies,
+// since e + (p - e) is not exactly p in fp32) — 4 B more read and 4 B more written per parameter, and a skipped step leaves it alone.
+// ET: how the average is moved, VT or — float4 kernel, an average that is not 16-byte aligned — four floats of element alignment
+struct alignas(4) Float4U { float f[4]; };
+template <typename VT, bool GUARD, bool CLIP, bool EMA, typename ET = VT>
 __global__ void __launch_bounds__(256) k_adam(VT* __restrict__ p, const VT* __restrict__ g, VT* __restrict__ m,
-                                              VT* __restrict__ v, int64_t n, float b1, float b2, float eps, AdamSources a) {
+                                              VT* __restrict__ v, ET* __restrict__ ema, int64_t n, float b1, float b2, float eps,
+                                              AdamSources a) {
+  static_assert(sizeof(ET) == sizeof(VT), "the average moves in steps of one VT");
   float step_size = a.step_size, inv_bc2_sqrt = a.inv_bc2_sqrt, gscale = a.gscale;
   if constexpr (GUARD || CLIP) {
     __shared__ unsigned sh[4];
@@ -46,29 +54,44 @@ __global__ void __launch_bounds__(256) k_adam(VT* __restrict__ p, const VT* __re
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float* P = reinterpret_cast<float*>(p + i); const float* Gd = reinterpret_cast<const float*>(g + i);
     float* M = reinterpret_cast<float*>(m + i); float* V = reinterpret_cast<float*>(v + i);
+    ET avg;                                       // (the average's VT in registers: one whole load in front of the weight test)
+    if constexpr (EMA) avg = ema[i];
+    float* E = reinterpret_cast<float*>(&avg);
 #pragma unroll
     for (int j = 0; j < (int)(sizeof(VT) / 4); ++j) {
       const float gr = Gd[j] * gscale;
       M[j] = b1 * M[j] + (1.f - b1) * gr;
       V[j] = b2 * V[j] + (1.f - b2) * gr * gr;
       P[j] -= step_size * (M[j] / (sqrtf(V[j]) * inv_bc2_sqrt + eps));
+      if constexpr (EMA) E[j] = (a.ema_w == 1.f) ? P[j] : E[j] + a.ema_w * (P[j] - E[j]);
     }
+    if constexpr (EMA) ema[i] = avg;
   }
 }
-// the float4 kernel for 16-byte-aligned buffers with n % 4 == 0, the scalar one otherwise; at most 4096 workgroups of 256
-template <bool GUARD, bool CLIP>
+// the float4 kernel for 16-byte-aligned buffers with n % 4 == 0, the scalar one otherwise; at most 4096 workgroups of 256.  The
+// average's own alignment never picks the kernel — the two differ in a last bit of m (see above), and the option must not move
+// p, m or v: the float4 kernel moves an average that is not 16-byte aligned as four floats
+template <bool GUARD, bool CLIP, bool EMA = false>
 static int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps,
-                       const AdamSources& a, pm_stream_t stream) {
+                       const AdamSources& a, pm_stream_t stream, float* ema = nullptr) {
   const bool vec = !(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) && (n % 4) == 0;
   const int64_t nv = vec ? n / 4 : n;
   int64_t nb = pm_cdiv(nv, 256); if (nb > 4096) nb = 4096;
+  if constexpr (EMA) {
+    if (vec && ((uintptr_t)ema & 15)) {
+      hipLaunchKernelGGL((k_adam<float4, GUARD, CLIP, true, Float4U>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                         reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m),
+                         reinterpret_cast<float4*>(v), reinterpret_cast<Float4U*>(ema), nv, b1, b2, eps, a);
+      return pm_check_launch();
+    }
+  }
   if (vec)
-    hipLaunchKernelGGL((k_adam<float4, GUARD, CLIP>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((k_adam<float4, GUARD, CLIP, EMA>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g), reinterpret_cast<float4*>(m),
-                       reinterpret_cast<float4*>(v), nv, b1, b2, eps, a);
+                       reinterpret_cast<float4*>(v), reinterpret_cast<float4*>(ema), nv, b1, b2, eps, a);
   else
-    hipLaunchKernelGGL((k_adam<float, GUARD, CLIP>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, nv, b1,
-                       b2, eps, a);
+    hipLaunchKernelGGL((k_adam<float, GUARD, CLIP, EMA>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema,
+                       nv, b1, b2, eps, a);
   return pm_check_launch();
 }
 // acc = (first ? 0 : acc) + scale * g   (gradient accumulation over micro-batches, training.py:149,158)
@@ -298,6 +321,49 @@ extern "C" int pm_adam_step_clipped(float* params, const float* grads, float* ex
   if (status) return launch_adam<true, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream);
   adam_bias_scalars(step, lr, beta1, beta2, a.step_size, a.inv_bc2_sqrt);       // (unguarded: the host's scalars, as pm_adam_step)
   return launch_adam<false, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream);
+}
+
+// ---- exponential moving average of the parameters (include/polyphemus_hip.h)
+// [a, a + n) and [b, b + n) share an element
+static inline bool ranges_overlap(const float* a, const float* b, int64_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+  return x < y ? y - x < len : x - y < len;
+}
+extern "C" int pm_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                                float lr, float beta1, float beta2, float eps, int32_t step, float grad_scale, float ema_weight,
+                                const double* clip, const uint32_t* status, pm_stream_t stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !ema || n <= 0 || ((uintptr_t)clip & 7) || (!status && step <= 0) ||
+      !(ema_weight > 0.f && ema_weight <= 1.f))                                  // (a NaN weight fails the comparison too)
+    return PM_E_INVALID;
+  if (ranges_overlap(ema, params, n) || ranges_overlap(ema, grads, n) || ranges_overlap(ema, exp_avg, n) ||
+      ranges_overlap(ema, exp_avg_sq, n))
+    return PM_E_INVALID;
+  AdamSources a{0.f, 0.f, grad_scale, clip, status, ema_weight};
+  if (!status) adam_bias_scalars(step, lr, beta1, beta2, a.step_size, a.inv_bc2_sqrt);
+  if (status && clip) return launch_adam<true, true, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream, ema);
+  if (status) return launch_adam<true, false, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream, ema);
+  if (clip) return launch_adam<false, true, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream, ema);
+  return launch_adam<false, false, true>(params, grads, exp_avg, exp_avg_sq, n, beta1, beta2, eps, a, stream, ema);
+}
+// a <-> b, VT = float4 or float; n counts VTs
+template <typename VT>
+__global__ void __launch_bounds__(256) k_buffer_swap(VT* __restrict__ a, VT* __restrict__ b, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const VT x = a[i], y = b[i];
+    a[i] = y; b[i] = x;
+  }
+}
+extern "C" int pm_buffer_swap(float* a, float* b, int64_t n, pm_stream_t stream) {
+  if (!a || !b || n <= 0 || ranges_overlap(a, b, n)) return PM_E_INVALID;
+  const bool vec = !(((uintptr_t)a | (uintptr_t)b) & 15) && (n % 4) == 0;
+  const int64_t nv = vec ? n / 4 : n;
+  int64_t nb = pm_cdiv(nv, 256); if (nb > 4096) nb = 4096;
+  if (vec)
+    hipLaunchKernelGGL(k_buffer_swap<float4>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<float4*>(a), reinterpret_cast<float4*>(b), nv);
+  else
+    hipLaunchKernelGGL(k_buffer_swap<float>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a, b, nv);
+  return pm_check_launch();
 }
 
 extern "C" int pm_abi_version(void) { return PM_ABI_VERSION; }

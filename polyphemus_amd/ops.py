@@ -788,3 +788,44 @@ def adam_step_clipped(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
         _chk_status(status)
     call("pm_adam_step_clipped", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), params.numel(), lr, beta1, beta2,
          eps, step, ptr(clip), ptr(status), stream())
+
+
+# ---- exponential moving average of the parameters (include/polyphemus_hip.h, "exponential moving average of the parameters")
+def ema_weight(decay) -> float:
+    """The weight of the fresh parameter in the average as the kernel takes it: float32(1 - decay), the difference formed in
+    double.  ValueError unless `decay` is a number (not a bool) in [0, 1) that is still below 1 as a float32: past that the
+    weight is under 2^-25, where ema + weight * (p - ema) rounds back to ema for every p within a factor of two of it (and
+    under 1.4e-45 the weight itself rounds to 0) — an average that never moves."""
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay < 1.0:
+        raise ValueError(f"ema_decay must be None or a number in [0, 1), not {decay!r}")
+    w = ctypes.c_float(1.0 - float(decay)).value
+    if not ctypes.c_float(decay).value < 1.0 or not 0.0 < w <= 1.0:
+        raise ValueError(f"ema_decay = {decay!r} is 1 as a float32 (weight {w!r}): the average would never move")
+    return w
+
+
+def adam_step_ema(params, grads, exp_avg, exp_avg_sq, ema, lr, beta1, beta2, eps, step, ema_weight, grad_scale=1.0, clip=None,
+                  status=None):
+    """`adam_step` (or, with `clip` / `status`, `adam_step_clipped` / `adam_step_guarded`: the same bits in params and both
+    moments) that also moves `ema` towards the parameter it stored: ema += ema_weight * (params - ema), a copy at
+    ema_weight == 1.  A skipped step leaves `ema` alone."""
+    _chk_adam(params, grads, exp_avg, exp_avg_sq)
+    _chk(ema, F32, "ema")
+    if ema.numel() != params.numel():
+        raise ValueError("ema must have as many elements as params")
+    if not 0.0 < ema_weight <= 1.0:
+        raise ValueError(f"ema_weight must be in (0, 1], not {ema_weight!r}")
+    if clip is not None:
+        _chk_clip(clip)
+    if status is not None:
+        _chk_status(status)
+    call("pm_adam_step_ema", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), ptr(ema), params.numel(), lr, beta1,
+         beta2, eps, step, grad_scale, ema_weight, ptr(clip), ptr(status), stream())
+
+
+def buffer_swap(a, b):
+    """a <-> b in place (two fp32 buffers of one size that do not overlap)."""
+    _chk(a, F32, "a"); _chk(b, F32, "b")
+    if a.numel() != b.numel():
+        raise ValueError("a and b must have the same number of elements")
+    call("pm_buffer_swap", ptr(a), ptr(b), a.numel(), stream())

@@ -21,6 +21,7 @@ p = 0.1 is always on in training (B-2).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -70,7 +71,7 @@ class HipTrainer:
                  structure_loss_on_logits: bool = False, beta: float = 0.0, process_group=None, native: bool = True,
                  iters_to_accumulate: int = 1, global_token_mean: bool = False, sync_bn: bool = False,
                  overflow: str = "ignore", train_metrics: bool = False, metrics_capacity: int = 1024,
-                 max_grad_norm: Optional[float] = None, grad_norm_capacity: int = 1024):
+                 max_grad_norm: Optional[float] = None, grad_norm_capacity: int = 1024, ema_decay: Optional[float] = None):
         if overflow not in ("ignore", "skip"):
             raise ValueError(f"overflow must be 'ignore' or 'skip', not {overflow!r}")
         if max_grad_norm is not None:
@@ -81,6 +82,8 @@ class HipTrainer:
                                  f"not {max_grad_norm!r}")
         if isinstance(grad_norm_capacity, bool) or not isinstance(grad_norm_capacity, int) or grad_norm_capacity < 1:
             raise ValueError(f"grad_norm_capacity must be a positive int, not {grad_norm_capacity!r}")
+        # (the average's weight crosses the C ABI as float32(1 - ema_decay): rejected here, not inside a step)
+        self._ema_w = None if ema_decay is None else ops.ema_weight(ema_decay)
         if not isinstance(train_metrics, bool):
             raise ValueError(f"train_metrics must be True or False, not {train_metrics!r}")
         if train_metrics and (not isinstance(metrics_capacity, int) or metrics_capacity < 1):
@@ -173,6 +176,17 @@ class HipTrainer:
         self.grad_accum = torch.zeros_like(flat) if self.iters_to_accumulate > 1 else None
         self._accum_bucket = GradBuckets(self.grad_accum, [], process_group) if self.grad_accum is not None else None
         broadcast_([vae.flat_params, vae.flat_buffers], 0, process_group)
+        # Exponential moving average of the parameters (what `torch.optim.swa_utils.AveragedModel` with
+        # `get_ema_multi_avg_fn(ema_decay)`, updated behind every `optimizer.step()`, gives the reference loop; the reference
+        # itself keeps none).  None: nothing of it runs.  A decay in [0, 1): `self.ema`, a flat buffer like the moments, starts
+        # as a copy of the (broadcast) initial weights — AveragedModel's first update copies too — and every APPLIED optimizer
+        # update moves it inside the Adam launch: ema += (1 - decay) * (p - ema).  An update the guard skips leaves it alone.
+        # Parameters only: BatchNorm's running statistics stay the live model's (AveragedModel(use_buffers=False)).
+        # `ema_weights()`, `evaluate*(ema=True)`, `ema_state_dict()` and the checkpoint use it.
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema = flat.detach().clone() if self._ema_w is not None else None
+        self._ema_t0 = 0                                   # Adam's t when the average started (n_averaged = t - t0)
+        self._ema_swapped = False                          # inside `ema_weights()`: flat_params holds the average
         vae.engine.set_sync_bn(process_group, self.sync_bn and self.world > 1)
         # every rank its own message-dropout stream (same seed = same masks on every replica): the model keeps its BASE
         # seed — what checkpoints store — and the rank only salts the seeds derived from it (VAE._next_seed), so building a
@@ -413,7 +427,10 @@ class HipTrainer:
             call("pm_grad_clip_finish", kp, mean_scale, self.max_grad_norm, rp, st)
         # 3. Adam: the scale from the clip block or `mean_scale`, t and its scalars from the decision or the host
         bufs = (self.vae.flat_params.data_ptr(), gp, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n)
-        if clip:
+        if self._ema_w is not None:                    # the one entry for the four combinations, the average riding in it
+            call("pm_adam_step_ema", *bufs[:4], self.ema.data_ptr(), n, lr, b1, b2, self.eps, t, mean_scale, self._ema_w,
+                 kp if clip else None, sp, st)
+        elif clip:
             call("pm_adam_step_clipped", *bufs, lr, b1, b2, self.eps, t, kp, sp, st)
         elif guard:
             call("pm_adam_step_guarded", *bufs, b1, b2, self.eps, mean_scale, sp, st)
@@ -431,6 +448,7 @@ class HipTrainer:
         and — every `iters_to_accumulate`-th call — the Adam update and the LR-schedule step.  Returns the device
         tensor [pitch, dur, structure, kld] of this batch's loss values (float64, no host sync)."""
         vae = self.vae
+        self._not_in_ema_weights("train_step")
         if not vae.training:
             raise RuntimeError("train_step needs vae.train()")
         if vae.flat_params.data_ptr() != self._flat_ptr:
@@ -468,11 +486,15 @@ class HipTrainer:
         return out
 
     # ---- evaluation (training.py:250-296 `evaluate`, :298-347 `_losses`, :349-497 `_accuracies`) --------------
-    def evaluate_batch(self, graph, eps: Optional[torch.Tensor] = None):
+    def evaluate_batch(self, graph, eps: Optional[torch.Tensor] = None, ema: bool = False):
         """One batch of `PolyphemusTrainer.evaluate`: eval-mode forward, the 7 losses and the 9 accuracies of the
         reference (same keys), computed by the loss / metric kernels with ONE host sync at the end (the reference
         takes 16).  Quirk kept (SURVEY B-1): the structure terms are evaluated on the target itself unless the
-        trainer was built with `structure_loss_on_logits=True`."""
+        trainer was built with `structure_loss_on_logits=True`.  `ema=True`: on the averaged parameters
+        (`ema_weights()`; needs `ema_decay`)."""
+        if ema:
+            with self.ema_weights():
+                return self.evaluate_batch(graph, eps)
         vae = self.vae
         was_training = vae.training
         vae.eval()
@@ -500,10 +522,13 @@ class HipTrainer:
         accs = ops.accuracies_from_counts(host[4:16] + [s_t.numel(), 0, 0, 0])
         return losses, accs
 
-    def evaluate(self, loader):
+    def evaluate(self, loader, ema: bool = False):
         """`PolyphemusTrainer.evaluate(loader)` (training.py:250-296): per-batch losses / accuracies averaged over the
         batches of `loader` (plain means of the per-batch values, like the reference's `mean(l)`); restores the
-        training mode it found."""
+        training mode it found.  `ema=True`: on the averaged parameters (one swap around the whole loader)."""
+        if ema:
+            with self.ema_weights():
+                return self.evaluate(loader)
         losses: Dict[str, list] = {}
         accs: Dict[str, list] = {}
         for graph in loader:
@@ -514,6 +539,51 @@ class HipTrainer:
                 accs.setdefault(k, []).append(v)
         mean = lambda l: sum(l) / len(l)
         return {k: mean(l) for k, l in losses.items()}, {k: mean(l) for k, l in accs.items()}
+
+    # ---- the parameter average ----------------------------------------------------------------------------------
+    def _need_ema(self, what: str) -> None:
+        if self._ema_w is None:
+            raise RuntimeError(f"{what} needs HipTrainer(..., ema_decay=...)")
+
+    def _not_in_ema_weights(self, what: str) -> None:
+        if getattr(self, "_ema_swapped", False):
+            raise RuntimeError(f"{what} inside `ema_weights()`: the model holds the averaged parameters there")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside this context the model IS the averaged model: `vae.flat_params` and `self.ema` exchange their contents
+        in place (`pm_buffer_swap`: no buffer moves, every parameter view and the native step's layout stay valid) and
+        exchange them back on the way out, an exception included.  `evaluate`, `generate_music`, `vae.state_dict()` and
+        `vae(graph)` in eval mode then read the average.  Parameters only: BatchNorm's running statistics are the live
+        model's (the `AveragedModel(use_buffers=False)` convention).  Not re-entrant; `train_step`, `save_checkpoint`
+        and `load_checkpoint` raise inside it."""
+        self._need_ema("ema_weights()")
+        self._not_in_ema_weights("ema_weights()")
+        flat = self.vae.flat_params
+        if flat.data_ptr() != self._flat_ptr:
+            raise RuntimeError("the model's flat parameter buffer moved after the trainer was built; rebuild it")
+        ops.buffer_swap(flat, self.ema)
+        self._ema_swapped = True
+        try:
+            yield self.vae
+        finally:
+            ops.buffer_swap(flat, self.ema)
+            self._ema_swapped = False
+
+    def ema_state_dict(self) -> dict:
+        """The averaged model in the layout of `vae.state_dict()` (the reference's keys, 255 at 8 layers; CPU copies):
+        parameters from `self.ema`, buffers — BatchNorm's running statistics among them — from the live model.  Swaps
+        nothing."""
+        self._need_ema("ema_state_dict()")
+        self._not_in_ema_weights("ema_state_dict()")
+        vae = self.vae
+        canon = {id(p): n for n, p in vae.named_parameters()}
+        at = {k: vae._offsets[canon[id(p)]] for k, p in vae.named_parameters(remove_duplicate=False)}
+        ema = self.ema.cpu()
+        out = {}
+        for k, v in vae.state_dict().items():
+            out[k] = ema[at[k]:at[k] + v.numel()].view(v.shape).clone() if k in at else v.detach().cpu().clone()
+        return out
 
     # ---- checkpoint interop (training.py:503-519 saves `optimizer.state_dict()` of torch.optim.Adam) ----------
     def optimizer_state_dict(self) -> dict:
@@ -561,20 +631,32 @@ class HipTrainer:
     def save_checkpoint(self, path: str, **extra) -> None:
         """The reference's checkpoint file (`_save_model`, training.py:498-519): a `torch.save`d dict with
         'model_state_dict' (the 255 reference keys), 'optimizer_state_dict' (torch.optim.Adam layout) and
-        'tot_batches'; `extra` carries the bookkeeping entries of the reference's loop (epoch, lrs, ...).
+        'tot_batches'; `extra` carries the bookkeeping entries of the reference's loop (epoch, lrs, ...).  With
+        `ema_decay` also 'ema_model_state_dict' (the average in the same keys) and 'ema' = {decay, n_averaged}.
         `generate.load_model` of the reference reads 'model_state_dict' from it."""
+        self._not_in_ema_weights("save_checkpoint")
         ckpt = dict(extra)
         ckpt.update(tot_batches=self.micro_batches, dropout_stream={"seed": self.vae.seed, "step": self.vae._step},
                     model_state_dict={k: v.detach().cpu().clone() for k, v in self.vae.state_dict().items()},
                     optimizer_state_dict=self.optimizer_state_dict())
+        if self._ema_w is not None:
+            # the average beside the live model, readable by key like 'model_state_dict'; n_averaged = the applied updates
+            # since it started, from the t the optimizer state just read
+            t = int(float(next(iter(ckpt["optimizer_state_dict"]["state"].values()))["step"]))
+            ckpt.update(ema_model_state_dict=self.ema_state_dict(),
+                        ema={"decay": self.ema_decay, "n_averaged": t - self._ema_t0})
         torch.save(ckpt, path)
 
     def load_checkpoint(self, path: str) -> dict:
         """Restore model, Adam moments, step count and LR-schedule position from `save_checkpoint` / a reference
-        checkpoint; returns the remaining entries."""
+        checkpoint; returns the remaining entries.  With `ema_decay` the average is restored too; a file without one
+        starts it from the loaded parameters.  Without `ema_decay` a file's average stays in the returned entries."""
+        self._not_in_ema_weights("load_checkpoint")
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
         self.vae.load_state_dict(ckpt.pop("model_state_dict"))
         self.load_optimizer_state_dict(ckpt.pop("optimizer_state_dict"))
+        if self._ema_w is not None:
+            self._load_ema(ckpt.pop("ema_model_state_dict", None), ckpt.pop("ema", None))
         self.micro_batches = int(ckpt.get("tot_batches", self.step_count * self.iters_to_accumulate))
         ds = ckpt.pop("dropout_stream", None)           # position of the counter-based dropout stream: a resumed run
         if ds is not None:                              # continues with fresh masks instead of replaying the old ones
@@ -584,6 +666,19 @@ class HipTrainer:
             #  attempts, not t)
             self.sched.update_steps = self.micro_batches // self.iters_to_accumulate if self._guard else self.step_count
         return ckpt
+
+    def _load_ema(self, sd: Optional[dict], meta: Optional[dict]) -> None:
+        """The average of a checkpoint into `self.ema`; without one the average starts from the loaded parameters."""
+        vae = self.vae
+        if sd is None:
+            self.ema.copy_(vae.flat_params.detach())
+            self._ema_t0 = self.step_count
+            return
+        P = dict(vae.named_parameters())
+        for n in vae._param_names:
+            o = vae._offsets[n]
+            self.ema[o:o + P[n].numel()].copy_(sd[n].reshape(-1))
+        self._ema_t0 = self.step_count - int((meta or {}).get("n_averaged", self.step_count))
 
     def losses_dict(self, out: torch.Tensor) -> dict:
         """Host copy of the loss vector in the reference's dict layout (this DOES sync)."""
