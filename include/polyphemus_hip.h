@@ -64,7 +64,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   accuracies (pm_vae_step_set_metrics, pm_unembed_ce_metrics, pm_unembed_ce_rows_metrics, pm_content_accuracy_slots,
  *   pm_train_metric_counts; no existing struct or argument list changed); gradient clipping by the global norm
  *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout); the
- *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap). */
+ *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap); sampled generation
+ *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -198,6 +199,45 @@ int pm_binary_from_logits(const float* s_logits /* [G,4,32] */, int32_t G, float
 int pm_mtp_from_logits(const float* c_logits /* [N,15,230] */, const float* s_tensor /* [G,4,32] 0/1 */, int32_t G,
                        int64_t N, int32_t* bar_nodes /* [G] */, int32_t* node_ptr /* [G+1] */,
                        float* mtp /* [G,4,32,15,230] */, pm_stream_t stream);
+
+/* ------------------------------------------------------------------ sampled generation
+ * No line of the reference stands behind these entries: its `muspy_from_mtp` (utils.py:103-105) takes the arg-max of every
+ * (cell, slot, head), so one latent gives one piece.  pm_sample_tokens draws the pitch and the duration token of every
+ * (node, slot) row on the device instead (temperature, top-k, nucleus), pm_mtp_from_tokens lays their one-hot rows out as
+ * the pianoroll, whose per-head arg-max is then the drawn token: `muspy_from_mtp` is fed unchanged.  Additive, same ABI
+ * version.
+ *
+ * c_logits is [N,15,230] fp32, contiguous; row r = n*15 + slot.  Head 0 (pitch) is the columns [0,131), head 1 (duration)
+ * the columns [131,230): V = 131 / 99, a token is a column index inside its head.  Every (row, head) is decided on its own.
+ *   rank    : tokens are ordered by raw logit, descending, equal logits by lower index first (exact: no arithmetic).
+ *   top_k   : 0 or >= V means off; otherwise the tokens of rank < top_k survive.
+ *   top_p   : in (0, 1], 1 means off.  Over the top_k survivors q_i = expf((l_i - max) * inv_T), Z = sum of q_i; a token
+ *             survives iff the q-mass of the survivors that outrank it is < top_p * Z.  The top token always survives.  The
+ *             order of the summations is the implementation's choice.
+ *   draw    : the arg-max over the survivors of l_i * inv_T + g_i in fp32 (a product, then a sum), lowest index on ties;
+ *               inv_T = (float)(1.0 / (double)temperature)
+ *               g_i   = -logf(-logf(u_i))                     (logf, not a fast variant: the library is built without fast-math)
+ *               u_i   = ((h >> 9) + 0.5f) * 2^-23             (exact in fp32, strictly inside (0, 1))
+ *               h     = pm_mix32(key(seed, head, r) + token * 0xC2B2AE35u)
+ *               key   = pm_mix32(pm_mix32(seed ^ (head + 1u) * 0x9E3779B9u) ^ (r * 0x85EBCA6Bu + 0x27D4EB2Fu))
+ *             (pm_mix32 and the key construction are those of the dropout stream, csrc/common.h.)  The stream is a pure
+ *             function of (seed, head, row, token): it depends neither on the launch shape nor on the wave that has the row.
+ *   temperature == 0: greedy, the arg-max of the raw logits, lowest index on ties, no noise; top_k == 1 gives the same tokens.
+ *   non-finite logits: nothing is promised about which token comes out; every token written is in [0, V) and nothing is
+ *             written outside `tokens`.
+ * pm_sample_tokens: one wave per row, the logits read once, tokens [rows,2] int32 = {pitch, duration} written.
+ *   PM_E_INVALID (before any launch): a NULL pointer, rows <= 0 or >= 2^32, temperature < 0 / NaN / inf, top_k < 0, top_p
+ *   outside (0, 1] (NaN included).
+ * pm_mtp_from_tokens: pm_mtp_from_logits with an active cell holding, per slot, 1.0 at column `pitch` and at column
+ *   131 + `duration` and 0 elsewhere (tokens [N,15,2]); a token outside its head's range lights no column of that head.  The
+ *   silence of the inactive cells, the workspaces, node_ptr[G] and the argument checks are those of pm_mtp_from_logits.
+ * pm_sample_hash: host-callable, h >> 9 of the draw above (the 23 bits u_i is made of). */
+int pm_sample_tokens(const float* c_logits /* [rows,230] */, int64_t rows, float temperature, int32_t top_k, float top_p,
+                     uint32_t seed, int32_t* tokens /* [rows,2] */, pm_stream_t stream);
+int pm_mtp_from_tokens(const int32_t* tokens /* [N,15,2] */, const float* s_tensor /* [G,4,32] 0/1 */, int32_t G, int64_t N,
+                       int32_t* bar_nodes /* [G] */, int32_t* node_ptr /* [G+1] */, float* mtp /* [G,4,32,15,230] */,
+                       pm_stream_t stream);
+uint32_t pm_sample_hash(uint32_t seed, uint32_t row, uint32_t head, uint32_t token);
 
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):

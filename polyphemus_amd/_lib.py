@@ -171,13 +171,15 @@ _SIGS = {
     "pm_adam_step_clipped": "pppplffffipps",
     "pm_adam_step_ema": "ppppplffffiffpps",
     "pm_buffer_swap": "ppls",
+    "pm_sample_tokens": "plfifups",
+    "pm_mtp_from_tokens": "ppilppps",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",
           "pm_unembed_dh_scratch_bytes", "pm_unembed_row_counts_len"}
 ABI_VERSION = 9          # PM_ABI_VERSION of include/polyphemus_hip.h this table was written against
-EXPORTED = sorted(list(_SIGS) + ["pm_abi_version", "pm_build_info", "pm_dropout_hash", "pm_vae_layout_bytes",
-                                 "pm_vae_step_state_bytes"])
+EXPORTED = sorted(list(_SIGS) + ["pm_abi_version", "pm_build_info", "pm_dropout_hash", "pm_sample_hash",
+                                 "pm_vae_layout_bytes", "pm_vae_step_state_bytes"])
 
 _lib: Optional[C.CDLL] = None
 
@@ -208,6 +210,8 @@ def lib() -> C.CDLL:
         L.pm_build_info.restype = C.c_char_p
         L.pm_dropout_hash.argtypes = [C.c_uint32] * 4
         L.pm_dropout_hash.restype = C.c_uint32
+        L.pm_sample_hash.argtypes = [C.c_uint32] * 4
+        L.pm_sample_hash.restype = C.c_uint32
         _lib = L
     return _lib
 

@@ -9,7 +9,9 @@
 //                           one-hot pitch PAD, duration part all zero).  The reference writes the tensor three times
 //                           (zeros, masked put of the logits, masked put of the silence); here every cell is written
 //                           once, HBM-write bound: 13.8 KB per cell.
-// Byte / index work, bit-exact against the oracle (tests/test_generate_gpu.py).
+//   pm_mtp_from_tokens    : the same pianoroll with an active cell holding the one-hot rows of its node's sampled tokens
+//                           (csrc/sample.hip) instead of its logits: the reference's arg-max decoding then returns the tokens.
+// Byte / index work, bit-exact against the oracle (tests/test_generate_gpu.py, tests/test_sampling_gpu.py).
 #include "common.h"
 
 namespace {
@@ -74,10 +76,12 @@ __global__ void __launch_bounds__(1024) k_bar_scan(const int* __restrict__ a, in
   if (threadIdx.x == 1023) ptr[G] = sa[1023];
 }
 
-// one workgroup per (bar, track): 32 cells of 13.8 KB, each wave takes 8 of them
-__global__ void __launch_bounds__(256) k_mtp_fill(const float* __restrict__ c_logits, const float* __restrict__ s,
-                                                  const int* __restrict__ node_ptr, int64_t N,
-                                                  float* __restrict__ mtp) {
+// one workgroup per (bar, track): 32 cells of 13.8 KB, each wave takes 8 of them.  TOK: an active cell holds the one-hot
+// rows of its node's tokens [15][2] (pm_mtp_from_tokens) instead of a copy of its logits.
+template <bool TOK>
+__global__ void __launch_bounds__(256) k_mtp_fill(const float* __restrict__ c_logits, const int* __restrict__ tokens,
+                                                  const float* __restrict__ s, const int* __restrict__ node_ptr,
+                                                  int64_t N, float* __restrict__ mtp) {
   __shared__ uint32_t masks[4];
   const int g = blockIdx.x >> 2, k = blockIdx.x & 3;
   if (threadIdx.x < 128) {
@@ -94,7 +98,20 @@ __global__ void __launch_bounds__(256) k_mtp_fill(const float* __restrict__ c_lo
   for (int t = wave; t < 32; t += 4) {
     v2f* dst = reinterpret_cast<v2f*>(mtp + ((int64_t)(g * 4 + k) * 32 + t) * CELL);      // 13800 B: 8-byte aligned
     const int64_t n = n0 + __popc(m & ((1u << t) - 1u));
-    if (((m >> t) & 1u) && n < N) {
+    if (TOK && ((m >> t) & 1u) && n < N) {
+      // lane 2 row + head holds that row's token; a token outside its head's range lights no column
+      const int tk = lane < 2 * PM_N_SLOTS ? tokens[n * (2 * PM_N_SLOTS) + lane] : -1;
+      const int hot_l = (lane & 1) ? ((unsigned)tk < (unsigned)PM_N_DUR ? PM_N_PITCH + tk : -1)
+                                   : ((unsigned)tk < (unsigned)PM_N_PITCH ? tk : -1);
+      for (int i0 = 0; i0 < CELL / 2; i0 += 64) {                                                 // (whole wave: shuffles)
+        const int i = i0 + lane, e = 2 * i, row = min(e / PM_N_TOK, PM_N_SLOTS - 1), col = e - row * PM_N_TOK;
+        const int hp = __shfl(hot_l, 2 * row, 64), hd = __shfl(hot_l, 2 * row + 1, 64);
+        v2f v;
+        v.x = (col == hp || col == hd) ? 1.0f : 0.0f;
+        v.y = (col + 1 == hp || col + 1 == hd) ? 1.0f : 0.0f;
+        if (i < CELL / 2) __builtin_nontemporal_store(v, dst + i);
+      }
+    } else if (((m >> t) & 1u) && n < N) {
       const v2f* src = reinterpret_cast<const v2f*>(c_logits + n * CELL);
       for (int i = lane; i < CELL / 2; i += 64) __builtin_nontemporal_store(src[i], dst + i);
     } else {
@@ -128,6 +145,18 @@ extern "C" int pm_mtp_from_logits(const float* c_logits, const float* s_tensor, 
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
   hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
-  hipLaunchKernelGGL(k_mtp_fill, dim3(G * 4), dim3(256), 0, st, c_logits, s_tensor, node_ptr, N, mtp);
+  hipLaunchKernelGGL(k_mtp_fill<false>, dim3(G * 4), dim3(256), 0, st, c_logits, nullptr, s_tensor, node_ptr, N, mtp);
+  return pm_check_launch();
+}
+
+extern "C" int pm_mtp_from_tokens(const int32_t* tokens, const float* s_tensor, int32_t G, int64_t N, int32_t* bar_nodes,
+                                  int32_t* node_ptr, float* mtp, pm_stream_t stream) {
+  if ((!tokens && N > 0) || !s_tensor || !bar_nodes || !node_ptr || !mtp || G <= 0 || N < 0 || bar_nodes == node_ptr)
+    return PM_E_INVALID;
+  if ((int64_t)G * 4 > 0x7fffffffLL) return PM_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
+  hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
+  hipLaunchKernelGGL(k_mtp_fill<true>, dim3(G * 4), dim3(256), 0, st, nullptr, tokens, s_tensor, node_ptr, N, mtp);
   return pm_check_launch();
 }

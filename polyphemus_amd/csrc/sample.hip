@@ -1,0 +1,186 @@
+// sample.hip — stochastic decoding of the content logits on the device ("sampled generation", include/polyphemus_hip.h):
+// temperature, top-k and nucleus (top-p) sampling of the pitch and the duration token of every (node, slot) row.
+//
+//   k_sample_tokens : one wave per row of 230 logits (920 B, read once), 8 B of tokens written.  Lane l holds the columns
+//                     l, l + 64, l + 128, l + 192 (four coalesced 256-byte wave loads; the last one 38 lanes wide), so a
+//                     token's place in index order is (slot, lane) and the head of a column is known per slot except for
+//                     slot 2, where the lanes 0..2 end the pitch head and the lanes 3..63 begin the duration head.
+//                     The draw is a Gumbel arg-max, so no cumulative sum and no second random number per row; the filters
+//                     are an all-pairs pass over the row (every column broadcast once with v_readlane, compared against
+//                     the lane's own columns of the same head, two vector instructions per pair and count): it counts the tokens that outrank a column (top-k) and
+//                     sums their softmax mass (top-p) in one go, exact under ties, with no LDS and no atomics.
+//                     MODE 0 greedy and MODE 1 unfiltered skip that pass altogether.
+#include "common.h"
+
+namespace {
+
+enum { SAMPLE_GREEDY = 0, SAMPLE_PLAIN = 1, SAMPLE_TOPK = 2, SAMPLE_TOPP = 3 };
+
+// a candidate of the arg-max: score, then the lower token index
+struct Cand { float s; int c; };
+__device__ static inline Cand cand_better(Cand a, Cand b) {
+  return (b.s > a.s || (b.s == a.s && b.c < a.c)) ? b : a;
+}
+__device__ static inline Cand cand_wave(Cand a) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    Cand b;
+    b.s = __shfl_xor(a.s, o, 64);
+    b.c = __shfl_xor(a.c, o, 64);
+    a = cand_better(a, b);
+  }
+  return a;
+}
+__device__ static inline float bcast(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// Gumbel noise of (key, token): the header's u, g
+__device__ static inline float gumbel(uint32_t key, uint32_t token) {
+  const uint32_t h = pm_group_hash(key, token);
+  const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;          // 2^-23: exact, inside (0, 1)
+  return -logf(-logf(u));
+}
+
+// the logit as an unsigned word of the same order; -0 and +0 share one key (they are equal logits)
+__device__ static inline unsigned ukey(float x) {
+  const unsigned b = __float_as_uint(x + 0.0f);
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_sample_tokens(const float* __restrict__ c_logits, int64_t rows, float inv_t,
+                                                       int top_k, float top_p, uint32_t seed, int* __restrict__ tokens) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;                                                        // wave-uniform
+  const float* x = c_logits + r * PM_N_TOK;
+  // slot j = column lane + 64 j; head and token of the slot
+  const bool p2 = lane < 3;                                                     // slot 2: columns 128..130 are pitch
+  const bool live3 = lane < PM_N_TOK - 192;
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) v[j] = x[lane + 64 * j];
+  v[3] = live3 ? x[lane + 192] : -INFINITY;
+  const int tok[4] = {lane, lane + 64, p2 ? lane + 128 : lane - 3, lane + 192 - PM_N_PITCH};
+
+  bool live[4] = {true, true, true, live3};
+  float score[4];
+  if (MODE == SAMPLE_GREEDY) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) score[j] = v[j];
+  } else {
+    if (MODE != SAMPLE_PLAIN) {
+      // rank (tokens that outrank the column) and the softmax mass of those tokens, per column of this lane
+      float mp = fmaxf(fmaxf(v[0], v[1]), p2 ? v[2] : -INFINITY), md = fmaxf(p2 ? -INFINITY : v[2], v[3]);
+      mp = pm_wave_max(mp); md = pm_wave_max(md);
+      float q[4];
+      q[0] = expf((v[0] - mp) * inv_t); q[1] = expf((v[1] - mp) * inv_t);
+      q[2] = expf((v[2] - (p2 ? mp : md)) * inv_t);
+      q[3] = live3 ? expf((v[3] - md) * inv_t) : 0.f;
+      // Branch-free: a column's logit as an unsigned key of the same order (-0 = +0), and per target a threshold `thr` such
+      // that "the source outranks it" is key(source) > thr: its own key when the source comes later in index order, its
+      // key - 1 when it comes earlier (equal logits: the lower index outranks), the largest word when the source is of the
+      // other head (slot 2 holds both).  Within one slot the source lane l comes earlier for the lanes above l.
+      const unsigned NONE = 0xffffffffu;
+      unsigned key[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) key[j] = ukey(v[j]);
+      const unsigned k2p = p2 ? key[2] : NONE, k2p1 = p2 ? key[2] - 1u : NONE;      // slot 2 as a pitch / a duration target
+      const unsigned k2d = p2 ? NONE : key[2], k2d1 = p2 ? NONE : key[2] - 1u;
+      int cnt[4] = {0, 0, 0, 0};
+      float mass[4] = {0.f, 0.f, 0.f, 0.f};
+      auto pair = [&](unsigned sk, float sq, unsigned thr, int t) {
+        const bool o = sk > thr;
+        cnt[t] += o ? 1 : 0;
+        if (MODE == SAMPLE_TOPP) mass[t] += o ? sq : 0.f;
+      };
+      auto src = [&](int s, int l, unsigned& sk, float& sq) {
+        sk = (unsigned)__builtin_amdgcn_readlane((int)key[s], l);
+        sq = MODE == SAMPLE_TOPP ? bcast(q[s], l) : 0.f;
+      };
+      unsigned sk;
+      float sq;
+      // pitch columns 0..130 against this lane's pitch columns
+      for (int l = 0; l < 64; ++l) {
+        src(0, l, sk, sq);
+        pair(sk, sq, key[0] - (l < lane ? 1u : 0u), 0); pair(sk, sq, key[1] - 1u, 1); pair(sk, sq, k2p1, 2);
+      }
+      for (int l = 0; l < 64; ++l) {
+        src(1, l, sk, sq);
+        pair(sk, sq, key[0], 0); pair(sk, sq, key[1] - (l < lane ? 1u : 0u), 1); pair(sk, sq, k2p1, 2);
+      }
+      for (int l = 0; l < 3; ++l) {
+        src(2, l, sk, sq);
+        pair(sk, sq, key[0], 0); pair(sk, sq, key[1], 1); pair(sk, sq, l < lane ? k2p1 : k2p, 2);
+      }
+      // duration columns 131..229 against this lane's duration columns
+      for (int l = 3; l < 64; ++l) {
+        src(2, l, sk, sq);
+        pair(sk, sq, l < lane ? k2d1 : k2d, 2); pair(sk, sq, key[3] - 1u, 3);
+      }
+      for (int l = 0; l < PM_N_TOK - 192; ++l) {
+        src(3, l, sk, sq);
+        pair(sk, sq, k2d, 2); pair(sk, sq, key[3] - (l < lane ? 1u : 0u), 3);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) live[j] = live[j] && cnt[j] < top_k;
+      if (MODE == SAMPLE_TOPP) {
+        float zp = (live[0] ? q[0] : 0.f) + (live[1] ? q[1] : 0.f) + (live[2] && p2 ? q[2] : 0.f);
+        float zd = (live[2] && !p2 ? q[2] : 0.f) + (live[3] ? q[3] : 0.f);
+        zp = pm_wave_sum(zp); zd = pm_wave_sum(zd);
+        const float ep = top_p * zp, ed = top_p * zd;
+        live[0] = live[0] && mass[0] < ep; live[1] = live[1] && mass[1] < ep;
+        live[2] = live[2] && mass[2] < (p2 ? ep : ed); live[3] = live[3] && mass[3] < ed;
+      }
+    }
+    const uint32_t kp = pm_edge_key(seed, 0u, (uint32_t)r), kd = pm_edge_key(seed, 1u, (uint32_t)r);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool pitch = j < 2 || (j == 2 && p2);
+      score[j] = __fadd_rn(__fmul_rn(v[j], inv_t), gumbel(pitch ? kp : kd, (uint32_t)tok[j]));
+    }
+  }
+  // arg-max per head over the surviving columns; a row that leaves none (non-finite logits) gives token 0
+  Cand bp = {-INFINITY, 0}, bd = {-INFINITY, 0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool pitch = j < 2 || (j == 2 && p2);
+    const Cand c = {live[j] ? score[j] : -INFINITY, live[j] ? tok[j] : 0x7fffffff};
+    if (j < 2) bp = cand_better(bp, c);
+    else if (j == 3) bd = cand_better(bd, c);
+    else { if (pitch) bp = cand_better(bp, c); else bd = cand_better(bd, c); }
+  }
+  bp = cand_wave(bp); bd = cand_wave(bd);
+  const int tp = min(max(bp.c, 0), PM_N_PITCH - 1), td = min(max(bd.c, 0), PM_N_DUR - 1);
+  if (lane < 2) tokens[r * 2 + lane] = lane ? td : tp;
+}
+
+}  // namespace
+
+extern "C" uint32_t pm_sample_hash(uint32_t seed, uint32_t row, uint32_t head, uint32_t token) {
+  return pm_group_hash(pm_edge_key(seed, head, row), token) >> 9;
+}
+
+extern "C" int pm_sample_tokens(const float* c_logits, int64_t rows, float temperature, int32_t top_k, float top_p,
+                                uint32_t seed, int32_t* tokens, pm_stream_t stream) {
+  if (!c_logits || !tokens || rows <= 0 || rows >= ((int64_t)1 << 32)) return PM_E_INVALID;
+  if (!(temperature >= 0.f) || !(temperature <= 3.4028234663852886e38f)) return PM_E_INVALID;      // NaN, inf, negative
+  if (top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f)) return PM_E_INVALID;
+  const dim3 grid((unsigned)pm_cdiv(rows, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const bool k_on = top_k > 0 && top_k < PM_N_PITCH, p_on = top_p < 1.f;
+  const int kk = top_k == 0 ? 0x7fffffff : top_k;
+  if (temperature == 0.f || top_k == 1) {
+    hipLaunchKernelGGL(k_sample_tokens<SAMPLE_GREEDY>, grid, block, 0, st, c_logits, rows, 1.f, kk, top_p, seed, tokens);
+  } else {
+    const float inv_t = (float)(1.0 / (double)temperature);
+    if (p_on)
+      hipLaunchKernelGGL(k_sample_tokens<SAMPLE_TOPP>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
+    else if (k_on)
+      hipLaunchKernelGGL(k_sample_tokens<SAMPLE_TOPK>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
+    else
+      hipLaunchKernelGGL(k_sample_tokens<SAMPLE_PLAIN>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
+  }
+  return pm_check_launch();
+}

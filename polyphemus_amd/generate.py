@@ -14,10 +14,21 @@ def generate_z(bs: int, d_model: int, device) -> torch.Tensor:
     return torch.randn(bs, d_model, device=device)
 
 
-def generate_music(vae, z, s_cond=None, s_tensor_cond=None):
+def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
+                   return_tokens=False):
     """generate.py:21-37.  `s_cond` is a batch of bar graphs (`vae.decoder._structure_from_binary`) or None (the
     structure then comes from the decoder's own thresholded logits); `s_tensor_cond` [B,n_bars,4,32] is the binary
-    structure the pianoroll is laid out on when given.  Returns (mtp [B,n_bars,4,32,15,230], s_tensor bool)."""
+    structure the pianoroll is laid out on when given.  Returns (mtp [B,n_bars,4,32,15,230], s_tensor bool).
+
+    With `temperature`, `top_k` and `top_p` all None this is the reference's call: the active cells of `mtp` hold the
+    content logits, of which `muspy_from_mtp` takes the arg-max.  With any of them given the pitch and the duration token
+    of every (node, slot) are drawn on the device (`ops.sample_tokens`; `temperature` defaults to 1.0, 0 = arg-max) and the
+    active cells hold their one-hot rows, so `muspy_from_mtp` decodes the drawn piece unchanged.  `seed` in [0, 2^32)
+    makes the draw a pure function of the logits; None takes one from torch's CPU generator (`torch.manual_seed`
+    repeats a run; no device synchronisation).  `return_tokens` appends the int32 [N,15,2] tokens (pitch, duration) to
+    the returned tuple; without sampling they are the arg-max tokens of the logits `mtp` holds."""
+    ops.check_sampling_args(temperature, top_k, top_p, seed)
+    sampled = temperature is not None or top_k is not None or top_p is not None
     vae.decoder.__dict__.pop("_last_structure", None)
     s_logits, c_logits = vae.decoder(z, s_cond)
     if s_tensor_cond is not None:
@@ -26,5 +37,12 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None):
         s_tensor = vae.decoder.__dict__["_last_structure"].view(s_logits.shape).bool()
     else:
         s_tensor = vae.decoder._binary_from_logits(s_logits)
-    mtp = ops.mtp_from_logits(c_logits.detach().contiguous().float(), s_tensor)
-    return mtp, s_tensor
+    c_logits = c_logits.detach().contiguous().float()
+    if not sampled:
+        mtp = ops.mtp_from_logits(c_logits, s_tensor)
+        return (mtp, s_tensor, ops.sample_tokens(c_logits, temperature=0.0)) if return_tokens else (mtp, s_tensor)
+    if seed is None:
+        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+    tokens = ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed)
+    mtp = ops.mtp_from_tokens(tokens, s_tensor)
+    return (mtp, s_tensor, tokens) if return_tokens else (mtp, s_tensor)

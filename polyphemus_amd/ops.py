@@ -200,6 +200,62 @@ def mtp_from_logits(c_logits: torch.Tensor, s_tensor: torch.Tensor, check: bool 
     return mtp
 
 
+def check_sampling_args(temperature=None, top_k=None, top_p=None, seed=None) -> None:
+    """The argument rules of sampled generation (`sample_tokens`, `generate.generate_music`); None = left at its default.
+    Raises ValueError naming the argument."""
+    import math
+    import numbers
+    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if temperature is not None and not (real(temperature) and math.isfinite(temperature) and temperature >= 0):
+        raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
+    if top_k is not None and not (isinstance(top_k, numbers.Integral) and not isinstance(top_k, bool) and top_k >= 1):
+        raise ValueError(f"top_k must be an int >= 1, got {top_k!r}")
+    if top_p is not None and not (real(top_p) and 0 < top_p <= 1):
+        raise ValueError(f"top_p must be a number in (0, 1], got {top_p!r}")
+    if seed is not None and not (isinstance(seed, numbers.Integral) and not isinstance(seed, bool) and 0 <= seed < 1 << 32):
+        raise ValueError(f"seed must be an int in [0, 2^32), got {seed!r}")
+
+
+def sample_tokens(c_logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
+                  top_p: Optional[float] = None, seed: int = 0) -> torch.Tensor:
+    """`pm_sample_tokens` ("sampled generation" in include/polyphemus_hip.h): the pitch and the duration token of every
+    (node, slot) row of `c_logits` [N,15,230], drawn at `temperature` from the `top_k` best tokens and / or the `top_p`
+    nucleus of each head (None = filter off; temperature 0 = arg-max).  A pure function of the logits and `seed`.
+    Returns int32 [N,15,2]."""
+    check_sampling_args(temperature, top_k, top_p, seed)
+    _chk(c_logits, F32, "c_logits")
+    if c_logits.dim() != 3 or c_logits.shape[1:] != (C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR):
+        raise ValueError("c_logits must be [N,15,230]")
+    N = c_logits.shape[0]
+    tokens = torch.empty(N, C.MAX_SIMU_TOKENS - 1, 2, dtype=I32, device=c_logits.device)
+    if N:
+        call("pm_sample_tokens", ptr(c_logits), N * (C.MAX_SIMU_TOKENS - 1), float(temperature),
+             0 if top_k is None else min(int(top_k), 1 << 30), 1.0 if top_p is None else float(top_p), int(seed), ptr(tokens),
+             stream())
+    return tokens
+
+
+def mtp_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool = True) -> torch.Tensor:
+    """`mtp_from_logits` with the one-hot rows of `tokens` (int32 [N,15,2] = pitch, duration) on the active cells instead of
+    the nodes' logits: the per-head arg-max of an active cell returns its tokens, so the reference's `muspy_from_mtp`
+    decodes a sampled piece unchanged.  A token outside its head's range leaves the head's columns zero.  Same `check`."""
+    _chk(tokens, I32, "tokens")
+    if tokens.dim() != 3 or tokens.shape[1:] != (C.MAX_SIMU_TOKENS - 1, 2):
+        raise ValueError("tokens must be [N,15,2]")
+    if s_tensor.dim() != 4 or s_tensor.shape[-2:] != (4, 32):
+        raise ValueError("s_tensor must be [B,n_bars,4,32]")
+    s = s_tensor.to(F32).contiguous()
+    G, N, dev = s.numel() // 128, tokens.shape[0], tokens.device
+    bn, npt = torch.empty(G, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
+    mtp = torch.empty(*s_tensor.shape, C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR, dtype=F32, device=dev)
+    call("pm_mtp_from_tokens", ptr(tokens), ptr(s), G, N, ptr(bn), ptr(npt), ptr(mtp), stream())
+    if check:
+        active = int(npt[G])
+        if active != N:
+            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, tokens has {N} nodes")
+    return mtp
+
+
 def gcl_forward_fused(x, T, plan: Plan, dropout_p: float, seed: int, layer_uid: int, w_frag, bias, col_stats=None,
                       planes=None, use_classes: bool = True):
     """`pm_gcl_forward_fused`: h = A'(x) @ [W_t; W_4; W_5; root] + bias of one GCL layer in one kernel (compact graphs,
