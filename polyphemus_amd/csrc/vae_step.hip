@@ -42,15 +42,13 @@ namespace {
 //   PM_DAGG_BN=0, PM_DAGG_RES=0, PM_PLAN_SIDE=0, PM_CHORD_TABLES=0, PM_H2=0, PM_BAR_ROUTE=0, PM_PAD_SKIP=0, PM_UNEMBED_DW=0, PM_SENC_FIRST=0: see
 //                       the fields of StepCfg
 //   PM_GCL_OFFSET_LIMIT=n, PM_DEBUG
-// Former switches that are constants now (their losing side was measured and removed: profiles/LOG.md): PM_NO_ROWS_TN,
-// PM_NO_UNEMBED_DH, PM_GCL_NO_BFRAG, PM_DENSE_DEG (16), PM_LATE_WGRADS, PM_DW_SIDE, PM_FUSED_HEADS (csrc/heads.hip, deleted in
-// round 6) — setting them has no effect.
+// Former switches (PM_NO_ROWS_TN, PM_NO_UNEMBED_DH, PM_GCL_NO_BFRAG, PM_DENSE_DEG, PM_LATE_WGRADS, PM_DW_SIDE, PM_FUSED_HEADS): their
+// losing side was measured and removed with the code it needed (profiles/LOG.md) — setting them has no effect.
 struct StepCfg {
-  bool gcl_fused, no_dw, no_rows_w, no_rows_tn, no_unembed_dh, no_classes, no_bfrag, fused_ce, debug;
+  bool gcl_fused, no_dw, no_rows_w, no_classes, fused_ce, debug;
   int side_stream;             // PM_SIDE_STREAM: bit per branch site (BR_*), default all
   int side_delay_us;           // PM_SIDE_DELAY_US (tests): every branch starts with a kernel that spins this long on the second stream,
                                // so a missing join shows as a wrong result instead of passing by luck of timing
-  bool dw_side;                // PM_DW_SIDE=1: the GCL weight gradients on the second stream
   bool dagg_bn;                // PM_DAGG_BN=0: the norm backward of a GCN layer as its own pass (pm_bn_bwd_fused) instead of inside the
                                // input gradient's prologue (pm_gcl_input_grad_bn; d in {128, 256})
   bool dagg_res;               // PM_DAGG_RES=1: the residual gradient rides in dA's self block (PmBnBwd.add_residual) instead of being a row
@@ -60,11 +58,8 @@ struct StepCfg {
   bool chord_tables;           // PM_CHORD_TABLES=0: the chord encoder through X [N, S, d] (gather, long-K product, weight-gradient product, token
                                // sums of dX) instead of as table algebra (chord.hip)
   bool plan_side;              // PM_PLAN_SIDE=0: the plan build on the caller's stream in front of the content encoder (see forward())
-  int late_wgrads_at;          // PM_LATE_WGRADS=2 (development A/B): forked behind the decoder's half of the head chain instead of in front of it
-  bool late_wgrads;            // PM_LATE_WGRADS=0: the decoder's weight gradients beside its GCL layers (round 3) instead of beside the head chain
   bool h2;                     // PM_H2=0: the GCL products of d in {128, 256} on the exact three-term bf16 split (six MFMA products per fp32
                                // product) instead of the fp16 pair format (three; PmH2 of the header) — the parity tests run both
-  int dense_deg;
   bool senc_first;             // PM_SENC_FIRST=0: the decoder's weight preparation ahead of the structure encoder on the second stream (rounds 3-5)
   bool unembed_dw;             // PM_UNEMBED_DW=0: the un-embedding weight gradients as three split-K products of the fp32 tile GEMM (rounds 2-5)
   bool pad_skip;               // PM_PAD_SKIP=0: the decoder head over every (node, active slot) row, PAD targets included (rounds 2-5)
@@ -77,23 +72,16 @@ static StepCfg read_cfg() {
   k.gcl_fused = flag("PM_GCL_FUSED", true);
   k.no_dw = flag("PM_GCL_NO_DW", false);
   k.no_rows_w = flag("PM_NO_ROWS_W", false);
-  k.no_rows_tn = false;
-  k.no_unembed_dh = false;
   k.no_classes = getenv("PM_GCL_NO_CLASSES") != nullptr;
-  k.no_bfrag = false;
   k.fused_ce = flag("PM_FUSED_CE", true);
   k.debug = getenv("PM_DEBUG") != nullptr;
   k.side_stream = getenv("PM_SIDE_STREAM") ? atoi(getenv("PM_SIDE_STREAM")) : 0xffff;
-  k.late_wgrads = true;
-  k.late_wgrads_at = 1;
-  k.dw_side = false;
   k.dagg_bn = flag("PM_DAGG_BN", true);
   k.plan_side = flag("PM_PLAN_SIDE", true);
   k.chord_tables = flag("PM_CHORD_TABLES", true);
   k.dagg_res = flag("PM_DAGG_RES", true);
   k.h2 = flag("PM_H2", true);
   k.side_delay_us = getenv("PM_SIDE_DELAY_US") ? atoi(getenv("PM_SIDE_DELAY_US")) : 0;
-  k.dense_deg = 16;
   k.bar_route = flag("PM_BAR_ROUTE", true);
   k.pad_skip = flag("PM_PAD_SKIP", true);
   k.unembed_dw = flag("PM_UNEMBED_DW", true);
@@ -132,7 +120,39 @@ struct Arena {
   double* zdbl(size_t n) { return (double*)z(n * sizeof(double)); }
 };
 
+// Which kernels ONE GCN stack takes in this step: every host decision of gcn_prepare / gcn_forward / gcn_backward, made once per
+// stack and step by gcn_route() (behind the carve-outs of gcn_prepare) and only read afterwards.  It never feeds a carve-out: the
+// measuring pass has no fragment planes, so its record differs from the real pass's, and the arena must not.
+constexpr int kDenseDeg = 16;            // mean in-degree from which a graph is "dense" (the fused forward's producers keep three
+                                         // edges per (node, relation) in flight and redo longer lists serially)
+struct GcnRoute {
+  // forward, L x { aggregate; multiply; norm }: the aggregate inside the product kernel (gcl.hip / wide.hip) | bar resident in LDS
+  // (bar.hip), to planes | segment-reduce (segreduce.hip) to planes | ... to fp32 rows (compact [N, 4d] or 7-block [N, 7d])
+  enum Agg { AGG_IN_PRODUCT, AGG_BAR, AGG_SEG_PLANES, AGG_SEG_F32 } agg;
+  // the aggregate's kernel multiplies | gcl.hip / wide.hip product from the aggregate's planes (dense graphs, d = 512) | grouped
+  // product over the four track relations (planes or fp32 operands) | one [N, 7d] x [7d, d] product
+  enum Mul { MUL_FUSED, MUL_FROM_PLANES, MUL_GROUPED, MUL_SEVEN } mul;
+  bool h2;                               // the stack's three GCL products in the fp16 pair format (PmH2; the _h2 form of each kernel)
+  bool x_tracked;                        // ... and the norm apply of layer i leaves |x|max for layer i+1's operand scale
+  bool plain_w_planes;                   // gcn_prepare splits the weights into row-major planes (operand of the grouped products)
+  // backward, L x { norm backward; input gradient; weight gradient; aggregation }: the norm backward inside the input gradient's
+  // prologue (k_gcl_dagg<.., true>; its sums by a pass of their own at the top layer) | pm_bn_bwd_fused (pair format: it writes the
+  // two dh planes) | batch_norm = False: relu backward + column sums
+  enum Norm { NORM_IN_DAGG, NORM_PASS, NORM_NONE } norm;
+  bool res_in_dagg;                      // ... and the residual gradient rides out in dA's self block (PmBnBwd.add_residual)
+  // pm_gcl_input_grad_bn (NORM_IN_DAGG) | A-stationary kernel (gcl.hip) / ring pipeline (wide.hip) | grouped product | 7-block product
+  enum Dagg { DAGG_BN, DAGG_TILES, DAGG_GROUPED, DAGG_SEVEN } dagg;
+  enum Dw { DW_TILES, DW_GROUPED, DW_SEVEN } dw;         // 128x128 tiles (gcl.hip) | grouped product | 7-block product
+  // cfg.dropout: segment-reduce, mask, add the residual gradient | bar.hip | segreduce.hip
+  enum Bagg { BAGG_SEG_DROPPED, BAGG_BAR, BAGG_SEG } bagg;
+  bool bagg_sums;                        // the aggregation of layer i also accumulates the norm backward's column sums of layer i-1
+  bool bagg_absmax;                      // ... and (pair format) leaves |dx|max of layer i-1 behind (PmNormSums.absmax_out)
+  bool frag;                             // fragment-major weight planes exist (B-direct GEMM mode)
+  int classes;                           // 1: skip all-zero onset / next blocks (PM_GCL_NO_CLASSES clears it)
+};
+
 struct GcnSaved {
+  GcnRoute rt;                           // filled by gcn_prepare
   float* T; float* x[PM_MAX_LAYERS + 1]; float* A[PM_MAX_LAYERS]; float* h[PM_MAX_LAYERS];
   const float* xin[PM_MAX_LAYERS];       // layer inputs after the cfg.dropout layer (model.py:199; = x[i] without dropout)
   uint32_t site0;                        // element-dropout stream id of layer 0
@@ -144,11 +164,11 @@ struct GcnSaved {
   uint16_t* Wfn; uint16_t* Wft; int64_t wf_stride;
   double* pool;                          // per layer PM_BN_REPL x ([2][d] forward column sums, [3][d] backward sums), fp64
   uint32_t seed, uid0; float p;
-  // fp16 pair format of the stack's three GCL products (PmH2): on / off, and its device words (zero region):
+  // fp16 pair format of the stack's three GCL products (PmH2, rt.h2): its device words (zero region):
   // mx[i * PM_ABSMAX_SLOTS ..] = |max| of layer i's input as float bits (i = 0 .. L-1), slot group L = of the distance table;
   // mdu[i * PM_ABSMAX_SLOTS ..] = of the gradient arriving at layer i's norm; sA[i] / sdh[i] = the scales the layer's A' / dh
   // planes were written with
-  bool h2; uint32_t* mx; uint32_t* mdu; float* sA; float* sdh;
+  uint32_t* mx; uint32_t* mdu; float* sA; float* sdh;
   bool x0_maxed;                           // the producer of the stack's input left its |max| in mx[0] already (pm_chord_sum_fwd_absmax)
   const float* x0_src; int64_t x0_src_n;   // optional: a smaller tensor with the same |max| as the stack's input (its rows are copies)
 };
@@ -220,7 +240,7 @@ struct Ctx {
 // capturable.  Norms on the branch use their own reduction scratch.
 // sites: structure encoder forward (+ weight preparation, its intermediate join BR_WPREP), structure decoder forward,
 // structure decoder backward, structure encoder backward, the weight gradients of the decoder head / of the chord encoder
-enum { BR_ENC_FWD = 0, BR_DEC_FWD, BR_DEC_BWD, BR_ENC_BWD, BR_WPREP, BR_DEC_WGRAD, BR_ENC_WGRAD, BR_WPREP_DEC, BR_ENC_HEAD_WGRAD, BR_GCL_DW0, BR_GCL_DW1, BR_PLAN_COUNT, BR_LOSSES, BR_ENC_S_FWD, BR_SITES };
+enum { BR_ENC_FWD = 0, BR_DEC_FWD, BR_DEC_BWD, BR_ENC_BWD, BR_WPREP, BR_DEC_WGRAD, BR_ENC_WGRAD, BR_WPREP_DEC, BR_ENC_HEAD_WGRAD, BR_PLAN_COUNT, BR_LOSSES, BR_ENC_S_FWD, BR_SITES };
 struct Branch { hipStream_t st; hipEvent_t fork[BR_SITES], join[BR_SITES], idle; bool ok; };
 static Branch* branch_of_device() {
   static Branch br[16];
@@ -255,7 +275,7 @@ struct BranchScope {
   BranchScope(Ctx& c_, int site_) : c(c_), main(c_.st), scratch_main(c_.bn_scratch), b(nullptr), site(site_) {
     // (deterministic mode: one stream — two gated kernels on two streams could each fill an XCD with waves waiting for a turn
     //  that belongs to a workgroup the other has not let in)
-    if (!c.s->ar.base || site_ >= BR_SITES || !(cfg().side_stream & (1 << site_)) || pm_det_on()) return;
+    if (!c.s->ar.base || !(cfg().side_stream & (1 << site_)) || pm_det_on()) return;
     b = branch_of_device();
     if (!b) return;
     if (hipEventRecord(b->fork[site], main) != hipSuccess || hipStreamWaitEvent(b->st, b->fork[site], 0) != hipSuccess) {
@@ -328,7 +348,7 @@ void lin_bwd(Ctx& c, const float* dy, const float* x, PmLin l, int M, int Nout, 
   w.transA = 1; w.M = Nout; w.N = Kin; w.K = M; w.A = dy; w.lda = lddy; w.B = x; w.ldb = ldx ? ldx : Kin;
   w.C = c.G + l.w; w.ldc = Kin; w.flags = PM_GEMM_ACCUM; w.split_k = 0; w.n_groups = 1;
   w.a_colsum = want_bias ? c.G + l.b : nullptr;
-  if (defer && defer->n < 8 && cfg().late_wgrads) defer->q[defer->n++] = w;
+  if (defer && defer->n < 8) defer->q[defer->n++] = w;
   else RUN(pm_gemm_f32_desc(&w, c.st));
   if (dx) RUN(pm_gemm_f32(0, 0, M, Kin, Nout, dy, lddy, c.P + l.w, Kin, dx, lddx ? lddx : Kin, nullptr,
                             c.s->ar.zeroed(dx) ? PM_GEMM_ZEROED : 0, 1, nullptr, 0, nullptr, c.st));
@@ -366,14 +386,10 @@ const float* drop(Ctx& c, const float* x, int64_t rows, int cols, uint32_t site,
   RUN(pm_dropout_rows(x, rows, cols, c.pdrop, seed, site, y, c.st));
   return y;
 }
-static bool gcl_fused_on() { return cfg().gcl_fused; }
 // chord weight gradients on the bf16 pipe (k_rows_tn of linear.hip: the loaders split fp32 rows on the fly): measured
 // 400 against 449 us per launch at d = 512, but 140 against 117 us at d = 256 — there the loaders' split arithmetic (5.5
 // vector instructions per element, on the SIMDs the MFMA waves run on) costs more than the fp32 matrix pipe loses
-static bool rows_tn_pays(int d) {
-  constexpr int min_d = 512;   // (development A/B)
-  return !cfg().no_rows_tn && d >= min_d && d % 128 == 0;
-}
+static bool rows_tn_pays(int d) { return d >= 512 && d % 128 == 0; }
 // widths the kernels of gcl.hip / linear.hip (128, 256) and wide.hip (512) cover
 static bool gcl_width(int d) { return d == 128 || d == 256 || d == 512; }
 // the kernels of gcl.hip / linear.hip address their operands with 32-bit byte offsets: batches beyond these sizes
@@ -384,11 +400,11 @@ static bool gcl_fits(int N, int d, int S) {
 }
 // descriptor skeleton of the compact GCL contractions: four track-relation groups, rows of group t listed in
 // plan.trk_list[t*N ..], live count plan.trk_cnt[t]
-PmGemmDesc gcl_desc(const PmPlanView& pv, int N, int d) {
+PmGemmDesc gcl_desc(const PmPlanView& pv, int N, int d, int classes) {
   PmGemmDesc q;
   memset(&q, 0, sizeof(q));
   q.flags = PM_GEMM_PARTITION; q.split_k = 1; q.rowmap = pv.trk_list; q.rows_per_entry = 1; q.dyn_entries = pv.trk_cnt;
-  if (!cfg().no_classes) { q.class_ptr = pv.trk_cnt + 8; q.class_block = d; }   // skip all-zero onset / next blocks
+  if (classes) { q.class_ptr = pv.trk_cnt + 8; q.class_block = d; }   // skip all-zero onset / next blocks
   q.n_groups = 4; q.map_group_stride = N; q.dyn_group_stride = 1;
   return q;
 }
@@ -398,34 +414,54 @@ PmGemmDesc gcl_desc(const PmPlanView& pv, int N, int d) {
 //   h[rows_t] = A[rows_t, 0:4d] @ [W_t; W_4; W_5; root] + b   (t = 0..3)
 // one grouped launch over the four track relations whose B operand is "stacked" (group rows + shared rows),
 // i.e. 8 N d^2 flops instead of 14 N d^2 (the other three track blocks of every row are identically zero).
-// which kernel set a GCN stack of this batch takes (host-known: shapes and switches)
-struct GcnRoute { bool gcl_kernels, dense, bar; };
+// The record of a stack (GcnRoute) from what the host knows: shapes, model switches, step switches, the mode, and whether
+// gcn_prepare built the fragment-major weight copies.  THE place where a stack's kernels are chosen.
 GcnRoute gcn_route(const Ctx& c, const GcnSaved& sv) {
+  const StepCfg& k = cfg();
+  const int d = c.d;
+  const bool dropping = c.pdrop > 0.f;
   GcnRoute r;
-  // the kernels of gcl.hip take the fragment-major weight copies (forward, input gradient) or no weight at all (weight gradient)
-  r.gcl_kernels = c.planes && c.compact && sv.Wfn && gcl_width(c.d) && gcl_fused_on() && gcl_fits(c.N, c.d, 1);
-  // dense graphs (mean in-degree >= cfg().dense_deg; the fused kernel's producers keep three edges per (node, relation)
-  // in flight and redo longer lists serially): stand-alone segment-reduce, then — at d = 512 — the product from its planes
-  r.dense = (int64_t)c.E >= (int64_t)cfg().dense_deg * c.N;
+  r.frag = sv.Wfn && sv.Wft;                             // (carved together: both or neither)
+  r.classes = k.no_classes ? 0 : 1;
+  // the tile kernels of gcl.hip / wide.hip read bf16 planes with 32-bit byte offsets.  The weight gradient takes no weight, so it
+  // needs no more than that (and a width); forward and input gradient take the fragment-major weight copies
+  const bool tiles = c.planes && c.compact && k.gcl_fused && gcl_fits(c.N, d, 1);
+  const bool gcl_kernels = tiles && r.frag && gcl_width(d);
+  // dense graphs: stand-alone aggregation, then — at d = 512 — the product from its planes ...
+  const bool dense = (int64_t)c.E >= (int64_t)kDenseDeg * c.N;
   // ... with the bar resident in LDS (bar.hip; round 6) instead of row gathers from L2 (segreduce.hip).  Deterministic mode keeps
   // the segment-reduce kernels (their one-wave-per-workgroup form orders the LDS table adds)
-  r.bar = r.dense && c.compact && c.planes && (c.d % 128) == 0 && cfg().bar_route && !pm_det_on();
-  return r;
-}
-// The stack's three GCL products in the fp16 pair format (gcl.hip H2 kernels): the fused forward, the input gradient with the
-// norm backward inside and the tile weight gradient all have to apply (they hand each other planes), d in {128, 256}
-static bool stack_h2(const Ctx& c, const GcnSaved& sv) {
-  const GcnRoute r = gcn_route(c, sv);
+  const bool bar = dense && c.compact && c.planes && (d % 128) == 0 && k.bar_route && !pm_det_on();
+  const bool fused = gcl_kernels && !dense;              // one kernel for aggregate + product
+  const bool from_planes = gcl_kernels && dense && d == 512;
+  r.agg = fused ? GcnRoute::AGG_IN_PRODUCT : bar ? GcnRoute::AGG_BAR : c.planes ? GcnRoute::AGG_SEG_PLANES : GcnRoute::AGG_SEG_F32;
+  r.mul = fused ? GcnRoute::MUL_FUSED : from_planes ? GcnRoute::MUL_FROM_PLANES : c.compact ? GcnRoute::MUL_GROUPED : GcnRoute::MUL_SEVEN;
+  r.plain_w_planes = c.planes && r.mul == GcnRoute::MUL_GROUPED;      // (the grouped input gradient runs only where the grouped forward does)
+  // The pair format: the forward, the input gradient and the tile weight gradient all have to apply (they hand each other planes).
   // (d <= 256: the norm backward runs inside the input gradient, which then writes the dh planes; d = 512: the norm's own pass does)
   // (dense graphs: at d = 512 the bar-resident aggregation writes the pair format and the product reads it from the planes)
-  return cfg().h2 && r.gcl_kernels && (!r.dense || (r.bar && c.d == 512)) && c.bn &&
-         (((c.d == 128 || c.d == 256) && cfg().dagg_bn) || c.d == 512) && !cfg().dw_side && !cfg().no_dw;
+  r.h2 = k.h2 && gcl_kernels && (!dense || (bar && d == 512)) && c.bn && (((d == 128 || d == 256) && k.dagg_bn) || d == 512) && !k.no_dw;
+  r.x_tracked = r.h2 && !dropping;
+  const bool in_dagg = c.bn && tiles && r.frag && (d == 128 || d == 256) && k.dagg_bn;
+  r.norm = in_dagg ? GcnRoute::NORM_IN_DAGG : c.bn ? GcnRoute::NORM_PASS : GcnRoute::NORM_NONE;
+  r.res_in_dagg = in_dagg && !dropping && k.dagg_res;
+  r.dagg = !c.compact ? GcnRoute::DAGG_SEVEN : in_dagg ? GcnRoute::DAGG_BN : gcl_kernels ? GcnRoute::DAGG_TILES : GcnRoute::DAGG_GROUPED;
+  r.dw = !c.compact ? GcnRoute::DW_SEVEN : (tiles && gcl_width(d) && !k.no_dw) ? GcnRoute::DW_TILES : GcnRoute::DW_GROUPED;
+  r.bagg = dropping ? GcnRoute::BAGG_SEG_DROPPED : bar ? GcnRoute::BAGG_BAR : GcnRoute::BAGG_SEG;
+  // the segment-reduce backward of layer i also accumulates the column sums of the norm backward of layer i-1; beyond
+  // d = 512 that variant spills (16-wave workgroups: 128 VGPRs), so wider models take the separate column-sum pass
+  // (no norm: no sums; cfg.dropout: the layer's input gradient is masked before it meets the residual gradient, so the sums
+  //  cannot be taken from the segment-reduce's registers)
+  r.bagg_sums = d <= 512 && c.bn && !dropping;
+  // (pm_segreduce_bwd_norm's 512-wide variant has no register for |dx|max, the bar-resident kernel has)
+  r.bagg_absmax = r.h2 && (d <= 256 || bar);
+  return r;
 }
 // The part of a GCN stack's forward that depends on the parameters only: the distance table of the shared edge_nn and
 // the bf16 planes of the layers' weights.  Issued at the start of the step, on the second stream.
 void gcn_prepare(Ctx& c, const PmGcn& g, GcnSaved& sv) {
   Arena& ar = c.s->ar;
-  const int N = c.N, d = c.d;
+  const int d = c.d;
   const int64_t dd = (int64_t)d * d;
   sv.T = ar.f((size_t)PM_N_DIST * d);
   if (ar.base) RUN(pm_edge_table(c.P + g.nn_w, c.P + g.nn_b, d, sv.T, c.st));
@@ -436,7 +472,10 @@ void gcn_prepare(Ctx& c, const PmGcn& g, GcnSaved& sv) {
     sv.mx = w; sv.mdu = w ? w + (c.L + 1) * SL : nullptr; sv.sA = w ? (float*)(w + (2 * c.L + 1) * SL) : nullptr;
     sv.sdh = w ? sv.sA + c.L : nullptr;
   }
-  sv.h2 = false;
+  // (layer 0 is followed by the shared edge_nn parameters, so it is converted on its own; layers 1.. are equally
+  //  spaced and go in one batched launch per kind)
+  const int64_t lstride = c.L > 2 ? g.weight[2] - g.weight[1] : 7 * dd;
+  sv.Wfn = sv.Wft = nullptr; sv.wf_stride = 7 * dd * 3;
   if (c.planes) {                                         // the GCL weights of this stack, split once per step
     sv.wp_base = g.weight[0];
     sv.wp_stride = (g.weight[c.L - 1] + 7 * dd - g.weight[0] + 7) & ~(int64_t)7;
@@ -444,40 +483,28 @@ void gcn_prepare(Ctx& c, const PmGcn& g, GcnSaved& sv) {
       if (g.weight[i] < sv.wp_base || ((g.weight[i] - sv.wp_base) & 7)) RUN(PM_E_INVALID);
     sv.Wp = (uint16_t*)ar.take((size_t)sv.wp_stride * 6);
     // fragment-major copies for the B-direct mode (d a multiple of 32, the layers' matrices equally spaced)
-    sv.Wfn = sv.Wft = nullptr; sv.wf_stride = 7 * dd * 3;
-    // (layer 0 is followed by the shared edge_nn parameters, so it is converted on its own; layers 1.. are equally
-    //  spaced and go in one batched launch per kind)
-    const int64_t lstride = c.L > 2 ? g.weight[2] - g.weight[1] : 7 * dd;
-    bool even = (d % 32) == 0 && c.compact && (lstride % 4) == 0 && !cfg().no_bfrag;
+    bool even = (d % 32) == 0 && c.compact && (lstride % 4) == 0;
     for (int i = 2; i < c.L; ++i) even = even && (g.weight[i] - g.weight[i - 1] == lstride);
     if (even) {
       sv.Wfn = (uint16_t*)ar.take((size_t)sv.wf_stride * 2 * c.L);
       sv.Wft = (uint16_t*)ar.take((size_t)sv.wf_stride * 2 * c.L);
-      sv.h2 = stack_h2(c, sv);
-      if (ar.base) {
-        for (int kind = 0; kind < 2; ++kind) {
-          uint16_t* dst = kind ? sv.Wfn : sv.Wft;
-          if (sv.h2) {
-            RUN(pm_split_planes_frag_h2(c.P + g.weight[0], 7 * d, d, kind, 1, 7 * dd, sv.wf_stride, kH2WScale, dst, c.st));
-            if (c.L > 1)
-              RUN(pm_split_planes_frag_h2(c.P + g.weight[1], 7 * d, d, kind, c.L - 1, lstride, sv.wf_stride, kH2WScale,
-                                            dst + sv.wf_stride, c.st));
-            continue;
-          }
-          RUN(pm_split_planes_frag(c.P + g.weight[0], 7 * d, d, kind, 1, 7 * dd, sv.wf_stride, dst, c.st));
-          if (c.L > 1)
-            RUN(pm_split_planes_frag(c.P + g.weight[1], 7 * d, d, kind, c.L - 1, lstride, sv.wf_stride,
-                                       dst + sv.wf_stride, c.st));
-        }
-        if (sv.h2) RUN(pm_absmax(sv.T, (int64_t)PM_N_DIST * d, sv.mx + c.L * PM_ABSMAX_SLOTS, c.st));
-      }
     }
   }
-  // plain (row-major) planes of the weights: operand of the grouped planes products only
-  const GcnRoute r = gcn_route(c, sv);
-  if (c.planes && (!r.gcl_kernels || (r.dense && d != 512)) && ar.base)
+  const GcnRoute& r = sv.rt = gcn_route(c, sv);           // behind the last carve-out of this function: nothing carved depends on it
+  if (r.frag) {
+    auto split = [&](const float* W, int n_mats, int64_t src_stride, int kind, uint16_t* dst) {
+      if (r.h2) RUN(pm_split_planes_frag_h2(W, 7 * d, d, kind, n_mats, src_stride, sv.wf_stride, kH2WScale, dst, c.st));
+      else RUN(pm_split_planes_frag(W, 7 * d, d, kind, n_mats, src_stride, sv.wf_stride, dst, c.st));
+    };
+    for (int kind = 0; kind < 2; ++kind) {
+      uint16_t* dst = kind ? sv.Wfn : sv.Wft;
+      split(c.P + g.weight[0], 1, 7 * dd, kind, dst);
+      if (c.L > 1) split(c.P + g.weight[1], c.L - 1, lstride, kind, dst + sv.wf_stride);
+    }
+    if (r.h2) RUN(pm_absmax(sv.T, (int64_t)PM_N_DIST * d, sv.mx + c.L * PM_ABSMAX_SLOTS, c.st));
+  }
+  if (r.plain_w_planes)                                   // plain (row-major) planes of the weights
     RUN(pm_split_planes(c.P + sv.wp_base, sv.wp_stride & ~(int64_t)3, sv.Wp, sv.wp_stride, c.st));
-  (void)N;
 }
 
 float* gcn_forward(Ctx& c, float* x0, const PmGcn& g, GcnSaved& sv, uint32_t seed, uint32_t uid0, float p) {
@@ -489,81 +516,86 @@ float* gcn_forward(Ctx& c, float* x0, const PmGcn& g, GcnSaved& sv, uint32_t see
   if (ar.base) pv = pm_plan_view(c.s->plan, N, c.E, c.Gn);
   sv.x[0] = x0;
   const int64_t aps = (int64_t)N * nb * d;                // plane stride of the aggregates (elements)
-  const GcnRoute r = gcn_route(c, sv);
-  const bool gcl_kernels = r.gcl_kernels, dense = r.dense;
+  const GcnRoute& r = sv.rt;
+  const bool dropping = c.pdrop > 0.f;
   sv.site0 = uid0 == 0 ? SITE_ENC_GCN : SITE_DEC_GCN;
   for (int i = 0; i < c.L; ++i) {
     if (c.planes) { sv.Ap[i] = (uint16_t*)ar.take((size_t)aps * 6); sv.A[i] = nullptr; }
     else sv.A[i] = ar.f((size_t)N * nb * d);
     sv.h[i] = ar.f((size_t)N * d); sv.x[i + 1] = ar.f((size_t)N * d);
     sv.mean[i] = ar.f(d); sv.var[i] = ar.f(d);
-    float* xdrop = c.pdrop > 0.f ? ar.f((size_t)N * d) : nullptr;
+    float* xdrop = dropping ? ar.f((size_t)N * d) : nullptr;
     if (!ar.base) continue;
     sv.xin[i] = drop(c, sv.x[i], N, d, sv.site0 + i, seed, xdrop);      // model.py:199 (the residual keeps the undropped x)
     const float* W = c.P + g.weight[i];
+    const float* bias = c.P + g.bias[i];
+    const uint16_t* Wf = r.frag ? sv.Wfn + (int64_t)i * sv.wf_stride : nullptr;
     double* sums = c.bn ? sv.pool + (size_t)i * 5 * d * PM_BN_REPL : nullptr;   // the GEMM epilogue leaves the BatchNorm statistics here
-    // one kernel for aggregate + product (gcl.hip) where it applies: compact planes path, fragment-major weights
-    const bool fused = gcl_kernels && !dense;
-    const bool from_planes = gcl_kernels && dense && d == 512;
-    const bool x_tracked = sv.h2 && i > 0 && !(c.pdrop > 0.f);   // (the norm apply of layer i-1 left |x|max in mx[i])
-    if ((fused || from_planes) && sv.h2) {
-      if (!x_tracked) {
+    PmH2 h2;
+    if (r.h2) {                                           // |x|max of the layer's input, the scale its A' planes are written with
+      if (!(r.x_tracked && i > 0)) {                      // (else: the norm apply of layer i-1 left |x|max in mx[i])
         // (the decoder's first input is the bar vectors broadcast to their nodes: the [G, d] source has the same |max|)
-        if (i == 0 && sv.x0_maxed && !(c.pdrop > 0.f)) {}
-        else if (i == 0 && sv.x0_src && !(c.pdrop > 0.f)) RUN(pm_absmax(sv.x0_src, sv.x0_src_n, sv.mx, c.st));
+        if (i == 0 && sv.x0_maxed && !dropping) {}
+        else if (i == 0 && sv.x0_src && !dropping) RUN(pm_absmax(sv.x0_src, sv.x0_src_n, sv.mx, c.st));
         else RUN(pm_absmax(sv.xin[i], (int64_t)N * d, sv.mx + i * PM_ABSMAX_SLOTS, c.st));
       }
-      PmH2 h2;
       h2.absmax_in = sv.mx + i * PM_ABSMAX_SLOTS; h2.absmax_aux = sv.mx + c.L * PM_ABSMAX_SLOTS; h2.scale_out = sv.sA + i;
       h2.w_scale = kH2WScale; h2.reserved = 0;
-      if (from_planes)                                     // dense graphs: bar-resident aggregation, then the product from its planes
-        RUN(pm_bar_aggregate_fwd(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, sv.Ap[i], aps, &h2, c.st));
-      else
-      RUN(pm_gcl_forward_fused_h2(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i,
-                                    sv.Wfn + (int64_t)i * sv.wf_stride, c.P + g.bias[i], cfg().no_classes ? 0 : 1,
-                                    sv.h[i], sums, sv.Ap[i], aps, &h2, c.st));
-    } else if (fused)
-      RUN(pm_gcl_forward_fused(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i,
-                                 sv.Wfn + (int64_t)i * sv.wf_stride, c.P + g.bias[i], cfg().no_classes ? 0 : 1,
-                                 sv.h[i], sums, sv.Ap[i], aps, c.st));
-    else if (r.bar)
-      RUN(pm_bar_aggregate_fwd(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, sv.Ap[i], aps, nullptr, c.st));
-    else if (c.planes)
-      RUN(pm_segreduce_fwd_planes(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, 1, sv.Ap[i], aps, c.st));
-    else
-      RUN(pm_segreduce_fwd(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, c.compact, sv.A[i], c.st));
-    if (fused) {
-    } else if (from_planes && sv.h2) {
-      RUN(pm_gcl_forward_from_planes_h2(sv.Ap[i], aps, c.s->plan, N, c.E, c.Gn, d, sv.Wfn + (int64_t)i * sv.wf_stride,
-                                          c.P + g.bias[i], cfg().no_classes ? 0 : 1, sv.h[i], sums, sv.sA + i, kH2WScale, c.st));
-    } else if (from_planes) {
-      RUN(pm_gcl_forward_from_planes(sv.Ap[i], aps, c.s->plan, N, c.E, c.Gn, d, sv.Wfn + (int64_t)i * sv.wf_stride,
-                                       c.P + g.bias[i], cfg().no_classes ? 0 : 1, sv.h[i], sums, c.st));
-    } else if (!c.compact) {
-      PmGemmDesc q;
-      memset(&q, 0, sizeof(q));
-      q.M = N; q.N = d; q.K = 7 * d; q.split_k = 1; q.n_groups = 1;
-      q.A = sv.A[i]; q.lda = 7 * d; q.B = W; q.ldb = d; q.C = sv.h[i]; q.ldc = d; q.bias = c.P + g.bias[i];
-      q.col_stats = sums;
-      RUN(pm_gemm_f32_desc(&q, c.st));
-    } else {
-      PmGemmDesc q = gcl_desc(pv, N, d);                  // h[rows_t] = A'[rows_t] @ [W_t; W_4; W_5; root] + b
-      q.M = N; q.N = d; q.K = 4 * d;
-      q.A = sv.A[i]; q.lda = 4 * d; q.B = W; q.ldb = d; q.C = sv.h[i]; q.ldc = d; q.bias = c.P + g.bias[i];
-      q.b_group_stride = dd; q.b_split_rows = d; q.b_shared_off = 3 * dd;
-      q.col_stats = sums;
-      if (c.planes) {
-        q.operand_planes = 1; q.A = (const float*)sv.Ap[i]; q.a_plane_stride = aps;
-        q.B = (const float*)(sv.Wp + (g.weight[i] - sv.wp_base)); q.b_plane_stride = sv.wp_stride;
-        if (sv.Wfn) q.b_frag = sv.Wfn + (int64_t)i * sv.wf_stride;
+    }
+    switch (r.agg) {
+      case GcnRoute::AGG_IN_PRODUCT:
+        if (r.h2)
+          RUN(pm_gcl_forward_fused_h2(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, Wf, bias, r.classes,
+                                        sv.h[i], sums, sv.Ap[i], aps, &h2, c.st));
+        else
+          RUN(pm_gcl_forward_fused(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, Wf, bias, r.classes,
+                                     sv.h[i], sums, sv.Ap[i], aps, c.st));
+        break;
+      case GcnRoute::AGG_BAR:
+        RUN(pm_bar_aggregate_fwd(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, sv.Ap[i], aps, r.h2 ? &h2 : nullptr, c.st)); break;
+      case GcnRoute::AGG_SEG_PLANES:
+        RUN(pm_segreduce_fwd_planes(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, 1, sv.Ap[i], aps, c.st)); break;
+      case GcnRoute::AGG_SEG_F32:
+        RUN(pm_segreduce_fwd(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, c.compact, sv.A[i], c.st)); break;
+    }
+    switch (r.mul) {
+      case GcnRoute::MUL_FUSED: break;
+      case GcnRoute::MUL_FROM_PLANES:
+        if (r.h2)
+          RUN(pm_gcl_forward_from_planes_h2(sv.Ap[i], aps, c.s->plan, N, c.E, c.Gn, d, Wf, bias, r.classes, sv.h[i], sums,
+                                              sv.sA + i, kH2WScale, c.st));
+        else
+          RUN(pm_gcl_forward_from_planes(sv.Ap[i], aps, c.s->plan, N, c.E, c.Gn, d, Wf, bias, r.classes, sv.h[i], sums, c.st));
+        break;
+      case GcnRoute::MUL_SEVEN: {
+        PmGemmDesc q;
+        memset(&q, 0, sizeof(q));
+        q.M = N; q.N = d; q.K = 7 * d; q.split_k = 1; q.n_groups = 1;
+        q.A = sv.A[i]; q.lda = 7 * d; q.B = W; q.ldb = d; q.C = sv.h[i]; q.ldc = d; q.bias = bias;
+        q.col_stats = sums;
+        RUN(pm_gemm_f32_desc(&q, c.st));
+        break;
       }
-      RUN(pm_gemm_f32_desc(&q, c.st));
+      case GcnRoute::MUL_GROUPED: {
+        PmGemmDesc q = gcl_desc(pv, N, d, r.classes);       // h[rows_t] = A'[rows_t] @ [W_t; W_4; W_5; root] + b
+        q.M = N; q.N = d; q.K = 4 * d;
+        q.A = sv.A[i]; q.lda = 4 * d; q.B = W; q.ldb = d; q.C = sv.h[i]; q.ldc = d; q.bias = bias;
+        q.b_group_stride = dd; q.b_split_rows = d; q.b_shared_off = 3 * dd;
+        q.col_stats = sums;
+        if (c.planes) {
+          q.operand_planes = 1; q.A = (const float*)sv.Ap[i]; q.a_plane_stride = aps;
+          q.B = (const float*)(sv.Wp + (g.weight[i] - sv.wp_base)); q.b_plane_stride = sv.wp_stride;
+          q.b_frag = Wf;
+        }
+        RUN(pm_gemm_f32_desc(&q, c.st));
+        break;
+      }
     }
     const PmBn& bn = g.norm[i];                           // x' = x + relu(BN(h))   (model.py:203-206)
     if (c.bn)
       RUN(pm_bn_apply_fused_absmax(sv.h[i], N, d, sums, 1e-5f, c.P + bn.w, c.P + bn.b, sv.x[i], 1, sv.x[i + 1], sv.mean[i],
                                      sv.var[i], c.Bf + bn.rm, c.Bf + bn.rv, 0.1f,
-                                     (sv.h2 && i + 1 < c.L && !(c.pdrop > 0.f)) ? sv.mx + (i + 1) * PM_ABSMAX_SLOTS : nullptr, c.st));
+                                     (r.x_tracked && i + 1 < c.L) ? sv.mx + (i + 1) * PM_ABSMAX_SLOTS : nullptr, c.st));
     else                                                  // batch_norm = False: x' = x + relu(h)
       RUN(pm_relu_residual_fwd(sv.h[i], sv.x[i], (int64_t)N * d, sv.x[i + 1], c.st));
   }
@@ -578,153 +610,133 @@ float* gcn_backward(Ctx& c, float* dx, const PmGcn& g, GcnSaved& sv) {
   float* dh = ar.f((size_t)N * d);
   float* dA = ar.f((size_t)N * nb * d);
   const int64_t aps = (int64_t)N * nb * d, dps = (int64_t)N * d;
-  // dh as operand planes; two buffers, alternating by layer, when the weight gradients run on the second stream (the
-  // weight gradient of layer i may then still read its planes while layer i-1's norm backward writes the other buffer)
-  uint16_t* dhp2[2];
-  dhp2[0] = c.planes ? (uint16_t*)ar.take((size_t)dps * 6) : nullptr;
-  const bool dws = cfg().dw_side && c.planes && c.compact;
-  dhp2[1] = dws ? (uint16_t*)ar.take((size_t)dps * 6) : dhp2[0];
+  uint16_t* const dhp = c.planes ? (uint16_t*)ar.take((size_t)dps * 6) : nullptr;      // dh as operand planes
   float* dxa = ar.f((size_t)N * d);
   float* dxb = ar.f((size_t)N * d);
   PmPlanView pv = pm_plan_view(c.s->plan, N, c.E, c.Gn);
-  // the segment-reduce backward of layer i also accumulates the column sums of the norm backward of layer i-1; beyond
-  // d = 512 that variant spills (16-wave workgroups: 128 VGPRs), so wider models take the separate column-sum pass
-  // (no norm: no sums; cfg.dropout: the layer's input gradient is masked before it meets the residual gradient, so the sums
-  //  cannot be taken from the segment-reduce's registers)
-  const bool dropping = c.pdrop > 0.f;
-  const bool fuse_sums = d <= 512 && c.bn && !dropping;
-  float* dxin = dropping ? ar.f((size_t)N * d) : nullptr;
+  float* dxin = c.pdrop > 0.f ? ar.f((size_t)N * d) : nullptr;
+  const GcnRoute& r = sv.rt;
   for (int i = c.L - 1; i >= 0; --i) {
     const float* W = c.P + g.weight[i];
     float* dW = c.G + g.weight[i];
     const PmBn& bn = g.norm[i];
-    uint16_t* const dhp = dhp2[i & 1];
-    const int dw_site = dws ? (BR_GCL_DW0 + (i & 1)) : BR_SITES;
-    if (dws) branch_join(c, dw_site);        // (the weight gradient of layer i+2 read the dh planes this call rewrites)
-    // the norm backward inside the input gradient (gcl.hip k_gcl_dagg<.., true>): no pass of its own over h, dx and the planes
-    const bool in_dagg = c.bn && c.compact && c.planes && sv.Wft && (d == 128 || d == 256) && gcl_fused_on() &&
-                         gcl_fits(N, d, 1) && cfg().dagg_bn && !dws;
-    // ... and the residual gradient rides out in dA's self block (PmBnBwd.add_residual): one row stream less in the segment-reduce
-    const bool res_in_dagg = in_dagg && !dropping && cfg().dagg_res;
+    const uint16_t* Wf = r.frag ? sv.Wft + (int64_t)i * sv.wf_stride : nullptr;
     double* const acc3 = sv.pool + ((size_t)i * 5 + 2) * d * PM_BN_REPL;
-    const bool sums_ready = i < c.L - 1 && fuse_sums;
-    const GcnRoute rt = gcn_route(c, sv);
-    const bool du_tracked = sums_ready && (d <= 256 || rt.bar);   // (h2: pm_segreduce_bwd_norm of layer i+1 also left |dx|max in mdu[i]; its 512-wide variant has no register for it, the bar-resident kernel has)
-    bool du_from_sums = false;                           // (the top layer of a stack: its |du|max rides in the norm's column sums)
-    if (in_dagg) {
-      if (!sums_ready) {
-        du_from_sums = sv.h2 && !du_tracked;
-        RUN(pm_bn_bwd_sums_absmax(sv.h[i], dx, N, d, sv.mean[i], sv.var[i], 1e-5f, c.P + bn.w, c.P + bn.b, 1, acc3,
-                                    du_from_sums ? sv.mdu + i * PM_ABSMAX_SLOTS : nullptr, c.st));
-      }
-    } else if (c.bn && sv.h2) {                          // d = 512 in the fp16 pair format: the norm's pass writes the two dh planes
-      if (!du_tracked) RUN(pm_absmax(dx, (int64_t)N * d, sv.mdu + i * PM_ABSMAX_SLOTS, c.st));
-      PmH2 h2;
-      h2.absmax_in = sv.mdu + i * PM_ABSMAX_SLOTS; h2.absmax_aux = nullptr; h2.scale_out = sv.sdh + i; h2.w_scale = kH2WScale; h2.reserved = 0;
-      RUN(pm_bn_bwd_fused_h2(sv.h[i], dx, N, d, sv.mean[i], sv.var[i], 1e-5f, c.P + bn.w, c.P + bn.b, 1, c.G + bn.w, c.G + bn.b,
-                               c.G + g.bias[i], sv.pool + ((size_t)i * 5 + 2) * d * PM_BN_REPL, dhp, dps,
-                               (i < c.L - 1 && fuse_sums) ? 1 : 0, &h2, c.st));
-    } else if (c.bn)
-      RUN(pm_bn_bwd_fused(sv.h[i], dx, N, d, sv.mean[i], sv.var[i], 1e-5f, c.P + bn.w, c.P + bn.b, 1, c.G + bn.w,
-                            c.G + bn.b, c.G + g.bias[i], c.planes ? nullptr : dh,
-                            sv.pool + ((size_t)i * 5 + 2) * d * PM_BN_REPL, dhp, dps, (i < c.L - 1 && fuse_sums) ? 1 : 0, c.st));
-    else {                                              // batch_norm = False: dh = dx * [h > 0]; GCL.bias gradient = its column sums
-      RUN(pm_relu_bwd_planes(dx, sv.h[i], (int64_t)N * d, dh, c.planes ? dhp : nullptr, dps, c.st));
-      RUN(pm_colsum_acc(dh, N, d, d, c.G + g.bias[i], c.st));
+    const bool sums_ready = i < c.L - 1 && r.bagg_sums;  // (the aggregation of layer i+1 accumulated this layer's column sums)
+    // pair format, |du|max of the gradient arriving at the layer's norm: the aggregation of layer i+1 left it in mdu[i] | (the top
+    // layer of a stack whose norm backward rides in the input gradient) it comes with the norm's column sums | else: pm_absmax
+    const bool du_tracked = sums_ready && r.bagg_absmax, du_from_sums = r.norm == GcnRoute::NORM_IN_DAGG && !sums_ready;
+    PmH2 h2 = {};                                        // (pair format: the scale the layer's dh planes are written with)
+    if (r.h2) { h2.absmax_in = sv.mdu + i * PM_ABSMAX_SLOTS; h2.scale_out = sv.sdh + i; h2.w_scale = kH2WScale; }
+    switch (r.norm) {
+      case GcnRoute::NORM_IN_DAGG:
+        if (!sums_ready)
+          RUN(pm_bn_bwd_sums_absmax(sv.h[i], dx, N, d, sv.mean[i], sv.var[i], 1e-5f, c.P + bn.w, c.P + bn.b, 1, acc3,
+                                      (r.h2 && du_from_sums) ? sv.mdu + i * PM_ABSMAX_SLOTS : nullptr, c.st));
+        break;
+      case GcnRoute::NORM_PASS:
+        if (r.h2) {                                      // d = 512 in the fp16 pair format: the norm's pass writes the two dh planes
+          if (!du_tracked) RUN(pm_absmax(dx, (int64_t)N * d, sv.mdu + i * PM_ABSMAX_SLOTS, c.st));
+          RUN(pm_bn_bwd_fused_h2(sv.h[i], dx, N, d, sv.mean[i], sv.var[i], 1e-5f, c.P + bn.w, c.P + bn.b, 1, c.G + bn.w, c.G + bn.b,
+                                   c.G + g.bias[i], acc3, dhp, dps, sums_ready ? 1 : 0, &h2, c.st));
+        } else
+          RUN(pm_bn_bwd_fused(sv.h[i], dx, N, d, sv.mean[i], sv.var[i], 1e-5f, c.P + bn.w, c.P + bn.b, 1, c.G + bn.w,
+                                c.G + bn.b, c.G + g.bias[i], c.planes ? nullptr : dh, acc3, dhp, dps, sums_ready ? 1 : 0, c.st));
+        break;
+      case GcnRoute::NORM_NONE:                          // batch_norm = False: dh = dx * [h > 0]; GCL.bias gradient = its column sums
+        RUN(pm_relu_bwd_planes(dx, sv.h[i], (int64_t)N * d, dh, c.planes ? dhp : nullptr, dps, c.st));
+        RUN(pm_colsum_acc(dh, N, d, d, c.G + g.bias[i], c.st));
+        break;
     }
-    if (!c.compact) {
-      RUN(pm_gemm_f32(0, 1, N, 7 * d, d, dh, d, W, d, dA, 7 * d, nullptr, 0, 1, nullptr, 0, nullptr, c.st));
-      RUN(pm_gemm_f32(1, 0, 7 * d, d, N, sv.A[i], 7 * d, dh, d, dW, d, nullptr, PM_GEMM_ACCUM, 0, nullptr, 0, nullptr, c.st));
-    } else {
-      const bool dw_first = dws;                // (second stream: issued before the input gradient, beside which it runs)
-      auto weight_grad = [&]() {
-      PmGemmDesc w = gcl_desc(pv, N, d);                  // d[W_t; W_4; W_5; root] += A'[rows_t]^T dh[rows_t]
-      w.transA = 1; w.M = 4 * d; w.N = d; w.K = N; w.flags = PM_GEMM_ACCUM | PM_GEMM_PARTITION; w.split_k = 0;
-      w.A = sv.A[i]; w.lda = 4 * d; w.B = dh; w.ldb = d; w.C = dW; w.ldc = d;
-      w.c_group_stride = dd; w.c_split_rows = d; w.c_shared_off = 3 * dd;
-      if (c.planes) {
-        w.operand_planes = 1; w.A = (const float*)sv.Ap[i]; w.a_plane_stride = aps;
-        w.B = (const float*)dhp; w.b_plane_stride = dps;
-      }
-      {
-        // PM_DW_SIDE=1 (A/B): the weight gradient of the layer on the second stream — nobody on the caller's stream waits
-        // for it; its workgroups fill the CUs that the input gradient's / the segment-reduce's unequal tiles leave idle
-        BranchScope brw(c, dw_site);
-        if (sv.h2)
-          RUN(pm_gcl_weight_grad_fused_h2(sv.Ap[i], aps, dhp, dps, c.s->plan, N, c.E, c.Gn, d, cfg().no_classes ? 0 : 1, dW,
-                                            sv.sA + i, sv.sdh + i, c.st));
-        else if (c.planes && gcl_width(d) && gcl_fused_on() && gcl_fits(N, d, 1) && !cfg().no_dw)      // 128x128 tiles (gcl.hip)
-          RUN(pm_gcl_weight_grad_fused(sv.Ap[i], aps, dhp, dps, c.s->plan, N, c.E, c.Gn, d,
-                                         cfg().no_classes ? 0 : 1, dW, c.st));
-        else
-          RUN(pm_gemm_f32_desc(&w, c.st));
-      }
-      };
-      if (dw_first) weight_grad();
-      PmGemmDesc q = gcl_desc(pv, N, d);                  // dA'[rows_t] = dh[rows_t] @ [W_t; W_4; W_5; root]^T
-      q.transB = 1; q.M = N; q.N = 4 * d; q.K = d;
-      q.A = dh; q.lda = d; q.B = W; q.ldb = d; q.C = dA; q.ldc = 4 * d;
-      q.b_group_stride = dd; q.b_split_rows = d; q.b_shared_off = 3 * dd;
-      if (c.planes) {
-        q.operand_planes = 1; q.A = (const float*)dhp; q.a_plane_stride = dps;
-        q.B = (const float*)(sv.Wp + (g.weight[i] - sv.wp_base)); q.b_plane_stride = sv.wp_stride;
-        if (sv.Wft) q.b_frag = sv.Wft + (int64_t)i * sv.wf_stride;
-      }
-      if (in_dagg) {
+    switch (r.dagg) {                                    // the input gradient ...
+      case GcnRoute::DAGG_SEVEN:
+        RUN(pm_gemm_f32(0, 1, N, 7 * d, d, dh, d, W, d, dA, 7 * d, nullptr, 0, 1, nullptr, 0, nullptr, c.st)); break;
+      case GcnRoute::DAGG_BN: {
         PmBnBwd nb;
         nb.h = sv.h[i]; nb.du = dx; nb.mean = sv.mean[i]; nb.var = sv.var[i]; nb.gamma = c.P + bn.w; nb.beta = c.P + bn.b;
         nb.acc3 = acc3; nb.dgamma = c.G + bn.w; nb.dbeta = c.G + bn.b; nb.dbias_pre = c.G + g.bias[i]; nb.eps = 1e-5f; nb.relu = 1;
-        nb.add_residual = res_in_dagg ? 1 : 0; nb.reserved = 0;
-        if (sv.h2) {
-          // |du|max: the segment-reduce backward of the layer above left it (PmNormSums.absmax_out); the top layer's comes from elsewhere
+        nb.add_residual = r.res_in_dagg ? 1 : 0; nb.reserved = 0;
+        if (r.h2) {
           if (!du_tracked && !du_from_sums) RUN(pm_absmax(dx, (int64_t)N * d, sv.mdu + i * PM_ABSMAX_SLOTS, c.st));
-          PmH2 h2;
-          h2.absmax_in = sv.mdu + i * PM_ABSMAX_SLOTS; h2.absmax_aux = nullptr; h2.scale_out = sv.sdh + i; h2.w_scale = kH2WScale; h2.reserved = 0;
-          RUN(pm_gcl_input_grad_bn_h2(&nb, dhp, dps, c.s->plan, N, c.E, c.Gn, d, sv.Wft + (int64_t)i * sv.wf_stride,
-                                        cfg().no_classes ? 0 : 1, dA, &h2, c.st));
+          RUN(pm_gcl_input_grad_bn_h2(&nb, dhp, dps, c.s->plan, N, c.E, c.Gn, d, Wf, r.classes, dA, &h2, c.st));
         } else
-        RUN(pm_gcl_input_grad_bn(&nb, dhp, dps, c.s->plan, N, c.E, c.Gn, d, sv.Wft + (int64_t)i * sv.wf_stride,
-                                   cfg().no_classes ? 0 : 1, dA, c.st));
-      } else if (sv.h2)                                   // (d = 512: ring pipeline of wide.hip on the pair-format planes)
-        RUN(pm_gcl_input_grad_fused_h2(dhp, dps, c.s->plan, N, c.E, c.Gn, d, sv.Wft + (int64_t)i * sv.wf_stride,
-                                         cfg().no_classes ? 0 : 1, dA, sv.sdh + i, kH2WScale, c.st));
-      else if (c.planes && sv.Wft && gcl_width(d) && gcl_fused_on() && gcl_fits(N, d, 1))      // A-stationary kernel (gcl.hip) / ring pipeline (wide.hip)
-        RUN(pm_gcl_input_grad_fused(dhp, dps, c.s->plan, N, c.E, c.Gn, d, sv.Wft + (int64_t)i * sv.wf_stride,
-                                      cfg().no_classes ? 0 : 1, dA, c.st));
-      else
+          RUN(pm_gcl_input_grad_bn(&nb, dhp, dps, c.s->plan, N, c.E, c.Gn, d, Wf, r.classes, dA, c.st));
+        break;
+      }
+      case GcnRoute::DAGG_TILES:
+        if (r.h2)                                        // (d = 512: ring pipeline of wide.hip on the pair-format planes)
+          RUN(pm_gcl_input_grad_fused_h2(dhp, dps, c.s->plan, N, c.E, c.Gn, d, Wf, r.classes, dA, sv.sdh + i, kH2WScale, c.st));
+        else
+          RUN(pm_gcl_input_grad_fused(dhp, dps, c.s->plan, N, c.E, c.Gn, d, Wf, r.classes, dA, c.st));
+        break;
+      case GcnRoute::DAGG_GROUPED: {
+        PmGemmDesc q = gcl_desc(pv, N, d, r.classes);       // dA'[rows_t] = dh[rows_t] @ [W_t; W_4; W_5; root]^T
+        q.transB = 1; q.M = N; q.N = 4 * d; q.K = d;
+        q.A = dh; q.lda = d; q.B = W; q.ldb = d; q.C = dA; q.ldc = 4 * d;
+        q.b_group_stride = dd; q.b_split_rows = d; q.b_shared_off = 3 * dd;
+        if (c.planes) {
+          q.operand_planes = 1; q.A = (const float*)dhp; q.a_plane_stride = dps;
+          q.B = (const float*)(sv.Wp + (g.weight[i] - sv.wp_base)); q.b_plane_stride = sv.wp_stride;
+          q.b_frag = Wf;
+        }
         RUN(pm_gemm_f32_desc(&q, c.st));
-      if (!dw_first) weight_grad();
+        break;
+      }
+    }
+    switch (r.dw) {                                      // ... and behind it the weight gradient
+      case GcnRoute::DW_SEVEN:
+        RUN(pm_gemm_f32(1, 0, 7 * d, d, N, sv.A[i], 7 * d, dh, d, dW, d, nullptr, PM_GEMM_ACCUM, 0, nullptr, 0, nullptr, c.st)); break;
+      case GcnRoute::DW_TILES:
+        if (r.h2)
+          RUN(pm_gcl_weight_grad_fused_h2(sv.Ap[i], aps, dhp, dps, c.s->plan, N, c.E, c.Gn, d, r.classes, dW, sv.sA + i, sv.sdh + i, c.st));
+        else
+          RUN(pm_gcl_weight_grad_fused(sv.Ap[i], aps, dhp, dps, c.s->plan, N, c.E, c.Gn, d, r.classes, dW, c.st));
+        break;
+      case GcnRoute::DW_GROUPED: {
+        PmGemmDesc w = gcl_desc(pv, N, d, r.classes);       // d[W_t; W_4; W_5; root] += A'[rows_t]^T dh[rows_t]
+        w.transA = 1; w.M = 4 * d; w.N = d; w.K = N; w.flags = PM_GEMM_ACCUM | PM_GEMM_PARTITION; w.split_k = 0;
+        w.A = sv.A[i]; w.lda = 4 * d; w.B = dh; w.ldb = d; w.C = dW; w.ldc = d;
+        w.c_group_stride = dd; w.c_split_rows = d; w.c_shared_off = 3 * dd;
+        if (c.planes) {
+          w.operand_planes = 1; w.A = (const float*)sv.Ap[i]; w.a_plane_stride = aps;
+          w.B = (const float*)dhp; w.b_plane_stride = dps;
+        }
+        RUN(pm_gemm_f32_desc(&w, c.st));
+        break;
+      }
     }
     float* out = (dx == dxa) ? dxb : dxa;
-    if (dropping) {
-      // dx_i = dx_{i+1} (residual) + dropout-mask * d(layer input): sv.xin is the DROPPED input the messages were built from
-      RUN(pm_segreduce_bwd(sv.xin[i], sv.T, dA, nullptr, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i, c.compact, dxin,
-                             dT, c.st));
-      drop(c, dxin, N, d, sv.site0 + i, sv.seed, dxin);
-      RUN(pm_add(dx, dxin, (int64_t)N * d, out, c.st));
-    } else if (i > 0 && fuse_sums) {                      // + the column sums of the norm backward of layer i-1
+    const float* res = r.res_in_dagg ? nullptr : dx;     // the residual gradient as a row stream of the aggregation (else: it rode in dA)
+    PmNormSums nn;                                       // + the column sums of the norm backward of layer i-1
+    const bool carry = i > 0 && r.bagg_sums;
+    if (carry) {
       const PmBn& pb = g.norm[i - 1];
-      PmNormSums nn;
       nn.h = sv.h[i - 1]; nn.mean = sv.mean[i - 1]; nn.var = sv.var[i - 1]; nn.gamma = c.P + pb.w; nn.beta = c.P + pb.b;
       nn.eps = 1e-5f; nn.relu = 1; nn.acc3 = sv.pool + ((size_t)(i - 1) * 5 + 2) * d * PM_BN_REPL;
-      nn.absmax_out = (sv.h2 && (d <= 256 || rt.bar)) ? sv.mdu + (i - 1) * PM_ABSMAX_SLOTS : nullptr;
-      if (rt.bar)
-        RUN(pm_bar_aggregate_bwd(sv.x[i], sv.T, dA, res_in_dagg ? nullptr : dx, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i,
-                                   out, dT, &nn, c.st));
-      else
-      RUN(pm_segreduce_bwd_norm(sv.x[i], sv.T, dA, res_in_dagg ? nullptr : dx, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i,
-                                  c.compact, out, dT, &nn, c.st));
-    } else if (rt.bar) {
-      RUN(pm_bar_aggregate_bwd(sv.x[i], sv.T, dA, res_in_dagg ? nullptr : dx, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i,
-                                 out, dT, nullptr, c.st));
-    } else {
-      RUN(pm_segreduce_bwd(sv.x[i], sv.T, dA, res_in_dagg ? nullptr : dx, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i,
-                             c.compact, out, dT, c.st));
+      nn.absmax_out = r.bagg_absmax ? sv.mdu + (i - 1) * PM_ABSMAX_SLOTS : nullptr;
+    }
+    switch (r.bagg) {
+      case GcnRoute::BAGG_SEG_DROPPED:
+        // dx_i = dx_{i+1} (residual) + dropout-mask * d(layer input): sv.xin is the DROPPED input the messages were built from
+        RUN(pm_segreduce_bwd(sv.xin[i], sv.T, dA, nullptr, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i, c.compact, dxin,
+                               dT, c.st));
+        drop(c, dxin, N, d, sv.site0 + i, sv.seed, dxin);
+        RUN(pm_add(dx, dxin, (int64_t)N * d, out, c.st));
+        break;
+      case GcnRoute::BAGG_BAR:
+        RUN(pm_bar_aggregate_bwd(sv.x[i], sv.T, dA, res, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i, out, dT,
+                                   carry ? &nn : nullptr, c.st));
+        break;
+      case GcnRoute::BAGG_SEG:
+        if (carry)
+          RUN(pm_segreduce_bwd_norm(sv.x[i], sv.T, dA, res, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i, c.compact, out,
+                                      dT, &nn, c.st));
+        else
+          RUN(pm_segreduce_bwd(sv.x[i], sv.T, dA, res, c.s->plan, N, c.E, c.Gn, d, sv.p, sv.seed, sv.uid0 + i, c.compact, out, dT, c.st));
+        break;
     }
     dx = out;
   }
-  branch_join(c, BR_GCL_DW0);
-  branch_join(c, BR_GCL_DW1);
   RUN(pm_edge_table_bwd(dT, d, c.G + g.nn_w, c.G + g.nn_b, c.st));
   return dx;
 }
@@ -769,7 +781,7 @@ void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
   // launches of the caller's stream (BranchScope::pause).
   BranchScope br(c, BR_ENC_FWD);
   const int S = c.S;                                   // token-level tensors are [N, S, .] (active slots only)
-  const bool rows_w_ok = gcl_width(d) && gcl_fused_on() && gcl_fits(N, d, S) && !cfg().no_rows_w;
+  const bool rows_w_ok = gcl_width(d) && cfg().gcl_fused && gcl_fits(N, d, S) && !cfg().no_rows_w;
   // ---------------- the batch's plan (CSR / CSC, row lists, histograms: plan.hip), issued first.  The content encoder's
   // first launches (embedding tables, gather, chord product: ~110 us) need only the token histogram, which the plan's
   // counting launch leaves behind; the remaining six launches of the plan (~50 us) and the encoder's weight preparation
@@ -833,7 +845,7 @@ void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
     }
     // the three un-embedding weights as k-major fragment planes for the input gradient of the backward (unembed.hip)
     s.w_unembed_dh = nullptr;
-    if (cfg().fused_ce && !cfg().no_unembed_dh && (dh == 64 || dh == 128 || dh == 256) &&
+    if (cfg().fused_ce && (dh == 64 || dh == 128 || dh == 256) &&
         (int64_t)N * S * (d > PM_N_TOK ? d : PM_N_TOK) * 4 < ((int64_t)1 << 31)) {   // (the kernel's 32-bit byte offsets into d_logits and dH)
       s.w_unembed_dh = (uint16_t*)ar.take((size_t)pm_unembed_dh_scratch_bytes(d));
       RUN(pm_unembed_dh(nullptr, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, nullptr, N, c.E, Gn, d, S,
@@ -1017,36 +1029,21 @@ void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
     // training accuracies (pm_vae_step_set_metrics): the head's metrics form writes the verdict bytes and clears the counts row,
     // one count launch behind the structure loss joins them — the default head's launches are the ones above when off
     int64_t* const met = logits_only ? nullptr : s.metrics;
-    if (fused_ce && !logits_only && s.pad_skip && met) {
-      RUN(pm_unembed_ce_rows_metrics(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
-                                       c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
-                                       (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
-                                       c.G + Y.dec_dur.b, s.losses, w_unembed, s.ue_lists, s.ue_counts, nullptr, s.verdict, met, c.st));
-      if (s.bt.flags & 4)            // (the rows left out have PAD targets: no verdict)
-        RUN(pm_unembed_ce_rows(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
-                                 c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
-                                 s.c_logits, s.dc_logits, nullptr, nullptr, nullptr, pad_losses, w_unembed, s.ue_lists + 3 * R,
-                                 s.ue_counts + 4, c.st));
-    } else if (fused_ce && !logits_only && met) {
-      RUN(pm_unembed_ce_metrics(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
-                                  c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
-                                  (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
-                                  c.G + Y.dec_dur.b, s.losses, w_unembed, nullptr, s.verdict, met, c.st));
-    } else if (fused_ce && !logits_only && s.pad_skip) {
-      RUN(pm_unembed_ce_rows(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
-                               c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
-                               (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
-                               c.G + Y.dec_dur.b, s.losses, w_unembed, s.ue_lists, s.ue_counts, c.st));
-      if (s.bt.flags & 4)            // every logit wanted: the same kernel over the rows left out (no loss, no gradient: PAD targets)
-        RUN(pm_unembed_ce_rows(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
-                                 c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
-                                 s.c_logits, s.dc_logits, nullptr, nullptr, nullptr, pad_losses, w_unembed, s.ue_lists + 3 * R,
-                                 s.ue_counts + 4, c.st));
-    } else if (fused_ce && !logits_only) {
-      RUN(pm_unembed_ce(s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b,
-                          c.P + Y.dec_dur.w, c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale,
-                          (s.bt.flags & 4) ? s.c_logits : nullptr, s.dc_logits, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b,
-                          c.G + Y.dec_dur.b, s.losses, w_unembed, c.st));
+    // the leading arguments the four forms of the kernel share, up to the logits to keep (or NULL), the three bias gradients and the losses
+#define UE_ARGS(logits, db_d, db_nd, db_dur, out)                                                                              \
+  s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b, c.P + Y.dec_dur.w,       \
+  c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale, logits, s.dc_logits, db_d, db_nd, db_dur, out, w_unembed
+#define UE_STEP UE_ARGS((s.bt.flags & 4) ? s.c_logits : nullptr, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, s.losses)
+    if (fused_ce && !logits_only) {
+      if (s.pad_skip && met) RUN(pm_unembed_ce_rows_metrics(UE_STEP, s.ue_lists, s.ue_counts, nullptr, s.verdict, met, c.st));
+      else if (met) RUN(pm_unembed_ce_metrics(UE_STEP, nullptr, s.verdict, met, c.st));
+      else if (s.pad_skip) RUN(pm_unembed_ce_rows(UE_STEP, s.ue_lists, s.ue_counts, c.st));
+      else RUN(pm_unembed_ce(UE_STEP, c.st));
+      // every logit wanted: the same kernel over the rows the lists left out (PAD targets: no loss, no gradient, no verdict)
+      if (s.pad_skip && (s.bt.flags & 4))
+        RUN(pm_unembed_ce_rows(UE_ARGS(s.c_logits, nullptr, nullptr, nullptr, pad_losses), s.ue_lists + 3 * R, s.ue_counts + 4, c.st));
+#undef UE_STEP
+#undef UE_ARGS
     } else {
     RUN(pm_gemm_f32(0, 1, (int)R, PM_N_DUR, dh, s.H + dh, d, c.P + Y.dec_dur.w, dh, s.c_logits + PM_N_PITCH, PM_N_TOK,
                       c.P + Y.dec_dur.b, 0, 1, nullptr, 0, nullptr, c.st));
@@ -1156,14 +1153,12 @@ void backward_decoder(Ctx& c) {
         lin_bwd(c, dH, s.dg.x[c.L], Y.dec_chord, N, S * d, d, nullptr);
     }
   };
-  const bool late_wgrads = cfg().late_wgrads;
-  if (!late_wgrads) decoder_weight_grads();
   if (chord_tn)     // dxL = dH @ W[:S*d, :] by the long-K kernel of linear.hip (weight rows as fragment-major planes, kind 1)
     RUN(pm_rows_times_weight_longk(dH, S * d, N, S * d, s.wf_dec_t, 1, 0, d, dxL, d, c.st));
   else
     lin_bwd(c, dH, s.dg.x[c.L], Y.dec_chord, N, S * d, d, dxL);        // slots >= S: zero gradient (all PAD)
   float* dx0 = gcn_backward(c, dxL, Y.dec_gcn, s.dg);
-  if (late_wgrads && cfg().late_wgrads_at != 2) decoder_weight_grads();
+  decoder_weight_grads();
   float* dcb = ar.f((size_t)Gn * d);
   RUN(pm_bar_broadcast_bwd(dx0, s.plan, N, c.E, Gn, d, dcb, c.st));
   Deferred df;
@@ -1175,12 +1170,10 @@ void backward_decoder(Ctx& c) {
   bn_bwd(c, s.zd, dzr, B, 2 * d, 1, Y.dec_bn, s.dm, s.dv, true, dzd);
   lin_bwd(c, dzd, s.z, Y.dec_lin, B, 2 * d, d, s.dz, 0, 0, 0, true, &df);
   RUN(pm_reparam_bwd(s.dz, s.lv, s.eps, (int64_t)B * d, s.dmu, s.dlv, c.st));
-  if (late_wgrads && cfg().late_wgrads_at == 2) decoder_weight_grads();
   if (df.n) {                                         // the two head products' weight gradients: behind the others on the second stream
-    BranchScope br(c, BR_DEC_WGRAD);
+    BranchScope br(c, BR_DEC_WGRAD);                  // (joined by pm_vae_step_join_decoder_grads / the encoder backward)
     flush_deferred(c, df);
   }
-  if (!late_wgrads) branch_join(c, BR_DEC_WGRAD);     // (late: joined by pm_vae_step_join_decoder_grads / the encoder backward)
 }
 
 // First part of the encoder backward: the head chain (mu / log_var heads, merge layer, bars encoder, attention pooling) and the
@@ -1349,9 +1342,8 @@ void measure_backward(Ctx& c) {
 }  // namespace
 
 extern "C" int64_t pm_vae_layout_bytes(void) { return (int64_t)sizeof(PmVaeLayout); }
-// The A/B switches of the step (PM_GCL_FUSED, PM_GCL_NO_DW, PM_NO_ROWS_W, PM_GCL_NO_CLASSES, PM_GCL_NO_BFRAG, PM_FUSED_CE,
-// PM_DENSE_DEG, PM_GCL_OFFSET_LIMIT, PM_DEBUG) are read from the environment once, when the library is loaded; this
-// re-reads them (host only; the next pm_vae_step_forward sees the new values) so that one process can run the same
+// The A/B switches of the step (the list above StepCfg; read_cfg() reads them all) are read from the environment once, when the
+// library is loaded; this re-reads them (host only; the next pm_vae_step_forward sees the new values) so that one process can run the same
 // batch through two kernel sets.
 extern "C" int pm_vae_step_reload_switches(void) {
   g_cfg = read_cfg();
@@ -1451,13 +1443,13 @@ extern "C" int pm_vae_step_info(const void* state, int32_t* info) {
   StepState tmp = *s;
   Ctx c = make_ctx(&tmp, nullptr);
   info[0] = c.compact; info[1] = c.planes; info[2] = c.S;
-  info[3] = (s->eg.Wfn && s->dg.Wfn) ? 1 : 0;          // fragment-major weight planes built (B-direct GEMM mode available)
+  info[3] = (s->eg.rt.frag && s->dg.rt.frag) ? 1 : 0;          // fragment-major weight planes built (B-direct GEMM mode available)
   info[4] = c.N; info[5] = c.E; info[6] = c.Gn; info[7] = c.B;
   // the EFFECTIVE switches (read from the environment at load / pm_vae_step_reload_switches, not at call time)
   info[8] = cfg().fused_ce ? 1 : 0; info[9] = pm_det_on() ? 0 : cfg().side_stream; info[10] = pm_det_on(); info[11] = cfg().gcl_fused ? 1 : 0;
   info[12] = cfg().dagg_bn ? 1 : 0;            // (the norm backward of the GCN layers inside the input gradient kernel)
   info[13] = s->chord_tab;                      // (the chord encoder as table algebra)
-  info[14] = (s->eg.h2 ? 1 : 0) | (s->dg.h2 ? 2 : 0);     // (the GCL products of the encoder / decoder stack in the fp16 pair format)
+  info[14] = (s->eg.rt.h2 ? 1 : 0) | (s->dg.rt.h2 ? 2 : 0);     // (the GCL products of the encoder / decoder stack in the fp16 pair format)
   info[15] = s->pad_skip;                       // (the decoder head ran over the row lists without PAD targets)
   return PM_OK;
 }

@@ -297,6 +297,9 @@ FORCED_ONLY = {
 DENSE_SHARD_B64 = dict(B=64, nb=2, d=512, L=8, p=1.0, dense=True, msg_p=0.1, seed=1234)
 
 
+PROF_CLASSES = 40            # launch classes of pm_prof_begin / pm_prof_end (PM_PROF_NCLASS of csrc/prof.h)
+
+
 def _as_dtype(batch, dtype):
     """The reference-format float inputs of a CPU batch (c_tensor, edge_attrs, s_tensor) in `dtype`."""
     out = BarGraphBatch(**{k: v for k, v in batch.__dict__.items() if not k.startswith("_")})
@@ -309,13 +312,17 @@ def _as_dtype(batch, dtype):
 def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     """One native HIP training step (the measured variant) on the synthetic batch of `spec`, default-init weights under
     manual_seed(0) and a fixed eps: model outputs, losses, gradients, the step variant, and what the oracle needs to
-    replay it (batch, state dict, eps, the two dropout seeds)."""
+    replay it (batch, state dict, eps, the two dropout seeds).  Optional keys of `spec`: `dropout` (0), `batch_norm` (True) — the
+    model's constructor switches — and `track_unique` (what the batch carries; False: the 7-block aggregates)."""
     import time
     from polyphemus_amd.model import VAE
     from polyphemus_amd.synthetic import synthetic_batch
     from polyphemus_amd.trainer import HipTrainer
-    cfg = dict(dropout=0, batch_norm=True, gnn_n_layers=spec["L"], d=spec["d"], n_bars=spec["nb"], resolution=8)
+    cfg = dict(dropout=spec.get("dropout", 0), batch_norm=spec.get("batch_norm", True), gnn_n_layers=spec["L"], d=spec["d"],
+               n_bars=spec["nb"], resolution=8)
     cpu = synthetic_batch(spec["B"], spec["nb"], p=spec["p"], seed=spec["seed"], dense=spec["dense"])
+    if "track_unique" in spec:
+        cpu.track_unique = bool(spec["track_unique"])
     torch.manual_seed(0)
     vae = VAE(**cfg, device=dev).to(dev)
     vae.train()
@@ -347,6 +354,7 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     info["launches"] = {"gcl_fwd": int(cnt[35]), "gcl_dagg": int(cnt[36]), "gcl_dw": int(cnt[37]), "rows_w": int(cnt[38]), "rows_tn": int(cnt[39]),
                         "planesB_nn": int(cnt[27]), "planesB_nt": int(cnt[28]), "planes_tn": int(cnt[26]),
                         "segreduce_fwd": int(cnt[33]), "segreduce_bwd": int(cnt[34])}
+    info["launch_counts"] = [int(cnt[i]) for i in range(PROF_CLASSES)]     # every launch class of the profiler, in its order
     hip = dict(s_logits=s_h.cpu(), c_logits=c_h.cpu(), mu=mu_h.cpu(), log_var=lv_h.cpu())
     hip_g = {n: tr._G[n].detach().cpu() for n in names}
     t_hip = time.time() - t0
