@@ -150,6 +150,32 @@ struct GcnRoute {
   bool frag;                             // fragment-major weight planes exist (B-direct GEMM mode)
   int classes;                           // 1: skip all-zero onset / next blocks (PM_GCL_NO_CLASSES clears it)
 };
+// Which kernels the chains around the two stacks take in this step — chord encoder, chord decoder, un-embedding — and where the
+// forward places its preparation: decided once by head_route() at the top of forward(), stored in StepState and only read
+// afterwards (the forward's stages, the backward calls, pm_vae_step_info / _outputs).  Like GcnRoute it never feeds a carve-out:
+// where a carve-out and a field share a predicate (rows_w_ok, chord_tab_ok, enc_frag_ok, unembed_dh_ok, fused_ce_on), both call it.
+// The route is taken at the forward FOR THE STEP: the backward calls read it, so one step is one consistent kernel set.  Changing
+// a switch (pm_vae_step_reload_switches) or the deterministic mode between a step's forward and its backward is not supported.
+struct HeadRoute {
+  // chord encoder, forward and dX: table algebra (chord.hip: no X) | all 15 slots: the full-width `lin` / `lin_bwd` | fragment
+  // planes of Wc (pm_rows_times_weight_longk forward, pm_rows_times_weight dX) | the fp32 tile product
+  enum Chord { CHORD_TABLES, CHORD_FULL, CHORD_FRAG, CHORD_TILES } chord;
+  bool chord_dw_tn;                      // ... its dW (CHORD_FRAG / CHORD_TILES): pm_rows_tn_weight_grad | the descriptor product with a_colsum
+  bool dec_rows;                         // chord decoder: forward on pm_rows_times_weight, dxL on the long-K kernel | `lin`, `lin_bwd`
+  bool dec_dw_tn;                        // ... its dW: pm_rows_tn_weight_grad | `lin_bwd`
+  // un-embedding, per direction: one kernel of unembed.hip (forward: fused with the cross-entropy) | three fp32 tile products
+  // (forward: followed by pm_content_ce_scaled / pm_content_accuracy_slots)
+  enum Ue { UE_KERNEL, UE_PRODUCTS } ue_fwd, ue_dh, ue_dw;
+  bool ue_rows;                          // ... over the row lists without the PAD targets (pm_unembed_row_lists; PM_PAD_SKIP): all three directions
+  bool keep_logits;                      // PmBatch.flags bit 2, the caller wants every logit: with ue_rows, a second forward pass over the PAD rows
+  bool logits_only;                      // PmBatch.flags bit 3, the caller computes the loss: logits by the products, no loss kernel
+  bool metrics;                          // the training accuracies are armed (pm_vae_step_set_metrics): the metrics form of the forward
+  // placement: the plan build on the second stream | the encoder's weight preparation on the caller's stream (in front of its
+  // wait for the plan) | the structure encoder ahead of the decoder's preparation on the second stream
+  bool plan_side, prep_main, senc_first;
+  // the switches the step was taken under, as pm_vae_step_info reports them
+  bool sw_fused_ce, sw_gcl_fused, sw_dagg_bn; int side_mask;
+};
 
 struct GcnSaved {
   GcnRoute rt;                           // filled by gcn_prepare
@@ -190,15 +216,17 @@ struct StepState {
   float *zd, *dm, *dv, *zr, *sb, *u1, *u2, *c2, *a2, *m2, *v2, *s_logits, *cb; GcnSaved dg; float *H, *c_logits;
   // loss gradients
   float *dc_logits, *ds_logits, *dmu, *dlv, *dz;
-  // rows of the decoder head that have a target (round 6, pm_unembed_row_lists): the fused un-embedding + CE, its input gradient and
-  // the un-embedding weight gradients skip the rows whose target is PAD (30 % at the bench's batches); off when the logits are kept or
-  // the caller supplies the loss
-  int pad_skip; int32_t* ue_lists; int32_t* ue_counts; float* dH;
+  HeadRoute head;
+  // rows of the decoder head that have a target (pm_unembed_row_lists, head.ue_rows): the fused un-embedding + CE, its input gradient
+  // and the un-embedding weight gradients skip the rows whose target is PAD (30 % at the bench's batches)
+  int32_t* ue_lists; int32_t* ue_counts; float* dH;
   float* dc_logits_own;                   // the arena's d(c_logits) buffer (dc_logits may point at the caller's gradient tensor: ext_loss)
-  float* PT; int chord_tab;          // chord encoder as table algebra (chord.hip): projected tables [2][S][2][131][d]
+  float* PT;                              // chord encoder as table algebra (chord.hip): projected tables [2][S][2][131][d]
   uint16_t *wf_enc, *wf_enc_t, *wf_dec, *wf_dec_t, *w_unembed_dh;   // chord encoder / decoder weights as fragment-major planes (kind 0 / 1)
   // cfg.dropout: the tensors behind the element dropout layers (the undropped ones when the model has none)
   const float *a1d, *h1d, *x0d, *xLg, *zcat_d, *zg_d, *zr_d, *sbd, *u1d, *H_d;
+  // ... and the buffers the dropped ones are written to: carved among their stage's activations, used where the layer runs
+  struct { float *a1, *h1, *x0, *xLg, *zcat, *zg, *zr, *sb, *u1; } dbuf;
   uint32_t seed_enc, seed_dec;
   float *bk_dx0, *bk_dzcat;               // carried from pm_vae_step_backward_encoder to ..._encoder_tail
   float *bk_dxL;                          // carried from pm_vae_step_backward_encoder_heads to pm_vae_step_backward_encoder
@@ -398,6 +426,18 @@ static bool gcl_fits(int N, int d, int S) {
   const int64_t lim = cfg().offset_limit;
   return (int64_t)N * 4 * d * 6 < lim && (int64_t)N * 4 * d * 4 < lim && (int64_t)N * S * d * 4 < lim;
 }
+// The predicates of the head chains that a carve-out AND a field of HeadRoute depend on: pure functions of shapes, layout and switches.
+// chord products on the kernels of linear.hip / wide.hip (their operands as fragment-major planes)
+static bool rows_w_ok(const Ctx& c) { return gcl_width(c.d) && cfg().gcl_fused && gcl_fits(c.N, c.d, c.S) && !cfg().no_rows_w; }
+// the chord encoder as table algebra (chord.hip): no X, no weight planes of its Linear
+static bool chord_tab_ok(const Ctx& c) { return cfg().chord_tables && c.d % 32 == 0 && c.d <= 512 && (int64_t)c.N * c.d * 4 < 0x7fffffffLL; }
+static bool enc_frag_ok(const Ctx& c) { return rows_w_ok(c) && c.S < PM_N_SLOTS && !chord_tab_ok(c); }
+static bool fused_ce_on() { return cfg().fused_ce; }
+// pm_unembed_dh's planes of the three un-embedding weights (its widths; the kernel's 32-bit byte offsets into d_logits and dH)
+static bool unembed_dh_ok(const Ctx& c) {
+  const int dh = c.d / 2;
+  return cfg().fused_ce && (dh == 64 || dh == 128 || dh == 256) && (int64_t)c.N * c.S * (c.d > PM_N_TOK ? c.d : PM_N_TOK) * 4 < ((int64_t)1 << 31);
+}
 // descriptor skeleton of the compact GCL contractions: four track-relation groups, rows of group t listed in
 // plan.trk_list[t*N ..], live count plan.trk_cnt[t]
 PmGemmDesc gcl_desc(const PmPlanView& pv, int N, int d, int classes) {
@@ -457,6 +497,39 @@ GcnRoute gcn_route(const Ctx& c, const GcnSaved& sv) {
   r.bagg_absmax = r.h2 && (d <= 256 || bar);
   return r;
 }
+// The record of the head chains (HeadRoute), from shapes, model and step switches, the mode and the batch's flags.  THE place where
+// the kernels of the chord encoder, the chord decoder and the un-embedding are chosen, forward and backward.
+HeadRoute head_route(const Ctx& c) {
+  const StepCfg& k = cfg();
+  const StepState& s = *c.s;
+  const int d = c.d, dh = d / 2;
+  const int64_t R = (int64_t)c.N * c.S;
+  HeadRoute r;
+  r.chord = chord_tab_ok(c) ? HeadRoute::CHORD_TABLES : c.S == PM_N_SLOTS ? HeadRoute::CHORD_FULL
+          : enc_frag_ok(c) ? HeadRoute::CHORD_FRAG : HeadRoute::CHORD_TILES;
+  r.chord_dw_tn = r.chord == HeadRoute::CHORD_FRAG && rows_tn_pays(d);
+  r.dec_rows = rows_w_ok(c);
+  r.dec_dw_tn = r.dec_rows && rows_tn_pays(d);
+  r.keep_logits = (s.bt.flags & 4) != 0;
+  r.logits_only = (s.bt.flags & 8) != 0;
+  r.metrics = !r.logits_only && s.metrics != nullptr;
+  r.plan_side = k.plan_side;
+  r.prep_main = r.chord == HeadRoute::CHORD_TABLES && r.plan_side;
+  r.senc_first = k.senc_first;
+  r.ue_fwd = (fused_ce_on() && !r.logits_only) ? HeadRoute::UE_KERNEL : HeadRoute::UE_PRODUCTS;
+  r.ue_dh = unembed_dh_ok(c) ? HeadRoute::UE_KERNEL : HeadRoute::UE_PRODUCTS;
+  // (the lists are built on the second stream behind the plan; off when the caller supplies the loss)
+  r.ue_rows = k.pad_skip && fused_ce_on() && r.plan_side && unembed_dh_ok(c) && !r.logits_only;
+  // (k_unembed_dw adds with float atomics per output block: the deterministic mode and d/2 < 128 keep the split-K tile products)
+  r.ue_dw = (k.unembed_dw && dh % 128 == 0 && !pm_det_on() && R * PM_N_TOK * 4 < ((int64_t)1 << 31) && R * (int64_t)d * 4 < ((int64_t)1 << 31))
+                ? HeadRoute::UE_KERNEL : HeadRoute::UE_PRODUCTS;
+  r.sw_fused_ce = k.fused_ce; r.sw_gcl_fused = k.gcl_fused; r.sw_dagg_bn = k.dagg_bn;
+  r.side_mask = k.side_stream;
+  return r;
+}
+// The caller's own d(c_logits) (pm_vae_step_set_output_grads) may be non-zero in any row, PAD targets included: the row lists
+// no longer name the rows that carry a gradient, so the backward's un-embedding kernels run over every row.
+void head_route_gradient_in_any_row(HeadRoute& r) { r.ue_rows = false; }
 // The part of a GCN stack's forward that depends on the parameters only: the distance table of the shared edge_nn and
 // the bf16 planes of the layers' weights.  Issued at the start of the step, on the second stream.
 void gcn_prepare(Ctx& c, const PmGcn& g, GcnSaved& sv) {
@@ -754,417 +827,471 @@ Ctx make_ctx(StepState* s, hipStream_t st) {
   return c;
 }
 
-// The forward pass + losses; with ar.base == nullptr it only measures the arena.
-void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
+// ---- the forward pass + losses as stages, called by forward() in the order the launches are issued.  Each stage does its own
+// carve-outs (their order is the workspace's layout) and then, in a real pass, its launches; with ar.base == nullptr it only
+// measures the arena.  Carve-outs depend on shapes, layout and the pure predicates above — never on the HeadRoute record.
+
+// BatchNorm2d + ReLU of the structure CNNs (model.py:218-238, 278-292), ReLU alone when the model has no norms
+void cnn_act_fwd(Ctx& c, const float* x, int O, int C, int I, PmBn bn, float* y, float* mean, float* var) {
+  if (c.bn) bn_fwd(c, x, O, C, I, bn, true, nullptr, y, mean, var);
+  else RUN(pm_relu_residual_fwd(x, nullptr, (int64_t)O * C * I, y, c.st));
+}
+void cnn_act_bwd(Ctx& c, const float* x, const float* dy, int O, int C, int I, PmBn bn, const float* mean, const float* var, float* dx) {
+  if (c.bn) bn_bwd(c, x, dy, O, C, I, bn, mean, var, true, dx);
+  else RUN(pm_relu_bwd(dy, x, (int64_t)O * C * I, dx, c.st));
+}
+// the embedding tables' parameters as pm_embed_tables takes them from the parameters (base = c.P) and pm_embed_tables_bwd hands
+// their gradients back (base = c.G): three Linear, three BatchNorm1d
+#define EMB_PARAMS(base)                                                                                                       \
+  base + Y.enc_pitch_d.w, base + Y.enc_pitch_d.b, base + Y.enc_pitch_nd.w, base + Y.enc_pitch_nd.b, base + Y.enc_dur.w,        \
+  base + Y.enc_dur.b, base + Y.enc_bn_d.w, base + Y.enc_bn_d.b, base + Y.enc_bn_nd.w, base + Y.enc_bn_nd.b,                    \
+  base + Y.enc_bn_dur.w, base + Y.enc_bn_dur.b
+// The un-embedding as three products of the fp32 tile GEMM (model.py:561-576: duration logits for every (node, slot) row, pitch
+// logits per drum / non-drum row list), in one of three directions: the logits from H | dH from d(logits) | the weight gradients
+// (split-K, accumulating).  Rows: the plan's two group lists for the pitch heads and every row for the duration head, or — `lists`,
+// weight gradients only — the head's three lists without the PAD targets.
+enum UeDir { UE_LOGITS, UE_DH, UE_DW };
+void unembed_products(Ctx& c, UeDir dir, bool lists, float* dH) {
   StepState& s = *c.s;
-  s.seed_enc = seed_enc; s.seed_dec = seed_dec;
-  const bool dropping = c.pdrop > 0.f;
-  Arena& ar = s.ar;
+  if (!s.ar.base) return;
   const PmVaeLayout& Y = s.lay;
-  const int N = c.N, Gn = c.Gn, B = c.B, d = c.d, nb = c.nb, dh = d / 2;
-  const bool run = ar.base != nullptr;
-  PmPlanView pv;
-  if (run) pv = pm_plan_view(s.plan, N, c.E, Gn);
-  s.bn_scratch = ar.dbl((size_t)PM_BN_SCRATCH(2 * d > 16 ? 2 * d : 16));
-  s.bn_scratch_side = ar.dbl((size_t)PM_BN_SCRATCH(2 * d > 16 ? 2 * d : 16));
-  c.bn_scratch = s.bn_scratch;
-  // ---------------- structure encoder (model.py:211-256,434-445)
-  s.zcat = ar.zf((size_t)B * 2 * d);                   // (zero region: its two halves are written by split-K products)
+  const int N = c.N, d = c.d, dh = d / 2;
+  const int64_t R = (int64_t)N * c.S;
+  const PmPlanView pv = pm_plan_view(s.plan, N, c.E, c.Gn);
+  const PmLin head[3] = {Y.dec_dur, Y.dec_pitch_d, Y.dec_pitch_nd};
+  for (int g = 0; g < 3; ++g) {                          // duration (columns [130, 230) of the logits, the upper half of H), drums, the rest
+    const int n_out = g ? PM_N_PITCH : PM_N_DUR, col = g ? 0 : PM_N_PITCH, hoff = g ? 0 : dh;
+    const int32_t* lst = g ? pv.row_list + (g == 2 ? (int64_t)N * PM_N_SLOTS : 0) : nullptr;
+    const int32_t* cnt = g ? pv.group_cnt + 1 + g : nullptr;
+    if (lists) { lst = s.ue_lists + (g + 2) % 3 * R; cnt = s.ue_counts + (g + 2) % 3; }   // (the lists' order: drums, the rest, duration)
+    const PmLin& w = head[g];
+    switch (dir) {
+      case UE_LOGITS:
+        RUN(pm_gemm_f32(0, 1, (int)R, n_out, dh, s.H + hoff, d, c.P + w.w, dh, s.c_logits + col, PM_N_TOK, c.P + w.b, 0, 1, lst,
+                          lst ? 1 : 0, cnt, c.st));
+        break;
+      case UE_DH:
+        RUN(pm_gemm_f32(0, 0, (int)R, dh, n_out, s.dc_logits + col, PM_N_TOK, c.P + w.w, dh, dH + hoff, d, nullptr, 0, 1, lst,
+                          lst ? 1 : 0, cnt, c.st));
+        break;
+      case UE_DW:
+        RUN(pm_gemm_f32(1, 0, n_out, dh, (int)R, s.dc_logits + col, PM_N_TOK, s.H + hoff, d, c.G + w.w, dh, nullptr, PM_GEMM_ACCUM, 0,
+                          lst, lst ? 1 : 0, cnt, c.st));
+        break;
+    }
+  }
+}
+
+// structure encoder (model.py:211-256,434-445): its activations, carved first; its launches go out behind the encoder stack
+// (structure_encoder below)
+void carve_structure_encoder(Ctx& c) {
+  StepState& s = *c.s; Arena& ar = s.ar;
+  const int Gn = c.Gn, d = c.d;
+  const bool dropping = c.pdrop > 0.f;
+  s.zcat = ar.zf((size_t)c.B * 2 * d);                 // (zero region: its two halves are written by split-K products)
   s.c0 = ar.f((size_t)Gn * 8 * 128); s.a0 = ar.f((size_t)Gn * 8 * 128); s.m0 = ar.f(8); s.v0 = ar.f(8);
   s.p0 = ar.f((size_t)Gn * 8 * 32); s.c1 = ar.f((size_t)Gn * 16 * 32); s.a1 = ar.f((size_t)Gn * 512);
   s.m1 = ar.f(16); s.v1 = ar.f(16); s.h1 = ar.f((size_t)Gn * d); s.h2 = ar.zf((size_t)Gn * d);
-  float* const a1d_buf = dropping ? ar.f((size_t)Gn * 512) : nullptr;
-  float* const h1d_buf = dropping ? ar.f((size_t)Gn * d) : nullptr;
-  // Second stream (forked here, at the very start of the step): everything that depends on the parameters only — first what
-  // the encoder needs (joined before the chord encoder), later what the decoder needs (joined before its first layer) —
-  // and the structure encoder (joined before the merge layer).  The host issues it in three pieces between the
-  // launches of the caller's stream (BranchScope::pause).
-  BranchScope br(c, BR_ENC_FWD);
-  const int S = c.S;                                   // token-level tensors are [N, S, .] (active slots only)
-  const bool rows_w_ok = gcl_width(d) && cfg().gcl_fused && gcl_fits(N, d, S) && !cfg().no_rows_w;
-  // ---------------- the batch's plan (CSR / CSC, row lists, histograms: plan.hip), issued first.  The content encoder's
-  // first launches (embedding tables, gather, chord product: ~110 us) need only the token histogram, which the plan's
-  // counting launch leaves behind; the remaining six launches of the plan (~50 us) and the encoder's weight preparation
-  // run BESIDE them on the second stream and are joined in front of the first GCL layer (PM_PLAN_SIDE=0: the plan on the
-  // caller's stream, in front of everything, as before).
-  const bool plan_side = cfg().plan_side;
-  if (!plan_side) br.pause();
-  if (run)
-    RUN(pm_plan_build_marked(s.bt.edge_index, s.bt.edge_type, s.bt.edge_dist, s.bt.bars, s.bt.batch, s.bt.is_drum, s.bt.tokens,
-                               nb, s.bt.n_slots, N, c.E, Gn, const_cast<int32_t*>(s.plan), c.st,
-                               plan_side ? br.mark_inside(BR_PLAN_COUNT) : nullptr));
-  // chord encoder Wc [d, 15d]: kind 0 for the forward (long-K kernel, columns [0, S*d)), kind 1 for its input gradient
-  s.wf_enc = s.wf_enc_t = s.wf_dec = s.wf_dec_t = nullptr;
-  // the chord encoder as table algebra (chord.hip): no X, no weight planes of its Linear
-  const bool chord_tab = cfg().chord_tables && d % 32 == 0 && d <= 512 && (int64_t)N * d * 4 < 0x7fffffffLL;
-  s.chord_tab = chord_tab ? 1 : 0;
-  const bool enc_frag = rows_w_ok && S < PM_N_SLOTS && !chord_tab;
-  if (enc_frag) {
-    s.wf_enc = (uint16_t*)ar.take((size_t)PM_N_SLOTS * d * d * 6);
-    s.wf_enc_t = (uint16_t*)ar.take((size_t)PM_N_SLOTS * d * d * 6);
+  s.dbuf.a1 = dropping ? ar.f((size_t)Gn * 512) : nullptr;
+  s.dbuf.h1 = dropping ? ar.f((size_t)Gn * d) : nullptr;
+}
+// chord encoder Wc [d, 15d] as fragment-major planes: kind 0 for the forward (long-K kernel, columns [0, S*d)), kind 1 for its
+// input gradient
+void chord_encoder_planes(Ctx& c, int kind) {
+  StepState& s = *c.s;
+  const int d = c.d;
+  if (s.head.chord == HeadRoute::CHORD_FRAG)
+    RUN(pm_split_planes_frag(c.P + s.lay.enc_chord.w, d, PM_N_SLOTS * d, kind, 1, (int64_t)PM_N_SLOTS * d * d,
+                               (int64_t)PM_N_SLOTS * d * d * 3, kind ? s.wf_enc_t : s.wf_enc, c.st));
+}
+// The batch's plan (CSR / CSC, row lists, histograms: plan.hip), issued first, and the encoder's weight preparation.  The content
+// encoder's first launches (embedding tables, gather, chord product: ~110 us) need only the token histogram, which the plan's
+// counting launch leaves behind; the remaining six launches of the plan (~50 us) and the encoder's weight preparation run BESIDE
+// them on the second stream and are joined in front of the first GCL layer (PM_PLAN_SIDE=0: the plan on the caller's stream, in
+// front of everything).
+void plan_and_encoder_prep(Ctx& c, BranchScope& br) {
+  StepState& s = *c.s;
+  const HeadRoute& rt = s.head;
+  const int d = c.d;
+  if (!rt.plan_side) br.pause();
+  RUN(pm_plan_build_marked(s.bt.edge_index, s.bt.edge_type, s.bt.edge_dist, s.bt.bars, s.bt.batch, s.bt.is_drum, s.bt.tokens,
+                             c.nb, s.bt.n_slots, c.N, c.E, c.Gn, const_cast<int32_t*>(s.plan), c.st,
+                             rt.plan_side ? br.mark_inside(BR_PLAN_COUNT) : nullptr));
+  if (enc_frag_ok(c)) {
+    s.wf_enc = (uint16_t*)s.ar.take((size_t)PM_N_SLOTS * d * d * 6);
+    s.wf_enc_t = (uint16_t*)s.ar.take((size_t)PM_N_SLOTS * d * d * 6);
   }
-  auto chord_planes = [&](int kind) {
-    if (enc_frag)
-      RUN(pm_split_planes_frag(c.P + Y.enc_chord.w, d, PM_N_SLOTS * d, kind, 1, (int64_t)PM_N_SLOTS * d * d,
-                                 (int64_t)PM_N_SLOTS * d * d * 3, kind ? s.wf_enc_t : s.wf_enc, c.st));
-  };
-  if (plan_side) {                                     // (the forward's planes on the caller's stream: its chord product is ~50 us away)
+  if (rt.plan_side) {                                  // (the forward's planes on the caller's stream: its chord product is ~50 us away)
     br.pause();
-    chord_planes(0);
+    chord_encoder_planes(c, 0);
   }
-  auto encoder_prep = [&]() {
-    br.resume();
-    if (!plan_side) chord_planes(0);
-    chord_planes(1);
-    gcn_prepare(c, Y.enc_gcn, s.eg);
-    br.mark(BR_WPREP);
-    br.pause();
-  };
-  // (table form of the chord encoder: its launches wait for the plan's counting launch only, ~35 us into the second stream's
-  //  work — the caller's stream has nothing to do until then, so the encoder's weight preparation (parameters only, ~30 us)
-  //  runs THERE, in front of that wait, and the second stream carries the plan alone)
-  const bool prep_main = chord_tab && plan_side;
-  if (prep_main) {
+  if (rt.prep_main) {
+    // (table form of the chord encoder: its launches wait for the plan's counting launch only, ~35 us into the second stream's
+    //  work — the caller's stream has nothing to do until then, so the encoder's weight preparation (parameters only, ~30 us)
+    //  runs THERE, in front of that wait, and the second stream carries the plan alone)
     br.mark(BR_WPREP);                                 // (what the first GCL layer waits for: the plan)
     br.pause();
-    gcn_prepare(c, Y.enc_gcn, s.eg);
-  } else encoder_prep();
-  // the rest of the branch: issued by decoder_prep_and_structure_encoder() below, behind the first launches of the content encoder
-  auto decoder_prep_and_structure_encoder = [&]() {
-    br.resume();
-    const bool senc_first = cfg().senc_first;
-    auto dec_prep = [&]() {
-    gcn_prepare(c, Y.dec_gcn, s.dg);
-    // chord decoder, rows [0, S*d) of its weight [15d, d]: kind 0 for the forward, kind 1 for the input gradient
-    if (rows_w_ok) {
-      s.wf_dec = (uint16_t*)ar.take((size_t)S * d * d * 6);
-      s.wf_dec_t = (uint16_t*)ar.take((size_t)S * d * d * 6);
-      for (int kind = 0; kind < 2; ++kind)
-        RUN(pm_split_planes_frag(c.P + Y.dec_chord.w, S * d, d, kind, 1, (int64_t)S * d * d, (int64_t)S * d * d * 3,
-                                   kind ? s.wf_dec_t : s.wf_dec, c.st));
-    }
-    // the three un-embedding weights as k-major fragment planes for the input gradient of the backward (unembed.hip)
-    s.w_unembed_dh = nullptr;
-    if (cfg().fused_ce && (dh == 64 || dh == 128 || dh == 256) &&
-        (int64_t)N * S * (d > PM_N_TOK ? d : PM_N_TOK) * 4 < ((int64_t)1 << 31)) {   // (the kernel's 32-bit byte offsets into d_logits and dH)
-      s.w_unembed_dh = (uint16_t*)ar.take((size_t)pm_unembed_dh_scratch_bytes(d));
-      RUN(pm_unembed_dh(nullptr, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, nullptr, N, c.E, Gn, d, S,
-                          nullptr, s.w_unembed_dh, 1, c.st));
-    }
-    // the decoder head's row lists without the PAD targets, and zeros in the rows of dH they leave out: tokens and plan only — here
-    // (second stream, behind the plan on the same stream), a millisecond ahead of their first reader
-    s.dH = ar.f((size_t)N * S * d);
-    // (PmBatch.flags bit 2 — the caller wants every logit —: the rows left out as lists of their own, for a second pass of the head)
-    const bool pad_rows = (s.bt.flags & 4) != 0;
-    s.ue_lists = (int32_t*)ar.take((size_t)6 * N * S * sizeof(int32_t));      // (3 + 3 whatever the flags: pm_vae_step_workspace_bytes does not see them)
-    s.ue_counts = (int32_t*)ar.take((size_t)pm_unembed_row_counts_len(N, S) * sizeof(int32_t));
-    s.pad_skip = (cfg().pad_skip && cfg().fused_ce && plan_side && s.w_unembed_dh && !(s.bt.flags & 8)) ? 1 : 0;
-    if (s.pad_skip)
-      RUN(pm_unembed_row_lists(s.bt.tokens, s.plan, N, c.E, Gn, d, S, s.ue_lists, pad_rows ? s.ue_lists + (size_t)3 * N * S : nullptr,
-                                 s.ue_counts, s.dH, c.st));
-    br.mark(BR_WPREP_DEC);
-    };
-    auto struct_enc = [&]() {
-    if (run) {
-    RUN(pm_conv3x3_fwd(s.bt.s_tensor, c.P + Y.enc_conv0.w, c.P + Y.enc_conv0.b, Gn, 1, 8, 4, 32, 0, s.c0, c.st));
-    if (c.bn) bn_fwd(c, s.c0, Gn, 8, 128, Y.enc_bn1, true, nullptr, s.a0, s.m0, s.v0);
-    else RUN(pm_relu_residual_fwd(s.c0, nullptr, (int64_t)Gn * 8 * 128, s.a0, c.st));       // model.py:218-238 without BatchNorm2d
-    RUN(pm_maxpool4_fwd(s.a0, (int64_t)Gn * 8 * 32, s.p0, c.st));
-    RUN(pm_conv3x3_fwd(s.p0, c.P + Y.enc_conv4.w, c.P + Y.enc_conv4.b, Gn, 8, 16, 4, 8, 0, s.c1, c.st));
-    if (c.bn) bn_fwd(c, s.c1, Gn, 16, 32, Y.enc_bn5, true, nullptr, s.a1, s.m1, s.v1);
-    else RUN(pm_relu_residual_fwd(s.c1, nullptr, (int64_t)Gn * 512, s.a1, c.st));
-    s.a1d = drop(c, s.a1, Gn, 512, SITE_ENC_CNN_IN, seed_enc, a1d_buf);                     // CNNEncoder.lin[0], model.py:244
-    lin(c, s.a1d, Y.enc_lin1, Gn, d, 512, s.h1, true);
-    s.h1d = drop(c, s.h1, Gn, d, SITE_ENC_CNN_MID, seed_enc, h1d_buf);                      // CNNEncoder.lin[3], model.py:247
-    lin(c, s.h1d, Y.enc_lin4, Gn, d, d, s.h2, false);
-    lin(c, s.h2, Y.enc_s_bars, B, d, nb * d, s.zcat + d, false, nb * d, 2 * d);           // z_s = zcat[:, d:]
-    }
-    br.mark(BR_ENC_S_FWD);
-    };
-    // the structure encoder FIRST (round 6): its output is wanted behind the encoder's eighth layer, the decoder's weight planes and row
-    // lists a stack later — in the other order the merge layer waited for this branch (PM_SENC_FIRST=0)
-    if (senc_first) { struct_enc(); dec_prep(); } else { dec_prep(); struct_enc(); }
-    br.end();
-  };
-  // ---------------- content encoder (model.py:344-417)
-  float* tables = ar.f((size_t)4 * PM_N_PITCH * dh);
+    gcn_prepare(c, s.lay.enc_gcn, s.eg);
+    return;
+  }
+  br.resume();
+  if (!rt.plan_side) chord_encoder_planes(c, 0);
+  chord_encoder_planes(c, 1);
+  gcn_prepare(c, s.lay.enc_gcn, s.eg);
+  br.mark(BR_WPREP);
+  br.pause();
+}
+// content encoder up to its GCN stack (model.py:344-417): embedding tables, chord encoder; returns the stack's input
+float* embeddings_and_chord_encoder(Ctx& c) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const HeadRoute& rt = s.head;
+  const int N = c.N, B = c.B, d = c.d, dh = d / 2, S = c.S;     // token-level tensors are [N, S, .] (active slots only)
+  const bool dropping = c.pdrop > 0.f, chord_tab = chord_tab_ok(c);
+  s.tables = ar.f((size_t)4 * PM_N_PITCH * dh);
   s.emb_stats = ar.f((size_t)4 * 2 * dh);
-  s.X = chord_tab ? nullptr : ar.f((size_t)N * S * d);
+  s.X = chord_tab ? nullptr : ar.f((size_t)N * S * d);           // (table form: no X, no weight planes of the chord Linear)
   s.PT = chord_tab ? ar.f((size_t)2 * S * 2 * PM_N_PITCH * d) : nullptr;
   s.x0 = ar.f((size_t)N * d);
-  s.tables = tables; s.cvec = ar.f((size_t)2 * d);
-  float* const x0d_buf = dropping ? ar.f((size_t)N * d) : nullptr;
-  float* const xLg_buf = dropping ? ar.f((size_t)N * d) : nullptr;
-  float* const zcatd_buf = dropping ? ar.f((size_t)B * 2 * d) : nullptr;
-  float* const zgd_buf = dropping ? ar.f((size_t)B * d) : nullptr;
-  uint16_t* const wf_enc = s.wf_enc;
-  if (run) {
-    branch_join(c, BR_PLAN_COUNT);                     // the token histogram of the plan (second stream) is final
-    RUN(pm_embed_tables(c.P + Y.enc_pitch_d.w, c.P + Y.enc_pitch_d.b, c.P + Y.enc_pitch_nd.w, c.P + Y.enc_pitch_nd.b,
-                          c.P + Y.enc_dur.w, c.P + Y.enc_dur.b, c.P + Y.enc_bn_d.w, c.P + Y.enc_bn_d.b,
-                          c.P + Y.enc_bn_nd.w, c.P + Y.enc_bn_nd.b, c.P + Y.enc_bn_dur.w, c.P + Y.enc_bn_dur.b,
-                          c.Bf + Y.enc_bn_d.rm, c.Bf + Y.enc_bn_d.rv, c.Bf + Y.enc_bn_nd.rm, c.Bf + Y.enc_bn_nd.rv,
-                          c.Bf + Y.enc_bn_dur.rm, c.Bf + Y.enc_bn_dur.rv, pv.tok_hist, d, 1, 1e-5f, 0.1f, tables,
-                          s.emb_stats, c.st));
-    if (chord_tab) {
-      // x0 = relu(cvec[group] + the 2 S looked-up rows of the projected tables): two launches, no X
-      RUN(pm_chord_tables_fwd(tables, c.P + Y.enc_chord.w, d, S, s.PT, c.P + Y.enc_chord.b, s.cvec, c.st));
-      s.eg.x0_maxed = s.eg.mx != nullptr;          // (max x0 = the |max| the encoder's first GCL layer scales its operand by)
-      RUN(pm_chord_sum_fwd_absmax(s.PT, s.cvec, s.bt.tokens, s.bt.is_drum, N, d, S, s.x0, s.eg.mx, c.st));
-      if (!plan_side) branch_join(c, BR_WPREP);
-    } else {
-    RUN(pm_embed_gather(tables, s.bt.tokens, s.bt.is_drum, N, d, S, s.X, c.st));
-    if (!plan_side) branch_join(c, BR_WPREP);          // weight planes and distance tables are ready
-    if (S == PM_N_SLOTS) lin(c, s.X, Y.enc_chord, N, d, PM_N_SLOTS * d, s.x0, true);
-    else {             // x0 = relu(X[:, :S] @ Wc[:, :S*d]^T + (bias + all-PAD tail slots, one vector per node group))
-      if (wf_enc) {                // long-K kernel of linear.hip: Wc [d, 15d] as fragment-major planes (kind 0), columns [0, S*d)
-        RUN(pm_rows_times_weight_longk(s.X, S * d, N, S * d, wf_enc, 0, PM_N_SLOTS * d / 16, d, s.x0, d, c.st));
-      } else
-        RUN(pm_gemm_f32(0, 1, N, d, S * d, s.X, S * d, c.P + Y.enc_chord.w, PM_N_SLOTS * d, s.x0, d, nullptr, 0, 1,
-                          nullptr, 0, nullptr, c.st));
-      RUN(pm_chord_pad_fwd(tables, c.P + Y.enc_chord.w, c.P + Y.enc_chord.b, s.bt.is_drum, N, d, S, s.cvec, s.x0, c.st));
+  s.cvec = ar.f((size_t)2 * d);
+  s.dbuf.x0 = dropping ? ar.f((size_t)N * d) : nullptr;
+  s.dbuf.xLg = dropping ? ar.f((size_t)N * d) : nullptr;
+  s.dbuf.zcat = dropping ? ar.f((size_t)B * 2 * d) : nullptr;
+  s.dbuf.zg = dropping ? ar.f((size_t)B * d) : nullptr;
+  float* const stack_in = dropping ? s.dbuf.x0 : s.x0;
+  if (!ar.base) return stack_in;
+  const PmPlanView pv = pm_plan_view(s.plan, N, c.E, c.Gn);
+  branch_join(c, BR_PLAN_COUNT);                       // the token histogram of the plan (second stream) is final
+  RUN(pm_embed_tables(EMB_PARAMS(c.P), c.Bf + Y.enc_bn_d.rm, c.Bf + Y.enc_bn_d.rv, c.Bf + Y.enc_bn_nd.rm, c.Bf + Y.enc_bn_nd.rv,
+                        c.Bf + Y.enc_bn_dur.rm, c.Bf + Y.enc_bn_dur.rv, pv.tok_hist, d, 1, 1e-5f, 0.1f, s.tables, s.emb_stats, c.st));
+  if (rt.chord == HeadRoute::CHORD_TABLES) {
+    // x0 = relu(cvec[group] + the 2 S looked-up rows of the projected tables): two launches, no X
+    RUN(pm_chord_tables_fwd(s.tables, c.P + Y.enc_chord.w, d, S, s.PT, c.P + Y.enc_chord.b, s.cvec, c.st));
+    s.eg.x0_maxed = s.eg.mx != nullptr;                // (max x0 = the |max| the encoder's first GCL layer scales its operand by)
+    RUN(pm_chord_sum_fwd_absmax(s.PT, s.cvec, s.bt.tokens, s.bt.is_drum, N, d, S, s.x0, s.eg.mx, c.st));
+    if (!rt.plan_side) branch_join(c, BR_WPREP);
+  } else {
+    RUN(pm_embed_gather(s.tables, s.bt.tokens, s.bt.is_drum, N, d, S, s.X, c.st));
+    if (!rt.plan_side) branch_join(c, BR_WPREP);       // weight planes and distance tables are ready
+    // x0 = relu(X[:, :S] @ Wc[:, :S*d]^T + (bias + all-PAD tail slots, one vector per node group))
+    switch (rt.chord) {
+      case HeadRoute::CHORD_FULL: lin(c, s.X, Y.enc_chord, N, d, PM_N_SLOTS * d, s.x0, true); break;
+      case HeadRoute::CHORD_FRAG:                      // long-K kernel of linear.hip: Wc as fragment-major planes (kind 0), columns [0, S*d)
+        RUN(pm_rows_times_weight_longk(s.X, S * d, N, S * d, s.wf_enc, 0, PM_N_SLOTS * d / 16, d, s.x0, d, c.st)); break;
+      default:
+        RUN(pm_gemm_f32(0, 1, N, d, S * d, s.X, S * d, c.P + Y.enc_chord.w, PM_N_SLOTS * d, s.x0, d, nullptr, 0, 1, nullptr, 0,
+                          nullptr, c.st));
     }
-    }
-    s.x0d = drop(c, s.x0, N, d, SITE_ENC_CHORD, seed_enc, x0d_buf);                          // model.py:389-390 (row = node)
+    if (rt.chord != HeadRoute::CHORD_FULL)
+      RUN(pm_chord_pad_fwd(s.tables, c.P + Y.enc_chord.w, c.P + Y.enc_chord.b, s.bt.is_drum, N, d, S, s.cvec, s.x0, c.st));
   }
-  if (run) branch_join(c, BR_WPREP);                   // the plan, the GCL weight planes and the distance table are ready
-  float* xL = gcn_forward(c, dropping ? x0d_buf : s.x0, Y.enc_gcn, s.eg, seed_enc, 0, msg_p);
-  decoder_prep_and_structure_encoder();                // (second stream; issued while the GPU works through the encoder's layers)
+  s.x0d = drop(c, s.x0, N, d, SITE_ENC_CHORD, s.seed_enc, s.dbuf.x0);                         // model.py:389-390 (row = node)
+  return stack_in;
+}
+// decoder preparation: everything of the decoder that depends on the parameters, the tokens and the plan only (second stream)
+void decoder_prep(Ctx& c, BranchScope& br) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const int N = c.N, d = c.d, S = c.S;
+  gcn_prepare(c, Y.dec_gcn, s.dg);
+  // chord decoder, rows [0, S*d) of its weight [15d, d]: kind 0 for the forward, kind 1 for the input gradient
+  if (rows_w_ok(c)) {
+    s.wf_dec = (uint16_t*)ar.take((size_t)S * d * d * 6);
+    s.wf_dec_t = (uint16_t*)ar.take((size_t)S * d * d * 6);
+    for (int kind = 0; kind < 2; ++kind)
+      RUN(pm_split_planes_frag(c.P + Y.dec_chord.w, S * d, d, kind, 1, (int64_t)S * d * d, (int64_t)S * d * d * 3,
+                                 kind ? s.wf_dec_t : s.wf_dec, c.st));
+  }
+  // the three un-embedding weights as k-major fragment planes for the input gradient of the backward (unembed.hip)
+  if (unembed_dh_ok(c)) {
+    s.w_unembed_dh = (uint16_t*)ar.take((size_t)pm_unembed_dh_scratch_bytes(d));
+    RUN(pm_unembed_dh(nullptr, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, nullptr, N, c.E, c.Gn, d, S,
+                        nullptr, s.w_unembed_dh, 1, c.st));
+  }
+  // the decoder head's row lists without the PAD targets, and zeros in the rows of dH they leave out: tokens and plan only — here
+  // (second stream, behind the plan on the same stream), a millisecond ahead of their first reader
+  s.dH = ar.f((size_t)N * S * d);
+  s.ue_lists = (int32_t*)ar.take((size_t)6 * N * S * sizeof(int32_t));      // (3 + 3 whatever the flags: pm_vae_step_workspace_bytes does not see them)
+  s.ue_counts = (int32_t*)ar.take((size_t)pm_unembed_row_counts_len(N, S) * sizeof(int32_t));
+  // (the logits are kept: the rows left out as lists of their own, for a second pass of the head)
+  if (s.head.ue_rows)
+    RUN(pm_unembed_row_lists(s.bt.tokens, s.plan, N, c.E, c.Gn, d, S, s.ue_lists,
+                               s.head.keep_logits ? s.ue_lists + (size_t)3 * N * S : nullptr, s.ue_counts, s.dH, c.st));
+  br.mark(BR_WPREP_DEC);
+}
+// the structure encoder's launches (its activations: carve_structure_encoder)
+void structure_encoder(Ctx& c, BranchScope& br) {
+  StepState& s = *c.s; const PmVaeLayout& Y = s.lay;
+  const int Gn = c.Gn, d = c.d, nb = c.nb;
+  if (s.ar.base) {
+    RUN(pm_conv3x3_fwd(s.bt.s_tensor, c.P + Y.enc_conv0.w, c.P + Y.enc_conv0.b, Gn, 1, 8, 4, 32, 0, s.c0, c.st));
+    cnn_act_fwd(c, s.c0, Gn, 8, 128, Y.enc_bn1, s.a0, s.m0, s.v0);
+    RUN(pm_maxpool4_fwd(s.a0, (int64_t)Gn * 8 * 32, s.p0, c.st));
+    RUN(pm_conv3x3_fwd(s.p0, c.P + Y.enc_conv4.w, c.P + Y.enc_conv4.b, Gn, 8, 16, 4, 8, 0, s.c1, c.st));
+    cnn_act_fwd(c, s.c1, Gn, 16, 32, Y.enc_bn5, s.a1, s.m1, s.v1);
+    s.a1d = drop(c, s.a1, Gn, 512, SITE_ENC_CNN_IN, s.seed_enc, s.dbuf.a1);                 // CNNEncoder.lin[0], model.py:244
+    lin(c, s.a1d, Y.enc_lin1, Gn, d, 512, s.h1, true);
+    s.h1d = drop(c, s.h1, Gn, d, SITE_ENC_CNN_MID, s.seed_enc, s.dbuf.h1);                  // CNNEncoder.lin[3], model.py:247
+    lin(c, s.h1d, Y.enc_lin4, Gn, d, d, s.h2, false);
+    lin(c, s.h2, Y.enc_s_bars, c.B, d, nb * d, s.zcat + d, false, nb * d, 2 * d);         // z_s = zcat[:, d:]
+  }
+  br.mark(BR_ENC_S_FWD);
+}
+// The rest of the branch forked at the start of the step, issued behind the launches of the encoder stack (the GPU works through
+// its layers meanwhile).  The structure encoder FIRST: its output is wanted behind the encoder's last layer, the decoder's weight
+// planes and row lists a stack later — in the other order the merge layer waited for this branch (PM_SENC_FIRST=0)
+void decoder_prep_and_structure_encoder(Ctx& c, BranchScope& br) {
+  br.resume();
+  if (c.s->head.senc_first) { structure_encoder(c, br); decoder_prep(c, br); }
+  else { decoder_prep(c, br); structure_encoder(c, br); }
+  br.end();
+}
+// gate network + attention pooling over the encoder stack's output, bars encoder (model.py:396-417)
+void attention_pool(Ctx& c, float* xL) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const int N = c.N, Gn = c.Gn, d = c.d;
   s.g = ar.f(N); s.gm = ar.f(4); s.gv = ar.f(4); s.alpha = ar.f(N); s.pooled = ar.f((size_t)Gn * d);
-  if (run) {
-    s.xLg = drop(c, xL, N, d, SITE_ENC_GATE, seed_enc, xLg_buf);                             // MLP.forward of the gate, model.py:160
-    RUN(pm_gate_fwd(s.xLg, c.P + Y.enc_gate.w, c.P + Y.enc_gate.b, N, d, s.g, c.st));
-    RUN(pm_bn_stats(s.g, N, 1, 1, s.gm, s.gv, c.Bf + Y.enc_gate_bn.rm, c.Bf + Y.enc_gate_bn.rv, 0.1f, c.bn_scratch, c.st));
-    RUN(pm_attnpool_fwd(xL, s.g, s.gm, s.gv, 1e-5f, c.P + Y.enc_gate_bn.w, c.P + Y.enc_gate_bn.b, s.plan, N, c.E, Gn, d,
-                          s.alpha, s.pooled, c.st));
-    lin(c, s.pooled, Y.enc_c_bars, B, d, nb * d, s.zcat, false, nb * d, 2 * d);   // z_c = zcat[:, :d]
-  }
-  // ---------------- merge + heads (model.py:472-481), reparametrisation (model.py:671-673)
+  if (!ar.base) return;
+  s.xLg = drop(c, xL, N, d, SITE_ENC_GATE, s.seed_enc, s.dbuf.xLg);                          // MLP.forward of the gate, model.py:160
+  RUN(pm_gate_fwd(s.xLg, c.P + Y.enc_gate.w, c.P + Y.enc_gate.b, N, d, s.g, c.st));
+  RUN(pm_bn_stats(s.g, N, 1, 1, s.gm, s.gv, c.Bf + Y.enc_gate_bn.rm, c.Bf + Y.enc_gate_bn.rv, 0.1f, c.bn_scratch, c.st));
+  RUN(pm_attnpool_fwd(xL, s.g, s.gm, s.gv, 1e-5f, c.P + Y.enc_gate_bn.w, c.P + Y.enc_gate_bn.b, s.plan, N, c.E, Gn, d,
+                        s.alpha, s.pooled, c.st));
+  lin(c, s.pooled, Y.enc_c_bars, c.B, d, c.nb * d, s.zcat, false, c.nb * d, 2 * d);          // z_c = zcat[:, :d]
+}
+// merge + heads (model.py:472-481), reparametrisation (model.py:671-673), and the two losses nothing of the decoder feeds
+void merge_and_latent(Ctx& c) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const int B = c.B, d = c.d;
   s.m = ar.zf((size_t)B * d); s.mm = ar.f(d); s.mv = ar.f(d); s.zg = ar.f((size_t)B * d);
   s.mu = ar.zf((size_t)B * d); s.lv = ar.zf((size_t)B * d); s.z = ar.f((size_t)B * d);
   s.dmu = ar.zf((size_t)B * d); s.dlv = ar.zf((size_t)B * d);
-  // ---------------- decoder (model.py:634-655)
+  if (!ar.base) return;
+  branch_join(c, BR_ENC_S_FWD);                       // the structure encoder's z_s
+  s.zcat_d = drop(c, s.zcat, B, 2 * d, SITE_ENC_MERGE_IN, s.seed_enc, s.dbuf.zcat);          // Encoder.dropout_layer, model.py:473
+  lin(c, s.zcat_d, Y.enc_merge, B, d, 2 * d, s.m, false);
+  bn_fwd(c, s.m, B, d, 1, Y.enc_bn_merge, true, nullptr, s.zg, s.mm, s.mv);
+  s.zg_d = drop(c, s.zg, B, d, SITE_ENC_MERGE_OUT, s.seed_enc, s.dbuf.zg);                   // model.py:479
+  // mu and log_var (model.py:480-481): two Linear(d, d) on the same input — one grouped launch (the weights lie where the flat
+  // parameter buffer has them, the outputs in the cleared region: K slices add with atomics as in `lin`'s small-product path)
+  if (d % 64 == 0 && d >= 128)
+    RUN(pm_gemm_f32_grouped(0, 1, B, d, d, s.zg_d, d, c.P + Y.enc_mu.w, d, s.mu, d, c.P + Y.enc_mu.b, PM_GEMM_ACCUM | PM_GEMM_ZEROED,
+                              d / 64 < 8 ? d / 64 : 8, nullptr, 0, nullptr, 2, 0, (int64_t)Y.enc_lv.w - (int64_t)Y.enc_mu.w, s.lv - s.mu,
+                              (int64_t)Y.enc_lv.b - (int64_t)Y.enc_mu.b, 0, 0, c.st));
+  else {
+    lin(c, s.zg_d, Y.enc_mu, B, d, d, s.mu, false);
+    lin(c, s.zg_d, Y.enc_lv, B, d, d, s.lv, false);
+  }
+  RUN(pm_reparam_fwd(s.mu, s.lv, s.eps, (int64_t)B * d, s.z, c.st));
+  if (s.head.logits_only) return;
+  // the KL term (mu, log_var) and, when the structure loss is the reference's constant (training.py:307 evaluates the BCE on the
+  // target itself, SURVEY B-1), that constant — two 64-workgroup launches beside the decoder, joined in front of the structure loss
+  // (`losses` is the caller's buffer: words 2 and 3 are cleared here, behind the fork, words 0 and 1 are stored by the cross-entropy)
+  BranchScope br(c, BR_LOSSES);
+  if (hipMemsetAsync(s.losses + 2, 0, 2 * sizeof(double), c.st) != hipSuccess) c.chk(PM_E_LAUNCH);
+  RUN(pm_kld_acc(s.mu, s.lv, B, d, s.beta, s.dmu, s.dlv, s.losses, c.st));
+  if (!s.fix_structure) RUN(pm_bce_logits_acc(s.bt.s_tensor, s.bt.s_tensor, (int64_t)c.Gn * 128, 1.0f, nullptr, s.losses, c.st));
+}
+// decoder up to its GCN stack (model.py:634-655): first layer, bars decoder, broadcast of the bar vectors to their nodes; returns
+// the stack's input.  The structure decoder's activations lie between the trunk's (carved here, used by structure_decoder).
+float* decoder_trunk(Ctx& c) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const int N = c.N, Gn = c.Gn, B = c.B, d = c.d;
+  const bool dropping = c.pdrop > 0.f;
   s.zd = ar.zf((size_t)B * 2 * d); s.dm = ar.f(2 * d); s.dv = ar.f(2 * d); s.zr = ar.f((size_t)B * 2 * d);
   s.sb = ar.zf((size_t)Gn * d); s.u1 = ar.f((size_t)Gn * d); s.u2 = ar.f((size_t)Gn * 512);
   s.c2 = ar.f((size_t)Gn * 8 * 128); s.a2 = ar.f((size_t)Gn * 8 * 128); s.m2 = ar.f(8); s.v2 = ar.f(8);
   s.s_logits = ar.f((size_t)Gn * 128); s.cb = ar.zf((size_t)Gn * d);
   float* xd0 = ar.f((size_t)N * d);
-  float* const zrd_buf = dropping ? ar.f((size_t)B * 2 * d) : nullptr;
-  float* const sbd_buf = dropping ? ar.f((size_t)Gn * d) : nullptr;
-  float* const u1d_buf = dropping ? ar.f((size_t)Gn * d) : nullptr;
-  if (run) {
-    branch_join(c, BR_ENC_S_FWD);                     // the structure encoder's z_s
-    s.zcat_d = drop(c, s.zcat, B, 2 * d, SITE_ENC_MERGE_IN, seed_enc, zcatd_buf);            // Encoder.dropout_layer, model.py:473
-    lin(c, s.zcat_d, Y.enc_merge, B, d, 2 * d, s.m, false);
-    bn_fwd(c, s.m, B, d, 1, Y.enc_bn_merge, true, nullptr, s.zg, s.mm, s.mv);
-    s.zg_d = drop(c, s.zg, B, d, SITE_ENC_MERGE_OUT, seed_enc, zgd_buf);                     // model.py:479
-    // mu and log_var (model.py:480-481): two Linear(d, d) on the same input — one grouped launch (the weights lie where the flat
-    // parameter buffer has them, the outputs in the cleared region: K slices add with atomics as in `lin`'s small-product path)
-    if (d % 64 == 0 && d >= 128)
-      RUN(pm_gemm_f32_grouped(0, 1, B, d, d, s.zg_d, d, c.P + Y.enc_mu.w, d, s.mu, d, c.P + Y.enc_mu.b, PM_GEMM_ACCUM | PM_GEMM_ZEROED,
-                                d / 64 < 8 ? d / 64 : 8, nullptr, 0, nullptr, 2, 0, (int64_t)Y.enc_lv.w - (int64_t)Y.enc_mu.w, s.lv - s.mu,
-                                (int64_t)Y.enc_lv.b - (int64_t)Y.enc_mu.b, 0, 0, c.st));
-    else {
-      lin(c, s.zg_d, Y.enc_mu, B, d, d, s.mu, false);
-      lin(c, s.zg_d, Y.enc_lv, B, d, d, s.lv, false);
-    }
-    RUN(pm_reparam_fwd(s.mu, s.lv, s.eps, (int64_t)B * d, s.z, c.st));
-    if (!(s.bt.flags & 8)) {
-      // the two losses nothing of the decoder feeds: the KL term (mu, log_var) and, when the structure loss is the reference's
-      // constant (training.py:307 evaluates the BCE on the target itself, SURVEY B-1), that constant — two 64-workgroup launches
-      // that used to follow the cross-entropy on the caller's stream, with a clear each
-      // (`losses` is the caller's buffer: words 2 and 3 are cleared here, behind the fork, words 0 and 1 are stored by the cross-entropy)
-      BranchScope br(c, BR_LOSSES);
-      if (hipMemsetAsync(s.losses + 2, 0, 2 * sizeof(double), c.st) != hipSuccess) c.chk(PM_E_LAUNCH);
-      RUN(pm_kld_acc(s.mu, s.lv, B, d, s.beta, s.dmu, s.dlv, s.losses, c.st));
-      if (!s.fix_structure) RUN(pm_bce_logits_acc(s.bt.s_tensor, s.bt.s_tensor, (int64_t)Gn * 128, 1.0f, nullptr, s.losses, c.st));
-    }
-    lin(c, s.z, Y.dec_lin, B, 2 * d, d, s.zd, false);
-    bn_fwd(c, s.zd, B, 2 * d, 1, Y.dec_bn, true, nullptr, s.zr, s.dm, s.dv);
-    s.zr_d = drop(c, s.zr, B, 2 * d, SITE_DEC_IN, seed_dec, zrd_buf);                        // Decoder.dropout, model.py:640
-    lin(c, s.zr_d + d, Y.dec_c_bars, B, nb * d, d, s.cb, false, 2 * d, 0);                // A = zr[:, d:]
-    RUN(pm_bar_broadcast_fwd(s.cb, s.plan, N, c.E, Gn, d, xd0, c.st));
-  }
-  // structure decoder: second stream, beside the chord decoder and the un-embedding (beside the decoder's first GCL layers it
-  // cost one k_gcl_fwd launch 22 us for the same step time); joined before the losses
-  auto structure_decoder = [&]() {
-    BranchScope br(c, BR_DEC_FWD);
-    lin(c, s.zr_d, Y.dec_s_bars, B, nb * d, d, s.sb, false, 2 * d, 0);                    // A = zr[:, :d]
-    s.sbd = drop(c, s.sb, Gn, d, SITE_DEC_CNN_IN, seed_dec, sbd_buf);                        // CNNDecoder.lin[0], model.py:267
-    lin(c, s.sbd, Y.dec_s_lin1, Gn, d, d, s.u1, true);
-    s.u1d = drop(c, s.u1, Gn, d, SITE_DEC_CNN_MID, seed_dec, u1d_buf);                       // CNNDecoder.lin[3], model.py:270
-    lin(c, s.u1d, Y.dec_s_lin4, Gn, 512, d, s.u2, true);
-    RUN(pm_conv3x3_fwd(s.u2, c.P + Y.dec_conv1.w, c.P + Y.dec_conv1.b, Gn, 16, 8, 4, 32, 1, s.c2, c.st));
-    if (c.bn) bn_fwd(c, s.c2, Gn, 8, 128, Y.dec_bn2, true, nullptr, s.a2, s.m2, s.v2);
-    else RUN(pm_relu_residual_fwd(s.c2, nullptr, (int64_t)Gn * 8 * 128, s.a2, c.st));       // model.py:278-292 without BatchNorm2d
-    RUN(pm_conv3x3_fwd(s.a2, c.P + Y.dec_conv4.w, c.P + Y.dec_conv4.b, Gn, 8, 1, 4, 32, 0, s.s_logits, c.st));
-  };
-  if (run) branch_join(c, BR_WPREP_DEC);               // the decoder's weight planes and distance table are ready
-  if (run) branch_join(c, BR_ENC_FWD);                 // (the end of that branch: same stream, in order)
-  s.dg.x0_src = s.cb; s.dg.x0_src_n = (int64_t)Gn * d;
-  float* xdL = gcn_forward(c, xd0, Y.dec_gcn, s.dg, seed_dec, 1000, msg_p);
-  if (run) structure_decoder();
+  s.dbuf.zr = dropping ? ar.f((size_t)B * 2 * d) : nullptr;
+  s.dbuf.sb = dropping ? ar.f((size_t)Gn * d) : nullptr;
+  s.dbuf.u1 = dropping ? ar.f((size_t)Gn * d) : nullptr;
+  if (!ar.base) return xd0;
+  lin(c, s.z, Y.dec_lin, B, 2 * d, d, s.zd, false);
+  bn_fwd(c, s.zd, B, 2 * d, 1, Y.dec_bn, true, nullptr, s.zr, s.dm, s.dv);
+  s.zr_d = drop(c, s.zr, B, 2 * d, SITE_DEC_IN, s.seed_dec, s.dbuf.zr);                      // Decoder.dropout, model.py:640
+  lin(c, s.zr_d + d, Y.dec_c_bars, B, c.nb * d, d, s.cb, false, 2 * d, 0);                // A = zr[:, d:]
+  RUN(pm_bar_broadcast_fwd(s.cb, s.plan, N, c.E, Gn, d, xd0, c.st));
+  return xd0;
+}
+// structure decoder (model.py:258-299): second stream, beside the chord decoder and the un-embedding (beside the decoder's first
+// GCL layers it cost one k_gcl_fwd launch 22 us for the same step time); joined before the losses
+void structure_decoder(Ctx& c) {
+  StepState& s = *c.s;
+  if (!s.ar.base) return;
+  const PmVaeLayout& Y = s.lay;
+  const int Gn = c.Gn, d = c.d;
+  BranchScope br(c, BR_DEC_FWD);
+  lin(c, s.zr_d, Y.dec_s_bars, c.B, c.nb * d, d, s.sb, false, 2 * d, 0);                  // A = zr[:, :d]
+  s.sbd = drop(c, s.sb, Gn, d, SITE_DEC_CNN_IN, s.seed_dec, s.dbuf.sb);                      // CNNDecoder.lin[0], model.py:267
+  lin(c, s.sbd, Y.dec_s_lin1, Gn, d, d, s.u1, true);
+  s.u1d = drop(c, s.u1, Gn, d, SITE_DEC_CNN_MID, s.seed_dec, s.dbuf.u1);                     // CNNDecoder.lin[3], model.py:270
+  lin(c, s.u1d, Y.dec_s_lin4, Gn, 512, d, s.u2, true);
+  RUN(pm_conv3x3_fwd(s.u2, c.P + Y.dec_conv1.w, c.P + Y.dec_conv1.b, Gn, 16, 8, 4, 32, 1, s.c2, c.st));
+  cnn_act_fwd(c, s.c2, Gn, 8, 128, Y.dec_bn2, s.a2, s.m2, s.v2);
+  RUN(pm_conv3x3_fwd(s.a2, c.P + Y.dec_conv4.w, c.P + Y.dec_conv4.b, Gn, 8, 1, 4, 32, 0, s.s_logits, c.st));
+}
+// decoder head behind the GCN stack: chord decoder, un-embedding, the losses, the training accuracies
+void decoder_head(Ctx& c, const float* xdL) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const HeadRoute& rt = s.head;
+  const int N = c.N, Gn = c.Gn, d = c.d, S = c.S;
   const int64_t R = (int64_t)N * S;                    // (node, active slot) rows of the head
   s.H = ar.f((size_t)R * d); s.c_logits = ar.f((size_t)R * PM_N_TOK);
   s.dc_logits = s.dc_logits_own = ar.f((size_t)R * PM_N_TOK); s.ds_logits = ar.f((size_t)Gn * 128);
+  // planes of the three un-embedding weights + accumulator replicas of the fused kernel
+  uint16_t* const w_unembed = fused_ce_on() ? (uint16_t*)ar.take((size_t)pm_unembed_scratch_bytes(d)) : nullptr;
+  double* const pad_losses = ar.zdbl(4);              // (the zero losses of the second head pass over the PAD rows)
+  if (!ar.base) return;
   // chord decoder (K = d, S*d output columns): A-stationary kernel of linear.hip, its weight rows as fragment-major planes
-  uint16_t* const wf_dec = s.wf_dec;
-  const bool rows_w = wf_dec != nullptr;
-  const bool fused_ce = cfg().fused_ce;
-  uint16_t* w_unembed = fused_ce ? (uint16_t*)ar.take((size_t)pm_unembed_scratch_bytes(d)) : nullptr;   // planes of the three un-embedding weights + accumulator replicas
-  double* const pad_losses = ar.zdbl(4);              // (the zero losses of the second head pass over the PAD rows, PmBatch.flags bit 2)
-  if (run) {
-    if (rows_w) {
-      RUN(pm_rows_times_weight(xdL, d, N, d, wf_dec, 0, 0, S * d, c.P + Y.dec_chord.b, s.H, S * d, c.st));
-    } else
-      lin(c, xdL, Y.dec_chord, N, S * d, d, s.H, false);          // rows [0, S*d) of chord_decoder.weight
-    drop(c, s.H, N, S * d, SITE_DEC_CHORD, seed_dec, s.H);        // ContentDecoder.dropout_layer, model.py:558-559 (in place; row = node)
-    // un-embedding (model.py:561-576: duration logits for every (node, slot) row, pitch logits per drum / non-drum row
-    // list) fused with the two cross-entropy terms of the loss (training.py:316-323): the logits of a 64-row tile never
-    // leave the CU, d(loss)/d(logits) and the three bias gradients come out; the logits themselves only on request
-    // (csrc/unembed.hip; PM_FUSED_CE=0: three products + the loss kernel)
-    // PmBatch.flags bit 3 (the drop-in module: the CALLER computes the loss): the logits only — three fp32 products, no
-    // cross-entropy, no d(logits) (224 MB at 15 slots that pm_vae_step_set_output_grads would overwrite), no KLD / BCE
-    const bool logits_only = (s.bt.flags & 8) != 0;
-    // training accuracies (pm_vae_step_set_metrics): the head's metrics form writes the verdict bytes and clears the counts row,
-    // one count launch behind the structure loss joins them — the default head's launches are the ones above when off
-    int64_t* const met = logits_only ? nullptr : s.metrics;
+  if (rt.dec_rows) RUN(pm_rows_times_weight(xdL, d, N, d, s.wf_dec, 0, 0, S * d, c.P + Y.dec_chord.b, s.H, S * d, c.st));
+  else lin(c, xdL, Y.dec_chord, N, S * d, d, s.H, false);       // rows [0, S*d) of chord_decoder.weight
+  drop(c, s.H, N, S * d, SITE_DEC_CHORD, s.seed_dec, s.H);        // ContentDecoder.dropout_layer, model.py:558-559 (in place; row = node)
+  // un-embedding fused with the two cross-entropy terms of the loss (training.py:316-323): the logits of a 64-row tile never
+  // leave the CU, d(loss)/d(logits) and the three bias gradients come out; the logits themselves only on request
+  // (csrc/unembed.hip; PM_FUSED_CE=0: three products + the loss kernel).
+  // rt.logits_only (the drop-in module: the CALLER computes the loss): the logits only — three fp32 products, no cross-entropy,
+  // no d(logits) (224 MB at 15 slots that pm_vae_step_set_output_grads would overwrite), no KLD / BCE.
+  // rt.metrics (pm_vae_step_set_metrics): the head's metrics form writes the verdict bytes and clears the counts row, one count
+  // launch behind the structure loss joins them.
+  int64_t* const met = rt.metrics ? s.metrics : nullptr;
+  if (rt.ue_fwd == HeadRoute::UE_KERNEL) {
     // the leading arguments the four forms of the kernel share, up to the logits to keep (or NULL), the three bias gradients and the losses
 #define UE_ARGS(logits, db_d, db_nd, db_dur, out)                                                                              \
   s.H, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_d.b, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_pitch_nd.b, c.P + Y.dec_dur.w,       \
   c.P + Y.dec_dur.b, s.bt.tokens, s.plan, N, c.E, Gn, d, S, 1.0f, s.bt.ce_scale, logits, s.dc_logits, db_d, db_nd, db_dur, out, w_unembed
-#define UE_STEP UE_ARGS((s.bt.flags & 4) ? s.c_logits : nullptr, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, s.losses)
-    if (fused_ce && !logits_only) {
-      if (s.pad_skip && met) RUN(pm_unembed_ce_rows_metrics(UE_STEP, s.ue_lists, s.ue_counts, nullptr, s.verdict, met, c.st));
-      else if (met) RUN(pm_unembed_ce_metrics(UE_STEP, nullptr, s.verdict, met, c.st));
-      else if (s.pad_skip) RUN(pm_unembed_ce_rows(UE_STEP, s.ue_lists, s.ue_counts, c.st));
-      else RUN(pm_unembed_ce(UE_STEP, c.st));
-      // every logit wanted: the same kernel over the rows the lists left out (PAD targets: no loss, no gradient, no verdict)
-      if (s.pad_skip && (s.bt.flags & 4))
-        RUN(pm_unembed_ce_rows(UE_ARGS(s.c_logits, nullptr, nullptr, nullptr, pad_losses), s.ue_lists + 3 * R, s.ue_counts + 4, c.st));
+#define UE_STEP UE_ARGS(rt.keep_logits ? s.c_logits : nullptr, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, s.losses)
+    if (rt.ue_rows && met) RUN(pm_unembed_ce_rows_metrics(UE_STEP, s.ue_lists, s.ue_counts, nullptr, s.verdict, met, c.st));
+    else if (met) RUN(pm_unembed_ce_metrics(UE_STEP, nullptr, s.verdict, met, c.st));
+    else if (rt.ue_rows) RUN(pm_unembed_ce_rows(UE_STEP, s.ue_lists, s.ue_counts, c.st));
+    else RUN(pm_unembed_ce(UE_STEP, c.st));
+    // every logit wanted: the same kernel over the rows the lists left out (PAD targets: no loss, no gradient, no verdict)
+    if (rt.ue_rows && rt.keep_logits)
+      RUN(pm_unembed_ce_rows(UE_ARGS(s.c_logits, nullptr, nullptr, nullptr, pad_losses), s.ue_lists + 3 * R, s.ue_counts + 4, c.st));
 #undef UE_STEP
 #undef UE_ARGS
-    } else {
-    RUN(pm_gemm_f32(0, 1, (int)R, PM_N_DUR, dh, s.H + dh, d, c.P + Y.dec_dur.w, dh, s.c_logits + PM_N_PITCH, PM_N_TOK,
-                      c.P + Y.dec_dur.b, 0, 1, nullptr, 0, nullptr, c.st));
-    RUN(pm_gemm_f32(0, 1, (int)R, PM_N_PITCH, dh, s.H, d, c.P + Y.dec_pitch_d.w, dh, s.c_logits, PM_N_TOK,
-                      c.P + Y.dec_pitch_d.b, 0, 1, pv.row_list, 1, pv.group_cnt + 2, c.st));
-    RUN(pm_gemm_f32(0, 1, (int)R, PM_N_PITCH, dh, s.H, d, c.P + Y.dec_pitch_nd.w, dh, s.c_logits, PM_N_TOK,
-                      c.P + Y.dec_pitch_nd.b, 0, 1, pv.row_list + (int64_t)N * PM_N_SLOTS, 1, pv.group_cnt + 3, c.st));
-    if (!logits_only)
-    RUN(pm_content_ce_scaled(s.c_logits, s.bt.tokens, pv.tok_hist, s.bt.is_drum, N, S, 1.0f, s.bt.ce_scale, s.dc_logits,
-                               c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, s.losses, c.st));
-    if (met) RUN(pm_content_accuracy_slots(s.c_logits, s.bt.tokens, nullptr, N, S, s.verdict, met, c.st));
+  } else {
+    unembed_products(c, UE_LOGITS, false, nullptr);
+    if (!rt.logits_only) {
+      const PmPlanView pv = pm_plan_view(s.plan, N, c.E, Gn);
+      RUN(pm_content_ce_scaled(s.c_logits, s.bt.tokens, pv.tok_hist, s.bt.is_drum, N, S, 1.0f, s.bt.ce_scale, s.dc_logits,
+                                 c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, s.losses, c.st));
     }
-    branch_join(c, BR_LOSSES);                     // (the KL term and the constant structure loss, issued behind the reparametrisation)
-    branch_join(c, BR_DEC_FWD);
-    if (!logits_only && s.fix_structure)
-      RUN(pm_bce_logits_acc(s.s_logits, s.bt.s_tensor, (int64_t)Gn * 128, 1.0f, s.ds_logits, s.losses, c.st));
-    // the join of the verdicts + the structure counts, on the structure loss's input (the target itself unless
-    // structure_loss_on_logits: SURVEY B-1, as evaluate_batch)
-    if (met)
-      RUN(pm_train_metric_counts(s.bt.tokens, s.bt.is_drum, s.verdict, N, S, s.fix_structure ? s.s_logits : s.bt.s_tensor,
-                                 s.bt.s_tensor, (int64_t)Gn * 128, met, c.st));
+    if (met) RUN(pm_content_accuracy_slots(s.c_logits, s.bt.tokens, nullptr, N, S, s.verdict, met, c.st));
   }
+  branch_join(c, BR_LOSSES);                           // (the KL term and the constant structure loss, issued behind the reparametrisation)
+  branch_join(c, BR_DEC_FWD);
+  if (!rt.logits_only && s.fix_structure)
+    RUN(pm_bce_logits_acc(s.s_logits, s.bt.s_tensor, (int64_t)Gn * 128, 1.0f, s.ds_logits, s.losses, c.st));
+  // the join of the verdicts + the structure counts, on the structure loss's input (the target itself unless
+  // structure_loss_on_logits: SURVEY B-1, as evaluate_batch)
+  if (met)
+    RUN(pm_train_metric_counts(s.bt.tokens, s.bt.is_drum, s.verdict, N, S, s.fix_structure ? s.s_logits : s.bt.s_tensor,
+                               s.bt.s_tensor, (int64_t)Gn * 128, met, c.st));
 }
 
-void backward_decoder(Ctx& c) {
-  StepState& s = *c.s;
-  Arena& ar = s.ar;
-  const PmVaeLayout& Y = s.lay;
-  const int N = c.N, Gn = c.Gn, B = c.B, d = c.d, nb = c.nb, dh = d / 2;
-  PmPlanView pv = pm_plan_view(s.plan, N, c.E, Gn);
-  const int S = c.S;
-  const int64_t R = (int64_t)N * S;
-  float* dzr = ar.zf((size_t)B * 2 * d);
-  // ---- structure decoder (only when the structure loss reaches the logits)
-  if (s.fix_structure) {
-    BranchScope br(c, BR_DEC_BWD);                     // joined before the norm of the decoder's first layer
-    float* da2 = ar.f((size_t)Gn * 8 * 128); float* dc2 = ar.f((size_t)Gn * 8 * 128);
-    float* du2 = ar.f((size_t)Gn * 512); float* du1 = ar.zf((size_t)Gn * d); float* dsb = ar.zf((size_t)Gn * d);
-    RUN(pm_conv3x3_bwd_weight(s.a2, s.ds_logits, Gn, 8, 1, 4, 32, 0, c.G + Y.dec_conv4.w, c.G + Y.dec_conv4.b, c.st));
-    RUN(pm_conv3x3_bwd_data(s.ds_logits, c.P + Y.dec_conv4.w, Gn, 8, 1, 4, 32, 0, da2, c.st));
-    if (c.bn) bn_bwd(c, s.c2, da2, Gn, 8, 128, Y.dec_bn2, s.m2, s.v2, true, dc2);
-    else RUN(pm_relu_bwd(da2, s.c2, (int64_t)Gn * 8 * 128, dc2, c.st));
-    RUN(pm_conv3x3_bwd_weight(s.u2, dc2, Gn, 16, 8, 4, 32, 1, c.G + Y.dec_conv1.w, c.G + Y.dec_conv1.b, c.st));
-    RUN(pm_conv3x3_bwd_data(dc2, c.P + Y.dec_conv1.w, Gn, 16, 8, 4, 32, 1, du2, c.st));
-    RUN(pm_relu_bwd(du2, s.u2, (int64_t)Gn * 512, du2, c.st));
-    lin_bwd(c, du2, s.u1d, Y.dec_s_lin4, Gn, 512, d, du1);
-    drop(c, du1, Gn, d, SITE_DEC_CNN_MID, s.seed_dec, du1);
-    RUN(pm_relu_bwd(du1, s.u1, (int64_t)Gn * d, du1, c.st));
-    lin_bwd(c, du1, s.sbd, Y.dec_s_lin1, Gn, d, d, dsb);
-    drop(c, dsb, Gn, d, SITE_DEC_CNN_IN, s.seed_dec, dsb);
-    lin_bwd(c, dsb, s.zr_d, Y.dec_s_bars, B, nb * d, d, dzr, 0, 2 * d, 2 * d);
+// The forward pass + losses; with ar.base == nullptr it only measures the arena.
+void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const bool run = ar.base != nullptr;
+  s.seed_enc = seed_enc; s.seed_dec = seed_dec;
+  s.head = head_route(c);
+  s.bn_scratch = ar.dbl((size_t)PM_BN_SCRATCH(2 * c.d > 16 ? 2 * c.d : 16));
+  s.bn_scratch_side = ar.dbl((size_t)PM_BN_SCRATCH(2 * c.d > 16 ? 2 * c.d : 16));
+  c.bn_scratch = s.bn_scratch;
+  carve_structure_encoder(c);
+  // Second stream (forked here, at the very start of the step): everything that depends on the parameters only — first what
+  // the encoder needs (joined before the chord encoder), later what the decoder needs (joined before its first layer) —
+  // and the structure encoder (joined before the merge layer).  The host issues it in three pieces between the
+  // launches of the caller's stream (BranchScope::pause).
+  BranchScope br(c, BR_ENC_FWD);
+  plan_and_encoder_prep(c, br);
+  float* x0 = embeddings_and_chord_encoder(c);
+  if (run) branch_join(c, BR_WPREP);                   // the plan, the GCL weight planes and the distance table are ready
+  float* xL = gcn_forward(c, x0, Y.enc_gcn, s.eg, seed_enc, 0, msg_p);
+  decoder_prep_and_structure_encoder(c, br);
+  attention_pool(c, xL);
+  merge_and_latent(c);
+  float* xd0 = decoder_trunk(c);
+  if (run) branch_join(c, BR_WPREP_DEC);               // the decoder's weight planes and distance table are ready
+  if (run) branch_join(c, BR_ENC_FWD);                 // (the end of that branch: same stream, in order)
+  s.dg.x0_src = s.cb; s.dg.x0_src_n = (int64_t)c.Gn * c.d;
+  float* xdL = gcn_forward(c, xd0, Y.dec_gcn, s.dg, seed_dec, 1000, msg_p);
+  structure_decoder(c);
+  decoder_head(c, xdL);
+}
+
+// ---- the decoder's backward, in stages
+// structure decoder (only when the structure loss reaches the logits): second stream, joined before the norm of the decoder's
+// first layer; its gradient arrives in dzr[:, :d]
+void structure_decoder_backward(Ctx& c, float* dzr) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const int Gn = c.Gn, d = c.d;
+  BranchScope br(c, BR_DEC_BWD);
+  float* da2 = ar.f((size_t)Gn * 8 * 128); float* dc2 = ar.f((size_t)Gn * 8 * 128);
+  float* du2 = ar.f((size_t)Gn * 512); float* du1 = ar.zf((size_t)Gn * d); float* dsb = ar.zf((size_t)Gn * d);
+  RUN(pm_conv3x3_bwd_weight(s.a2, s.ds_logits, Gn, 8, 1, 4, 32, 0, c.G + Y.dec_conv4.w, c.G + Y.dec_conv4.b, c.st));
+  RUN(pm_conv3x3_bwd_data(s.ds_logits, c.P + Y.dec_conv4.w, Gn, 8, 1, 4, 32, 0, da2, c.st));
+  cnn_act_bwd(c, s.c2, da2, Gn, 8, 128, Y.dec_bn2, s.m2, s.v2, dc2);
+  RUN(pm_conv3x3_bwd_weight(s.u2, dc2, Gn, 16, 8, 4, 32, 1, c.G + Y.dec_conv1.w, c.G + Y.dec_conv1.b, c.st));
+  RUN(pm_conv3x3_bwd_data(dc2, c.P + Y.dec_conv1.w, Gn, 16, 8, 4, 32, 1, du2, c.st));
+  RUN(pm_relu_bwd(du2, s.u2, (int64_t)Gn * 512, du2, c.st));
+  lin_bwd(c, du2, s.u1d, Y.dec_s_lin4, Gn, 512, d, du1);
+  drop(c, du1, Gn, d, SITE_DEC_CNN_MID, s.seed_dec, du1);
+  RUN(pm_relu_bwd(du1, s.u1, (int64_t)Gn * d, du1, c.st));
+  lin_bwd(c, du1, s.sbd, Y.dec_s_lin1, Gn, d, d, dsb);
+  drop(c, dsb, Gn, d, SITE_DEC_CNN_IN, s.seed_dec, dsb);
+  lin_bwd(c, dsb, s.zr_d, Y.dec_s_bars, c.B, c.nb * d, d, dzr, 0, 2 * d, 2 * d);
+}
+// input gradient of the three un-embeddings (the critical chain: dH -> dxL -> the decoder's layers) into s.dH (carved by the
+// forward: the rows of PAD targets are zero already when the lists are used)
+void unembed_input_grad(Ctx& c) {
+  StepState& s = *c.s; const PmVaeLayout& Y = s.lay;
+  const HeadRoute& rt = s.head;
+  const int N = c.N, d = c.d, S = c.S;
+  if (rt.ue_dh == HeadRoute::UE_PRODUCTS) unembed_products(c, UE_DH, false, s.dH);
+  else if (rt.ue_rows)                                  // one launch on the bf16 pipe (unembed.hip) over the rows that have a target
+    RUN(pm_unembed_dh_rows(s.dc_logits, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, s.plan, N, c.E, c.Gn, d, S,
+                             s.dH, s.w_unembed_dh, s.ue_lists, s.ue_counts, c.st));
+  else                                                  // ... over every row
+    RUN(pm_unembed_dh(s.dc_logits, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, s.plan, N, c.E, c.Gn, d, S,
+                        s.dH, s.w_unembed_dh, 0, c.st));
+  drop(c, s.dH, N, S * d, SITE_DEC_CHORD, s.seed_dec, s.dH);       // backward of ContentDecoder.dropout_layer (in place)
+}
+// The weight gradients of the un-embeddings and of the chord decoder (nobody in this call waits for them): second stream.
+// WHEN: beside the decoder's GCL layers they cost the first layer's three kernels 174 us (67 + 94 + 146 against
+// 46 + 46 + 41 us: those hold one workgroup per CU) for 385 us of their own; the head chain behind the layers (bar
+// broadcast, the decoder's and the encoder's head products and norms: ~40 launches of 16-64 workgroups, ~400 us) leaves
+// the chip all but idle, so they are issued there and joined when the decoder's gradient bucket is needed
+// (pm_vae_step_join_decoder_grads: data parallel) or before the encoder's GCL layers (pm_vae_step_backward_encoder).
+void decoder_weight_grads(Ctx& c) {
+  StepState& s = *c.s; const PmVaeLayout& Y = s.lay;
+  const HeadRoute& rt = s.head;
+  const int N = c.N, d = c.d, S = c.S;
+  BranchScope br(c, BR_DEC_WGRAD);
+  // the three un-embedding weight gradients: one launch that reads every row once (unembed.hip k_unembed_dw; float atomics per
+  // output block: the deterministic mode, d/2 < 128 and PM_UNEMBED_DW=0 keep the three split-K tile products)
+  if (rt.ue_dw == HeadRoute::UE_KERNEL)
+    RUN(pm_unembed_dw(s.dc_logits, s.H, s.plan, N, c.E, c.Gn, d, S, c.G + Y.dec_pitch_d.w, c.G + Y.dec_pitch_nd.w, c.G + Y.dec_dur.w,
+                        rt.ue_rows ? s.ue_lists : nullptr, rt.ue_rows ? s.ue_counts : nullptr, c.st));
+  else unembed_products(c, UE_DW, rt.ue_rows, nullptr);
+  if (s.ext_loss) {
+    // the caller's loss: the bias gradients of the three un-embeddings are the column sums of ITS d(logits) (with the
+    // step's own loss the fused un-embedding + cross-entropy kernel of the forward has already left them)
+    RUN(pm_unembed_bias_grads(s.dc_logits, s.bt.is_drum, N, S, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, c.st));
   }
-  // ---- content decoder
-  float* dH = s.dH;                                     // (carved by the forward: the rows of PAD targets are zero already when pad_skip)
-  const bool skip = s.pad_skip != 0;
-  // input gradients of the three un-embeddings first (the critical chain: dH -> dxL -> the decoder's layers) ...
-  const PmLin pit[2] = {Y.dec_pitch_d, Y.dec_pitch_nd};
-  if (s.w_unembed_dh && skip)                           // ... over the rows that have a target
-    RUN(pm_unembed_dh_rows(s.dc_logits, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, s.plan, N, c.E, Gn, d, S,
-                             dH, s.w_unembed_dh, s.ue_lists, s.ue_counts, c.st));
-  else if (s.w_unembed_dh)                              // one launch on the bf16 pipe (unembed.hip)
-    RUN(pm_unembed_dh(s.dc_logits, c.P + Y.dec_pitch_d.w, c.P + Y.dec_pitch_nd.w, c.P + Y.dec_dur.w, s.plan, N, c.E, Gn, d, S,
-                        dH, s.w_unembed_dh, 0, c.st));
-  else {
-    RUN(pm_gemm_f32(0, 0, (int)R, dh, PM_N_DUR, s.dc_logits + PM_N_PITCH, PM_N_TOK, c.P + Y.dec_dur.w, dh, dH + dh, d,
-                      nullptr, 0, 1, nullptr, 0, nullptr, c.st));
-    for (int g = 0; g < 2; ++g) {
-      const int32_t* lst = pv.row_list + (g ? (int64_t)N * PM_N_SLOTS : 0);   // (node, slot) rows of the group
-      RUN(pm_gemm_f32(0, 0, (int)R, dh, PM_N_PITCH, s.dc_logits, PM_N_TOK, c.P + pit[g].w, dh, dH, d, nullptr, 0, 1, lst,
-                        1, pv.group_cnt + 2 + g, c.st));
-    }
-  }
-  drop(c, dH, N, S * d, SITE_DEC_CHORD, s.seed_dec, dH);           // backward of ContentDecoder.dropout_layer (in place)
-  float* dxL = ar.f((size_t)N * d);
-  const bool chord_tn = s.wf_dec_t != nullptr;
-  // ... their weight gradients and the chord decoder's (nobody in this call waits for them) go to the second stream.
-  // WHEN: beside the decoder's GCL layers they cost the first layer's three kernels 174 us (67 + 94 + 146 against
-  // 46 + 46 + 41 us: those hold one workgroup per CU) for 385 us of their own; the head chain behind the layers (bar
-  // broadcast, the decoder's and the encoder's head products and norms: ~40 launches of 16-64 workgroups, ~400 us) leaves
-  // the chip all but idle, so they are issued there and joined when the decoder's gradient bucket is needed
-  // (pm_vae_step_join_decoder_grads: data parallel) or before the encoder's GCL layers (pm_vae_step_backward_encoder).
-  auto decoder_weight_grads = [&]() {
-    BranchScope br(c, BR_DEC_WGRAD);
-    // the three un-embedding weight gradients: one launch that reads every row once (unembed.hip k_unembed_dw; float atomics per
-    // output block: the deterministic mode, d/2 < 128 and PM_UNEMBED_DW=0 keep the three split-K tile products)
-    if (cfg().unembed_dw && dh % 128 == 0 && !pm_det_on() && R * PM_N_TOK * 4 < ((int64_t)1 << 31) && R * (int64_t)d * 4 < ((int64_t)1 << 31)) {
-      RUN(pm_unembed_dw(s.dc_logits, s.H, s.plan, N, c.E, Gn, d, S, c.G + Y.dec_pitch_d.w, c.G + Y.dec_pitch_nd.w, c.G + Y.dec_dur.w,
-                          skip ? s.ue_lists : nullptr, skip ? s.ue_counts : nullptr, c.st));
-    } else {
-    RUN(pm_gemm_f32(1, 0, PM_N_DUR, dh, (int)R, s.dc_logits + PM_N_PITCH, PM_N_TOK, s.H + dh, d, c.G + Y.dec_dur.w, dh,
-                      nullptr, PM_GEMM_ACCUM, 0, skip ? s.ue_lists + 2 * R : nullptr, skip ? 1 : 0, skip ? s.ue_counts + 2 : nullptr, c.st));
-    for (int g = 0; g < 2; ++g) {
-      const int32_t* lst = skip ? s.ue_lists + g * R : pv.row_list + (g ? (int64_t)N * PM_N_SLOTS : 0);
-      RUN(pm_gemm_f32(1, 0, PM_N_PITCH, dh, (int)R, s.dc_logits, PM_N_TOK, s.H, d, c.G + pit[g].w, dh, nullptr,
-                        PM_GEMM_ACCUM, 0, lst, 1, skip ? s.ue_counts + g : pv.group_cnt + 2 + g, c.st));
-    }
-    }
-    if (s.ext_loss) {
-      // the caller's loss: the bias gradients of the three un-embeddings are the column sums of ITS d(logits) (with the
-      // step's own loss the fused un-embedding + cross-entropy kernel of the forward has already left them)
-      RUN(pm_unembed_bias_grads(s.dc_logits, s.bt.is_drum, N, S, c.G + Y.dec_pitch_d.b, c.G + Y.dec_pitch_nd.b, c.G + Y.dec_dur.b, c.st));
-    }
-    if (chord_tn) {
-      if (rows_tn_pays(d))                                          // dW[:S*d] += dH^T x_L, bias gradient (linear.hip)
-        RUN(pm_rows_tn_weight_grad(dH, S * d, S * d, s.dg.x[c.L], d, d, N, c.G + Y.dec_chord.w, d, c.G + Y.dec_chord.b, c.st));
-      else
-        lin_bwd(c, dH, s.dg.x[c.L], Y.dec_chord, N, S * d, d, nullptr);
-    }
-  };
-  if (chord_tn)     // dxL = dH @ W[:S*d, :] by the long-K kernel of linear.hip (weight rows as fragment-major planes, kind 1)
-    RUN(pm_rows_times_weight_longk(dH, S * d, N, S * d, s.wf_dec_t, 1, 0, d, dxL, d, c.st));
-  else
-    lin_bwd(c, dH, s.dg.x[c.L], Y.dec_chord, N, S * d, d, dxL);        // slots >= S: zero gradient (all PAD)
-  float* dx0 = gcn_backward(c, dxL, Y.dec_gcn, s.dg);
-  decoder_weight_grads();
+  if (rt.dec_dw_tn)                                     // dW[:S*d] += dH^T x_L, bias gradient (linear.hip)
+    RUN(pm_rows_tn_weight_grad(s.dH, S * d, S * d, s.dg.x[c.L], d, d, N, c.G + Y.dec_chord.w, d, c.G + Y.dec_chord.b, c.st));
+  else if (rt.dec_rows) lin_bwd(c, s.dH, s.dg.x[c.L], Y.dec_chord, N, S * d, d, nullptr);
+}
+// the chain behind the decoder's layers: bar broadcast, bars decoder, first layer, reparametrisation
+void decoder_trunk_backward(Ctx& c, float* dx0, float* dzr) {
+  StepState& s = *c.s; Arena& ar = s.ar; const PmVaeLayout& Y = s.lay;
+  const int N = c.N, Gn = c.Gn, B = c.B, d = c.d;
   float* dcb = ar.f((size_t)Gn * d);
   RUN(pm_bar_broadcast_bwd(dx0, s.plan, N, c.E, Gn, d, dcb, c.st));
   Deferred df;
   float* dzd = ar.zf((size_t)B * 2 * d);
   s.dz = ar.zf((size_t)B * d);
-  lin_bwd(c, dcb, s.zr_d + d, Y.dec_c_bars, B, nb * d, d, dzr + d, 0, 2 * d, 2 * d, true, &df);
+  lin_bwd(c, dcb, s.zr_d + d, Y.dec_c_bars, B, c.nb * d, d, dzr + d, 0, 2 * d, 2 * d, true, &df);
   branch_join(c, BR_DEC_BWD);
   drop(c, dzr, B, 2 * d, SITE_DEC_IN, s.seed_dec, dzr);           // backward of Decoder.dropout
   bn_bwd(c, s.zd, dzr, B, 2 * d, 1, Y.dec_bn, s.dm, s.dv, true, dzd);
@@ -1174,6 +1301,21 @@ void backward_decoder(Ctx& c) {
     BranchScope br(c, BR_DEC_WGRAD);                  // (joined by pm_vae_step_join_decoder_grads / the encoder backward)
     flush_deferred(c, df);
   }
+}
+void backward_decoder(Ctx& c) {
+  StepState& s = *c.s; const PmVaeLayout& Y = s.lay;
+  const int N = c.N, d = c.d, S = c.S;
+  float* dzr = s.ar.zf((size_t)c.B * 2 * d);
+  if (s.fix_structure) structure_decoder_backward(c, dzr);
+  unembed_input_grad(c);
+  float* dxL = s.ar.f((size_t)N * d);
+  if (s.head.dec_rows)  // dxL = dH @ W[:S*d, :] by the long-K kernel of linear.hip (weight rows as fragment-major planes, kind 1)
+    RUN(pm_rows_times_weight_longk(s.dH, S * d, N, S * d, s.wf_dec_t, 1, 0, d, dxL, d, c.st));
+  else
+    lin_bwd(c, s.dH, s.dg.x[c.L], Y.dec_chord, N, S * d, d, dxL);      // slots >= S: zero gradient (all PAD)
+  float* dx0 = gcn_backward(c, dxL, Y.dec_gcn, s.dg);
+  decoder_weight_grads(c);
+  decoder_trunk_backward(c, dx0, dzr);
 }
 
 // First part of the encoder backward: the head chain (mu / log_var heads, merge layer, bars encoder, attention pooling) and the
@@ -1220,13 +1362,11 @@ void backward_encoder_heads(Ctx& c) {
     RUN(pm_relu_bwd(dh1, s.h1, (int64_t)Gn * d, dh1, c.st));
     lin_bwd(c, dh1, s.a1d, Y.enc_lin1, Gn, d, 512, da1);
     drop(c, da1, Gn, 512, SITE_ENC_CNN_IN, s.seed_enc, da1);
-    if (c.bn) bn_bwd(c, s.c1, da1, Gn, 16, 32, Y.enc_bn5, s.m1, s.v1, true, dc1);
-    else RUN(pm_relu_bwd(da1, s.c1, (int64_t)Gn * 512, dc1, c.st));
+    cnn_act_bwd(c, s.c1, da1, Gn, 16, 32, Y.enc_bn5, s.m1, s.v1, dc1);
     RUN(pm_conv3x3_bwd_weight(s.p0, dc1, Gn, 8, 16, 4, 8, 0, c.G + Y.enc_conv4.w, c.G + Y.enc_conv4.b, c.st));
     RUN(pm_conv3x3_bwd_data(dc1, c.P + Y.enc_conv4.w, Gn, 8, 16, 4, 8, 0, dp0, c.st));
     RUN(pm_maxpool4_bwd(s.a0, dp0, (int64_t)Gn * 8 * 32, da0, c.st));
-    if (c.bn) bn_bwd(c, s.c0, da0, Gn, 8, 128, Y.enc_bn1, s.m0, s.v0, true, dc0);
-    else RUN(pm_relu_bwd(da0, s.c0, (int64_t)Gn * 8 * 128, dc0, c.st));
+    cnn_act_bwd(c, s.c0, da0, Gn, 8, 128, Y.enc_bn1, s.m0, s.v0, dc0);
     RUN(pm_conv3x3_bwd_weight(s.bt.s_tensor, dc0, Gn, 1, 8, 4, 32, 0, c.G + Y.enc_conv0.w, c.G + Y.enc_conv0.b, c.st));
   }
   // ---- content branch (z_c = zcat[:, :d])
@@ -1273,13 +1413,14 @@ void backward_encoder_tail(Ctx& c) {
   float* dx0 = s.bk_dx0;
   float* dzcat = s.bk_dzcat;
   const int S = c.S;
-  const bool chord_tab = s.chord_tab != 0;
+  const HeadRoute& rt = s.head;
+  const bool chord_tab = chord_tab_ok(c);
   float* dX = chord_tab ? nullptr : ar.f((size_t)N * S * d);
   // (table form: the token sums and the tables' sums only ever ADD — both live in the zero region the forward cleared)
   float* Stab = chord_tab ? ar.zf((size_t)4 * PM_N_PITCH * dh) : ar.f((size_t)4 * PM_N_PITCH * dh);
   float* gsum = ar.f((size_t)2 * d);
   float* Gt = chord_tab ? ar.zf((size_t)2 * S * 2 * PM_N_PITCH * d) : nullptr;
-  if (chord_tab) {
+  if (rt.chord == HeadRoute::CHORD_TABLES) {
     // token sums of dx0 per (group, slot, kind) on the matrix cores, then the weight / bias gradients and the tables' token
     // sums from them (chord.hip): no dX, no 10.7 GFLOP weight-gradient product.  Beside the token sums (second stream): the
     // closed-form tail slots; behind them the two small products side by side.
@@ -1295,11 +1436,11 @@ void backward_encoder_tail(Ctx& c) {
       RUN(pm_chord_tables_bwd_w(Gt, s.tables, d, S, c.G + Y.enc_chord.w, c.G + Y.enc_chord.b, c.st));
     }
     branch_join(c, BR_ENC_WGRAD);
-  } else if (S == PM_N_SLOTS) lin_bwd(c, dx0, s.X, Y.enc_chord, N, d, PM_N_SLOTS * d, dX);
+  } else if (rt.chord == HeadRoute::CHORD_FULL) lin_bwd(c, dx0, s.X, Y.enc_chord, N, d, PM_N_SLOTS * d, dX);
   else {               // active slots through the GEMMs (weight columns [0, S*d)), the all-PAD tail in closed form
     {                                        // (the weight gradient beside the input gradient: second stream, joined below)
       BranchScope br(c, BR_ENC_WGRAD);
-      if (s.wf_enc_t && rows_tn_pays(d))                      // d Wc[:, :S*d] += dx0^T X, d bias += column sums of dx0 (linear.hip)
+      if (rt.chord_dw_tn)                                     // d Wc[:, :S*d] += dx0^T X, d bias += column sums of dx0 (linear.hip)
         RUN(pm_rows_tn_weight_grad(dx0, d, d, s.X, S * d, S * d, N, c.G + Y.enc_chord.w, PM_N_SLOTS * d, c.G + Y.enc_chord.b, c.st));
       else {
         PmGemmDesc w;                        // d Wc[:, :S*d] += dx0^T X, d bias += column sums of dx0
@@ -1310,23 +1451,20 @@ void backward_encoder_tail(Ctx& c) {
         RUN(pm_gemm_f32_desc(&w, c.st));
       }
     }
-    if (s.wf_enc_t) {                                     // dX = dx0 @ Wc[:, :S*d], A-stationary
+    if (rt.chord == HeadRoute::CHORD_FRAG)                // dX = dx0 @ Wc[:, :S*d], A-stationary
       RUN(pm_rows_times_weight(dx0, d, N, d, s.wf_enc_t, 1, PM_N_SLOTS * d / 32, S * d, nullptr, dX, S * d, c.st));
-    } else
+    else
       RUN(pm_gemm_f32(0, 0, N, S * d, d, dx0, d, c.P + Y.enc_chord.w, PM_N_SLOTS * d, dX, S * d, nullptr, 0, 1, nullptr, 0,
                         nullptr, c.st));
   }
-  if (!chord_tab) {
+  if (rt.chord != HeadRoute::CHORD_TABLES) {
     RUN(pm_embed_bwd_scatter(dX, s.bt.tokens, s.plan, N, c.E, Gn, d, S, Stab, c.st));
     RUN(pm_chord_pad_bwd(dx0, s.bt.is_drum, N, d, S, s.tables, c.P + Y.enc_chord.w, gsum, c.G + Y.enc_chord.w, Stab, c.st));
   }
   PmPlanView pv = pm_plan_view(s.plan, N, c.E, Gn);
   RUN(pm_embed_tables_bwd(Stab, c.P + Y.enc_pitch_d.w, c.P + Y.enc_pitch_d.b, c.P + Y.enc_pitch_nd.w, c.P + Y.enc_pitch_nd.b,
                             c.P + Y.enc_dur.w, c.P + Y.enc_dur.b, c.P + Y.enc_bn_d.w, c.P + Y.enc_bn_nd.w,
-                            c.P + Y.enc_bn_dur.w, s.emb_stats, pv.tok_hist, d, 1e-5f, c.G + Y.enc_pitch_d.w,
-                            c.G + Y.enc_pitch_d.b, c.G + Y.enc_pitch_nd.w, c.G + Y.enc_pitch_nd.b, c.G + Y.enc_dur.w,
-                            c.G + Y.enc_dur.b, c.G + Y.enc_bn_d.w, c.G + Y.enc_bn_d.b, c.G + Y.enc_bn_nd.w,
-                            c.G + Y.enc_bn_nd.b, c.G + Y.enc_bn_dur.w, c.G + Y.enc_bn_dur.b, c.st));
+                            c.P + Y.enc_bn_dur.w, s.emb_stats, pv.tok_hist, d, 1e-5f, EMB_PARAMS(c.G), c.st));
   branch_join(c, BR_ENC_WGRAD);
   branch_join(c, BR_ENC_BWD);                        // the structure branch issued by backward_encoder
 }
@@ -1446,11 +1584,12 @@ extern "C" int pm_vae_step_info(const void* state, int32_t* info) {
   info[3] = (s->eg.rt.frag && s->dg.rt.frag) ? 1 : 0;          // fragment-major weight planes built (B-direct GEMM mode available)
   info[4] = c.N; info[5] = c.E; info[6] = c.Gn; info[7] = c.B;
   // the EFFECTIVE switches (read from the environment at load / pm_vae_step_reload_switches, not at call time)
-  info[8] = cfg().fused_ce ? 1 : 0; info[9] = pm_det_on() ? 0 : cfg().side_stream; info[10] = pm_det_on(); info[11] = cfg().gcl_fused ? 1 : 0;
-  info[12] = cfg().dagg_bn ? 1 : 0;            // (the norm backward of the GCN layers inside the input gradient kernel)
-  info[13] = s->chord_tab;                      // (the chord encoder as table algebra)
+  const HeadRoute& rt = s->head;
+  info[8] = rt.sw_fused_ce ? 1 : 0; info[9] = pm_det_on() ? 0 : rt.side_mask; info[10] = pm_det_on(); info[11] = rt.sw_gcl_fused ? 1 : 0;
+  info[12] = rt.sw_dagg_bn ? 1 : 0;            // (the norm backward of the GCN layers inside the input gradient kernel)
+  info[13] = rt.chord == HeadRoute::CHORD_TABLES ? 1 : 0;      // (the chord encoder as table algebra)
   info[14] = (s->eg.rt.h2 ? 1 : 0) | (s->dg.rt.h2 ? 2 : 0);     // (the GCL products of the encoder / decoder stack in the fp16 pair format)
-  info[15] = s->pad_skip;                       // (the decoder head ran over the row lists without PAD targets)
+  info[15] = rt.ue_rows ? 1 : 0;                // (the decoder head ran over the row lists without PAD targets)
   return PM_OK;
 }
 // Model outputs of the last forward (the arena keeps them until the next pm_vae_step_forward): asynchronous
@@ -1464,8 +1603,7 @@ extern "C" int pm_vae_step_outputs(const void* state, float* s_logits, float* c_
   const size_t N = s->bt.N, S = s->bt.n_slots, G = s->bt.G, B = s->bt.B, d = s->lay.d;
   hipError_t e = hipSuccess;
   if (s_logits && e == hipSuccess) e = hipMemcpyAsync(s_logits, s->s_logits, sizeof(float) * G * 128, hipMemcpyDeviceToDevice, st);
-  const bool fused_ce = cfg().fused_ce;
-  if (c_logits && fused_ce && !(s->bt.flags & (4 | 8))) return PM_E_INVALID;      // the step was told not to keep the logits
+  if (c_logits && s->head.ue_fwd == HeadRoute::UE_KERNEL && !s->head.keep_logits) return PM_E_INVALID;   // the step was told not to keep the logits
   if (c_logits && e == hipSuccess) e = hipMemcpyAsync(c_logits, s->c_logits, sizeof(float) * N * S * PM_N_TOK, hipMemcpyDeviceToDevice, st);
   if (mu && e == hipSuccess) e = hipMemcpyAsync(mu, s->mu, sizeof(float) * B * d, hipMemcpyDeviceToDevice, st);
   if (log_var && e == hipSuccess) e = hipMemcpyAsync(log_var, s->lv, sizeof(float) * B * d, hipMemcpyDeviceToDevice, st);
@@ -1501,7 +1639,7 @@ extern "C" int pm_vae_step_set_output_grads(void* state, const float* d_s_logits
   if (e == hipSuccess) e = hipMemsetAsync(s->G + Y.dec_dur.b, 0, sizeof(float) * PM_N_DUR, st);
   s->fix_structure = d_s_logits ? 1 : 0;
   s->ext_loss = 1;
-  s->pad_skip = 0;                                      // (the caller's d(c_logits) may be non-zero in any row)
+  head_route_gradient_in_any_row(s->head);
   return e == hipSuccess ? PM_OK : PM_E_LAUNCH;
 }
 

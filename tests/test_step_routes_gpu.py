@@ -3,7 +3,8 @@ once and compared from then on (tests/golden/step_routes.json; `python tests/tes
 
 csrc/vae_step.hip decides on the host which kernels a GCN stack takes (fused GCL kernels, bar-resident aggregation, grouped planes
 products, the 7-block product; the fp16 pair format; where the norm backward and the residual ride).  A change that only
-re-organises those decisions must leave every row of the table as it is.  Observed per case, on one step of a small batch
+re-organises those decisions must leave every row of the table as it is.  The same holds for the chains around the stacks
+(chord encoder, chord decoder, un-embedding: the head cases of `_cases`).  Observed per case, on one step of a small batch
 (n_bars = 2, L = 2, message dropout 0.1, the default seed of `synthetic_batch`):
 
     the 40 launch-class counts of the in-library profiler (GEMM classes, both segment-reduce directions, the three GCL kernels,
@@ -49,6 +50,19 @@ def _cases():
             ("d512_dense_det", dict(DENSE, d=512), True, {})]
     out += [(f"d256_sparse_{k}={v}", dict(SPARSE, d=256), False, {k: v}) for k, v in SWITCH_ROWS]
     out += [(f"d512_dense_{k}={v}", dict(DENSE, d=512), False, {k: v}) for k, v in (("PM_BAR_ROUTE", 0), ("PM_H2", 0))]
+    # the head's decisions (chord encoder / decoder, un-embedding): the bench's head stores no logits; the structure loss on the
+    # logits; the accuracy counts; all 15 slots (the full-width chord products); the chord encoder per width without the tables
+    s256 = dict(SPARSE, d=256)
+    out += [("d256_sparse_keep_logits_off", dict(s256, keep_logits=False), False, {}),
+            ("d256_sparse_keep_logits_off_PM_PAD_SKIP=0", dict(s256, keep_logits=False), False, {"PM_PAD_SKIP": 0}),
+            ("d256_sparse_fix_structure", dict(s256, fix_structure=True), False, {}),
+            ("d256_sparse_metrics", dict(s256, train_metrics=True), False, {}),
+            ("d256_sparse_metrics_PM_FUSED_CE=0", dict(s256, train_metrics=True), False, {"PM_FUSED_CE": 0}),
+            ("d256_sparse_all_slots", dict(s256, n_slots=15), False, {}),
+            ("d256_sparse_all_slots_PM_CHORD_TABLES=0", dict(s256, n_slots=15), False, {"PM_CHORD_TABLES": 0}),
+            ("d512_sparse_PM_CHORD_TABLES=0", dict(SPARSE, d=512), False, {"PM_CHORD_TABLES": 0}),
+            ("d128_sparse_PM_CHORD_TABLES=0", dict(SPARSE, d=128), False, {"PM_CHORD_TABLES": 0}),
+            ("d256_sparse_dropout_fix_structure", dict(s256, dropout=0.1, fix_structure=True), False, {})]
     return out
 
 

@@ -313,7 +313,9 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     """One native HIP training step (the measured variant) on the synthetic batch of `spec`, default-init weights under
     manual_seed(0) and a fixed eps: model outputs, losses, gradients, the step variant, and what the oracle needs to
     replay it (batch, state dict, eps, the two dropout seeds).  Optional keys of `spec`: `dropout` (0), `batch_norm` (True) — the
-    model's constructor switches — and `track_unique` (what the batch carries; False: the 7-block aggregates)."""
+    model's constructor switches —, `track_unique` (what the batch carries; False: the 7-block aggregates), `n_slots` (the token
+    slots the batch declares active), `train_metrics` (False: the trainer's accuracy counts) and `keep_logits` (True; False is the
+    bench's head — the logits are not stored, `step_outputs()` is skipped and `outputs` is None)."""
     import time
     from polyphemus_amd.model import VAE
     from polyphemus_amd.synthetic import synthetic_batch
@@ -323,6 +325,8 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     cpu = synthetic_batch(spec["B"], spec["nb"], p=spec["p"], seed=spec["seed"], dense=spec["dense"])
     if "track_unique" in spec:
         cpu.track_unique = bool(spec["track_unique"])
+    if "n_slots" in spec:
+        cpu.n_slots = int(spec["n_slots"])
     torch.manual_seed(0)
     vae = VAE(**cfg, device=dev).to(dev)
     vae.train()
@@ -330,8 +334,9 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     sd = {k: v.detach().cpu().clone() for k, v in vae.state_dict().items()}
     names = [n for n, _ in vae.named_parameters()]
     eps = torch.randn(spec["B"], spec["d"], generator=torch.Generator().manual_seed(99))
-    tr = HipTrainer(vae, lr=lr, structure_loss_on_logits=bool(spec.get("fix_structure", False)))
-    tr.keep_logits = True
+    tr = HipTrainer(vae, lr=lr, structure_loss_on_logits=bool(spec.get("fix_structure", False)),
+                    train_metrics=bool(spec.get("train_metrics", False)))
+    tr.keep_logits = bool(spec.get("keep_logits", True))
     step0 = vae._step
     t0 = time.time()
     # launch-class counters of the in-library profiler: WHICH kernels the step took (35 / 36 / 37 = the three GCL kernels of
@@ -348,14 +353,15 @@ def hip_fullsize_step(spec, dev="cuda", lr=5e-6, keep=None):
     clamps = _lm.h2_clamp_events()
     ms, work, cnt = (ctypes.c_double * 64)(), (ctypes.c_double * 64)(), (ctypes.c_int64 * 64)()
     L.pm_prof_end(*(ctypes.cast(a, ctypes.c_void_p) for a in (ms, work, cnt)))
-    (s_h, c_h), mu_h, lv_h = tr.step_outputs()
+    if tr.keep_logits:
+        (s_h, c_h), mu_h, lv_h = tr.step_outputs()
     info = tr.step_info()
     info["h2_clamp_events"] = clamps              # threads of the pair-format splits that saturated in this step (must be 0)
     info["launches"] = {"gcl_fwd": int(cnt[35]), "gcl_dagg": int(cnt[36]), "gcl_dw": int(cnt[37]), "rows_w": int(cnt[38]), "rows_tn": int(cnt[39]),
                         "planesB_nn": int(cnt[27]), "planesB_nt": int(cnt[28]), "planes_tn": int(cnt[26]),
                         "segreduce_fwd": int(cnt[33]), "segreduce_bwd": int(cnt[34])}
     info["launch_counts"] = [int(cnt[i]) for i in range(PROF_CLASSES)]     # every launch class of the profiler, in its order
-    hip = dict(s_logits=s_h.cpu(), c_logits=c_h.cpu(), mu=mu_h.cpu(), log_var=lv_h.cpu())
+    hip = dict(s_logits=s_h.cpu(), c_logits=c_h.cpu(), mu=mu_h.cpu(), log_var=lv_h.cpu()) if tr.keep_logits else None
     hip_g = {n: tr._G[n].detach().cpu() for n in names}
     t_hip = time.time() - t0
     vae._step = step0
