@@ -733,6 +733,32 @@ int pm_conv3x3_bwd_weight(const float* x, const float* dy, int32_t G, int32_t Ci
                           int up4, float* dw /* += */, float* db /* += */, pm_stream_t stream);
 int pm_maxpool4_fwd(const float* x, int64_t n_out, float* y, pm_stream_t stream);
 int pm_maxpool4_bwd(const float* x, const float* dy, int64_t n_out, float* dx, pm_stream_t stream);
+/* The conv / norm / pool chains of the model's CNNs in training mode (BatchNorm2d on batch statistics), bar resident: a
+ * workgroup keeps its bars in LDS between the launch boundaries that the batch statistics force.  Fixed shapes: s [G,1,4,32],
+ * c0 / a0 [G,8,4,32], p0 [G,8,4,8], c1 / a1 [G,16,4,8]; u2 [G,16,4,8], c2 / a2 [G,8,4,32], s_logits [G,1,4,32].  Convolution
+ * outputs have the bits of pm_conv3x3_fwd on the same input; statistics are fp64 partial sums per workgroup in `scratch`
+ * (`scratch_len` doubles: the grid is sized to it, at most 256 workgroups of 48 / 16 / 1296 doubles), added in a fixed order: no
+ * float atomics, the same bits in every run and in both modes.  mean* / var* [C] are written (saved for the backward), rmean* / rvar* (or NULL)
+ * updated with `momentum`, as pm_bn_stats does.  c0, a0, c1, a1, c2, a2, da0, dc0: 16-byte aligned.
+ * Structure encoder forward, CNNEncoder.conv (model.py:219-230): conv0, BN1, ReLU, MaxPool2d((1,4)), conv4, BN5, ReLU.  3 launches. */
+int pm_cnn_enc_fwd(const float* s, const float* w0 /* [8,1,3,3] */, const float* b0, const float* gamma1, const float* beta1,
+                   const float* w4 /* [16,8,3,3] */, const float* b4, const float* gamma5, const float* beta5, int32_t G, float eps,
+                   float momentum, float* c0, float* a0, float* p0, float* c1, float* a1, float* mean1, float* var1,
+                   float* rmean1, float* rvar1, float* mean5, float* var5, float* rmean5, float* rvar5, double* scratch,
+                   int64_t scratch_len, pm_stream_t stream);
+/* Structure decoder forward, CNNDecoder.conv (model.py:279-285): Upsample((1,4)), conv1, BN2, ReLU, conv4.  2 launches. */
+int pm_cnn_dec_fwd(const float* u2, const float* w1 /* [8,16,3,3] */, const float* b1, const float* gamma2, const float* beta2,
+                   const float* w4 /* [1,8,3,3] */, const float* b4, int32_t G, float eps, float momentum, float* c2, float* a2,
+                   float* s_logits, float* mean2, float* var2, float* rmean2, float* rvar2, double* scratch, int64_t scratch_len,
+                   pm_stream_t stream);
+/* Backward of pm_cnn_enc_fwd (the autograd of model.py:219-230) from da1 = d(loss)/d(a1): dw*, db*, dgamma*, dbeta* += (each
+ * element once, from fp64 sums over the workgroups' partials in `scratch`, conv0's by a one-workgroup launch of its own); da0 [G,8,4,32] is written; dc1 [G,16,4,8] and dc0 [G,8,4,32] are written when not NULL (the input has
+ * no gradient).  4 launches. */
+int pm_cnn_enc_bwd(const float* s, const float* c0, const float* a0, const float* p0, const float* c1, const float* da1,
+                   const float* mean1, const float* var1, const float* gamma1, const float* beta1, const float* mean5,
+                   const float* var5, const float* gamma5, const float* beta5, const float* w4, int32_t G, float eps, float* dw0,
+                   float* db0, float* dgamma1, float* dbeta1, float* dw4, float* db4, float* dgamma5, float* dbeta5, float* dc1,
+                   float* da0, float* dc0, double* scratch, int64_t scratch_len, pm_stream_t stream);
 
 /* ------------------------------------------------------------------ loss (training.py:298-347)
  * Fused softmax cross-entropy of the pitch (131, ignore 130) and duration (99, ignore 98)

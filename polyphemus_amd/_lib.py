@@ -100,6 +100,9 @@ _SIGS = {
     "pm_conv3x3_bwd_weight": "ppiiiiiipps",
     "pm_maxpool4_fwd": "plps",
     "pm_maxpool4_bwd": "pplps",
+    "pm_cnn_enc_fwd": "pppppppppiffppppppppppppppls",
+    "pm_cnn_dec_fwd": "pppppppiffppppppppls",
+    "pm_cnn_enc_bwd": "pppppppppppppppifppppppppppppls",
     "pm_content_ce": "ppppiifppppps",
     "pm_content_ce_scaled": "ppppiifpppppps",
     "pm_unembed_ce": "pppppppppiiiiifpppppppps",

@@ -39,6 +39,8 @@ namespace {
 //   PM_FUSED_CE=0       three un-embedding products + the loss kernel instead of the fused un-embedding / cross-entropy kernel
 //   PM_SIDE_STREAM=m    bit mask of the branch sites (BR_* below) issued on the library's second stream (default: all;
 //                       0: everything on the caller's stream);  PM_SIDE_DELAY_US=n (tests): every branch starts n us late
+//   PM_CNN_FUSED=0      the structure CNNs' conv / norm / pool chains as generic launches (cnn.hip, norm.hip: 9 + 5 + 10) instead of
+//                       the bar-resident kernels of cnn.hip (3 + 2 + 4) — the parity test's reference
 //   PM_DAGG_BN=0, PM_DAGG_RES=0, PM_PLAN_SIDE=0, PM_CHORD_TABLES=0, PM_H2=0, PM_BAR_ROUTE=0, PM_PAD_SKIP=0, PM_UNEMBED_DW=0, PM_SENC_FIRST=0: see
 //                       the fields of StepCfg
 //   PM_GCL_OFFSET_LIMIT=n, PM_DEBUG
@@ -63,6 +65,7 @@ struct StepCfg {
   bool senc_first;             // PM_SENC_FIRST=0: the decoder's weight preparation ahead of the structure encoder on the second stream (rounds 3-5)
   bool unembed_dw;             // PM_UNEMBED_DW=0: the un-embedding weight gradients as three split-K products of the fp32 tile GEMM (rounds 2-5)
   bool pad_skip;               // PM_PAD_SKIP=0: the decoder head over every (node, active slot) row, PAD targets included (rounds 2-5)
+  bool cnn_fused;              // PM_CNN_FUSED=0: see above
   bool bar_route;              // PM_BAR_ROUTE=0: dense graphs on the row-gather kernels of segreduce.hip (rounds 1-5) instead of bar.hip
   int64_t offset_limit;        // PM_GCL_OFFSET_LIMIT: operand bytes up to which the 32-bit-offset kernels are used (tests lower it)
 };
@@ -86,6 +89,7 @@ static StepCfg read_cfg() {
   k.pad_skip = flag("PM_PAD_SKIP", true);
   k.unembed_dw = flag("PM_UNEMBED_DW", true);
   k.senc_first = flag("PM_SENC_FIRST", true);
+  k.cnn_fused = flag("PM_CNN_FUSED", true);
   k.offset_limit = getenv("PM_GCL_OFFSET_LIMIT") ? atoll(getenv("PM_GCL_OFFSET_LIMIT")) : 0x7fffffffLL;
   return k;
 }
@@ -169,6 +173,9 @@ struct HeadRoute {
   bool ue_rows;                          // ... over the row lists without the PAD targets (pm_unembed_row_lists; PM_PAD_SKIP): all three directions
   bool keep_logits;                      // PmBatch.flags bit 2, the caller wants every logit: with ue_rows, a second forward pass over the PAD rows
   bool logits_only;                      // PmBatch.flags bit 3, the caller computes the loss: logits by the products, no loss kernel
+  // structure CNNs, the conv / norm / pool chains of encoder forward, decoder forward and encoder backward: the bar-resident kernels
+  // (pm_cnn_enc_fwd / pm_cnn_dec_fwd / pm_cnn_enc_bwd: the model's fixed shapes with norms) | generic convolution, pool and norm launches
+  bool cnn_fused;
   bool metrics;                          // the training accuracies are armed (pm_vae_step_set_metrics): the metrics form of the forward
   // placement: the plan build on the second stream | the encoder's weight preparation on the caller's stream (in front of its
   // wait for the plan) | the structure encoder ahead of the decoder's preparation on the second stream
@@ -516,6 +523,7 @@ HeadRoute head_route(const Ctx& c) {
   r.plan_side = k.plan_side;
   r.prep_main = r.chord == HeadRoute::CHORD_TABLES && r.plan_side;
   r.senc_first = k.senc_first;
+  r.cnn_fused = k.cnn_fused && c.bn;
   r.ue_fwd = (fused_ce_on() && !r.logits_only) ? HeadRoute::UE_KERNEL : HeadRoute::UE_PRODUCTS;
   r.ue_dh = unembed_dh_ok(c) ? HeadRoute::UE_KERNEL : HeadRoute::UE_PRODUCTS;
   // (the lists are built on the second stream behind the plan; off when the caller supplies the loss)
@@ -836,6 +844,8 @@ void cnn_act_fwd(Ctx& c, const float* x, int O, int C, int I, PmBn bn, float* y,
   if (c.bn) bn_fwd(c, x, O, C, I, bn, true, nullptr, y, mean, var);
   else RUN(pm_relu_residual_fwd(x, nullptr, (int64_t)O * C * I, y, c.st));
 }
+// doubles in each of the step's two norm scratches (forward(): bn_scratch, bn_scratch_side) — what the fused CNN chains size their grids to
+int64_t bn_scratch_len(const Ctx& c) { return (int64_t)PM_BN_SCRATCH(2 * c.d > 16 ? 2 * c.d : 16); }
 void cnn_act_bwd(Ctx& c, const float* x, const float* dy, int O, int C, int I, PmBn bn, const float* mean, const float* var, float* dx) {
   if (c.bn) bn_bwd(c, x, dy, O, C, I, bn, mean, var, true, dx);
   else RUN(pm_relu_bwd(dy, x, (int64_t)O * C * I, dx, c.st));
@@ -1022,11 +1032,18 @@ void structure_encoder(Ctx& c, BranchScope& br) {
   StepState& s = *c.s; const PmVaeLayout& Y = s.lay;
   const int Gn = c.Gn, d = c.d, nb = c.nb;
   if (s.ar.base) {
-    RUN(pm_conv3x3_fwd(s.bt.s_tensor, c.P + Y.enc_conv0.w, c.P + Y.enc_conv0.b, Gn, 1, 8, 4, 32, 0, s.c0, c.st));
-    cnn_act_fwd(c, s.c0, Gn, 8, 128, Y.enc_bn1, s.a0, s.m0, s.v0);
-    RUN(pm_maxpool4_fwd(s.a0, (int64_t)Gn * 8 * 32, s.p0, c.st));
-    RUN(pm_conv3x3_fwd(s.p0, c.P + Y.enc_conv4.w, c.P + Y.enc_conv4.b, Gn, 8, 16, 4, 8, 0, s.c1, c.st));
-    cnn_act_fwd(c, s.c1, Gn, 16, 32, Y.enc_bn5, s.a1, s.m1, s.v1);
+    if (s.head.cnn_fused) {
+      RUN(pm_cnn_enc_fwd(s.bt.s_tensor, c.P + Y.enc_conv0.w, c.P + Y.enc_conv0.b, c.P + Y.enc_bn1.w, c.P + Y.enc_bn1.b,
+                           c.P + Y.enc_conv4.w, c.P + Y.enc_conv4.b, c.P + Y.enc_bn5.w, c.P + Y.enc_bn5.b, Gn, 1e-5f, 0.1f, s.c0, s.a0,
+                           s.p0, s.c1, s.a1, s.m0, s.v0, c.Bf + Y.enc_bn1.rm, c.Bf + Y.enc_bn1.rv, s.m1, s.v1, c.Bf + Y.enc_bn5.rm,
+                           c.Bf + Y.enc_bn5.rv, c.bn_scratch, bn_scratch_len(c), c.st));
+    } else {
+      RUN(pm_conv3x3_fwd(s.bt.s_tensor, c.P + Y.enc_conv0.w, c.P + Y.enc_conv0.b, Gn, 1, 8, 4, 32, 0, s.c0, c.st));
+      cnn_act_fwd(c, s.c0, Gn, 8, 128, Y.enc_bn1, s.a0, s.m0, s.v0);
+      RUN(pm_maxpool4_fwd(s.a0, (int64_t)Gn * 8 * 32, s.p0, c.st));
+      RUN(pm_conv3x3_fwd(s.p0, c.P + Y.enc_conv4.w, c.P + Y.enc_conv4.b, Gn, 8, 16, 4, 8, 0, s.c1, c.st));
+      cnn_act_fwd(c, s.c1, Gn, 16, 32, Y.enc_bn5, s.a1, s.m1, s.v1);
+    }
     s.a1d = drop(c, s.a1, Gn, 512, SITE_ENC_CNN_IN, s.seed_enc, s.dbuf.a1);                 // CNNEncoder.lin[0], model.py:244
     lin(c, s.a1d, Y.enc_lin1, Gn, d, 512, s.h1, true);
     s.h1d = drop(c, s.h1, Gn, d, SITE_ENC_CNN_MID, s.seed_enc, s.dbuf.h1);                  // CNNEncoder.lin[3], model.py:247
@@ -1125,6 +1142,12 @@ void structure_decoder(Ctx& c) {
   lin(c, s.sbd, Y.dec_s_lin1, Gn, d, d, s.u1, true);
   s.u1d = drop(c, s.u1, Gn, d, SITE_DEC_CNN_MID, s.seed_dec, s.dbuf.u1);                     // CNNDecoder.lin[3], model.py:270
   lin(c, s.u1d, Y.dec_s_lin4, Gn, 512, d, s.u2, true);
+  if (s.head.cnn_fused) {
+    RUN(pm_cnn_dec_fwd(s.u2, c.P + Y.dec_conv1.w, c.P + Y.dec_conv1.b, c.P + Y.dec_bn2.w, c.P + Y.dec_bn2.b, c.P + Y.dec_conv4.w,
+                         c.P + Y.dec_conv4.b, Gn, 1e-5f, 0.1f, s.c2, s.a2, s.s_logits, s.m2, s.v2, c.Bf + Y.dec_bn2.rm,
+                         c.Bf + Y.dec_bn2.rv, c.bn_scratch, bn_scratch_len(c), c.st));
+    return;
+  }
   RUN(pm_conv3x3_fwd(s.u2, c.P + Y.dec_conv1.w, c.P + Y.dec_conv1.b, Gn, 16, 8, 4, 32, 1, s.c2, c.st));
   cnn_act_fwd(c, s.c2, Gn, 8, 128, Y.dec_bn2, s.a2, s.m2, s.v2);
   RUN(pm_conv3x3_fwd(s.a2, c.P + Y.dec_conv4.w, c.P + Y.dec_conv4.b, Gn, 8, 1, 4, 32, 0, s.s_logits, c.st));
@@ -1194,8 +1217,8 @@ void forward(Ctx& c, float msg_p, uint32_t seed_enc, uint32_t seed_dec) {
   const bool run = ar.base != nullptr;
   s.seed_enc = seed_enc; s.seed_dec = seed_dec;
   s.head = head_route(c);
-  s.bn_scratch = ar.dbl((size_t)PM_BN_SCRATCH(2 * c.d > 16 ? 2 * c.d : 16));
-  s.bn_scratch_side = ar.dbl((size_t)PM_BN_SCRATCH(2 * c.d > 16 ? 2 * c.d : 16));
+  s.bn_scratch = ar.dbl((size_t)bn_scratch_len(c));
+  s.bn_scratch_side = ar.dbl((size_t)bn_scratch_len(c));
   c.bn_scratch = s.bn_scratch;
   carve_structure_encoder(c);
   // Second stream (forked here, at the very start of the step): everything that depends on the parameters only — first what
@@ -1362,12 +1385,19 @@ void backward_encoder_heads(Ctx& c) {
     RUN(pm_relu_bwd(dh1, s.h1, (int64_t)Gn * d, dh1, c.st));
     lin_bwd(c, dh1, s.a1d, Y.enc_lin1, Gn, d, 512, da1);
     drop(c, da1, Gn, 512, SITE_ENC_CNN_IN, s.seed_enc, da1);
-    cnn_act_bwd(c, s.c1, da1, Gn, 16, 32, Y.enc_bn5, s.m1, s.v1, dc1);
-    RUN(pm_conv3x3_bwd_weight(s.p0, dc1, Gn, 8, 16, 4, 8, 0, c.G + Y.enc_conv4.w, c.G + Y.enc_conv4.b, c.st));
-    RUN(pm_conv3x3_bwd_data(dc1, c.P + Y.enc_conv4.w, Gn, 8, 16, 4, 8, 0, dp0, c.st));
-    RUN(pm_maxpool4_bwd(s.a0, dp0, (int64_t)Gn * 8 * 32, da0, c.st));
-    cnn_act_bwd(c, s.c0, da0, Gn, 8, 128, Y.enc_bn1, s.m0, s.v0, dc0);
-    RUN(pm_conv3x3_bwd_weight(s.bt.s_tensor, dc0, Gn, 1, 8, 4, 32, 0, c.G + Y.enc_conv0.w, c.G + Y.enc_conv0.b, c.st));
+    if (s.head.cnn_fused) {                             // (dc1, dp0, dc0 stay carved: the workspace is the same on both routes)
+      RUN(pm_cnn_enc_bwd(s.bt.s_tensor, s.c0, s.a0, s.p0, s.c1, da1, s.m0, s.v0, c.P + Y.enc_bn1.w, c.P + Y.enc_bn1.b, s.m1, s.v1,
+                           c.P + Y.enc_bn5.w, c.P + Y.enc_bn5.b, c.P + Y.enc_conv4.w, Gn, 1e-5f, c.G + Y.enc_conv0.w, c.G + Y.enc_conv0.b,
+                           c.G + Y.enc_bn1.w, c.G + Y.enc_bn1.b, c.G + Y.enc_conv4.w, c.G + Y.enc_conv4.b, c.G + Y.enc_bn5.w,
+                           c.G + Y.enc_bn5.b, nullptr, da0, nullptr, c.bn_scratch, bn_scratch_len(c), c.st));
+    } else {
+      cnn_act_bwd(c, s.c1, da1, Gn, 16, 32, Y.enc_bn5, s.m1, s.v1, dc1);
+      RUN(pm_conv3x3_bwd_weight(s.p0, dc1, Gn, 8, 16, 4, 8, 0, c.G + Y.enc_conv4.w, c.G + Y.enc_conv4.b, c.st));
+      RUN(pm_conv3x3_bwd_data(dc1, c.P + Y.enc_conv4.w, Gn, 8, 16, 4, 8, 0, dp0, c.st));
+      RUN(pm_maxpool4_bwd(s.a0, dp0, (int64_t)Gn * 8 * 32, da0, c.st));
+      cnn_act_bwd(c, s.c0, da0, Gn, 8, 128, Y.enc_bn1, s.m0, s.v0, dc0);
+      RUN(pm_conv3x3_bwd_weight(s.bt.s_tensor, dc0, Gn, 1, 8, 4, 32, 0, c.G + Y.enc_conv0.w, c.G + Y.enc_conv0.b, c.st));
+    }
   }
   // ---- content branch (z_c = zcat[:, :d])
   lin_bwd(c, dzcat, s.pooled, Y.enc_c_bars, B, d, nb * d, dpooled, 2 * d, nb * d, nb * d, true, &df);

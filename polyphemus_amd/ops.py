@@ -633,6 +633,52 @@ def maxpool4_bwd(x, dy):
     return dx
 
 
+# ---- the training step's CNN chains as bar-resident kernels (model.py:219-230 / 279-285 with BatchNorm2d on batch statistics) ----
+def cnn_enc_fwd(s, w0, b0, gamma1, beta1, w4, b4, gamma5, beta5, G, rmean1=None, rvar1=None, rmean5=None, rvar5=None,
+                eps=1e-5, momentum=0.1, scratch=None):
+    """conv0, BN1, ReLU, pool (1,4), conv4, BN5, ReLU over s [G,1,4,32]: dict of c0, a0, p0, c1, a1 and the saved mean / var
+    of the two norms (m0, v0, m1, v1); the running statistics are updated in place."""
+    dev = s.device
+    o = {"c0": torch.empty(G, 8, 4, 32, dtype=F32, device=dev), "a0": torch.empty(G, 8, 4, 32, dtype=F32, device=dev),
+         "p0": torch.empty(G, 8, 4, 8, dtype=F32, device=dev), "c1": torch.empty(G, 16, 4, 8, dtype=F32, device=dev),
+         "a1": torch.empty(G, 16, 4, 8, dtype=F32, device=dev), "m0": torch.empty(8, dtype=F32, device=dev),
+         "v0": torch.empty(8, dtype=F32, device=dev), "m1": torch.empty(16, dtype=F32, device=dev),
+         "v1": torch.empty(16, dtype=F32, device=dev)}
+    scratch = scratch if scratch is not None else bn_scratch(512, dev)      # (the step's at d = 256)
+    call("pm_cnn_enc_fwd", ptr(s), ptr(w0), ptr(b0), ptr(gamma1), ptr(beta1), ptr(w4), ptr(b4), ptr(gamma5), ptr(beta5), G, eps,
+         momentum, ptr(o["c0"]), ptr(o["a0"]), ptr(o["p0"]), ptr(o["c1"]), ptr(o["a1"]), ptr(o["m0"]), ptr(o["v0"]), ptr(rmean1),
+         ptr(rvar1), ptr(o["m1"]), ptr(o["v1"]), ptr(rmean5), ptr(rvar5), ptr(scratch), scratch.numel(), stream())
+    return o
+
+
+def cnn_dec_fwd(u2, w1, b1, gamma2, beta2, w4, b4, G, rmean2=None, rvar2=None, eps=1e-5, momentum=0.1, scratch=None):
+    """upsample (1,4), conv1, BN2, ReLU, conv4 over u2 [G,16,4,8]: dict of c2, a2, s_logits and the norm's saved m2, v2."""
+    dev = u2.device
+    o = {"c2": torch.empty(G, 8, 4, 32, dtype=F32, device=dev), "a2": torch.empty(G, 8, 4, 32, dtype=F32, device=dev),
+         "s_logits": torch.empty(G, 1, 4, 32, dtype=F32, device=dev), "m2": torch.empty(8, dtype=F32, device=dev),
+         "v2": torch.empty(8, dtype=F32, device=dev)}
+    scratch = scratch if scratch is not None else bn_scratch(512, dev)      # (the step's at d = 256)
+    call("pm_cnn_dec_fwd", ptr(u2), ptr(w1), ptr(b1), ptr(gamma2), ptr(beta2), ptr(w4), ptr(b4), G, eps, momentum, ptr(o["c2"]),
+         ptr(o["a2"]), ptr(o["s_logits"]), ptr(o["m2"]), ptr(o["v2"]), ptr(rmean2), ptr(rvar2), ptr(scratch), scratch.numel(),
+         stream())
+    return o
+
+
+def cnn_enc_bwd(s, fwd, da1, gamma1, beta1, gamma5, beta5, w4, G, dw0, db0, dgamma1, dbeta1, dw4, db4, dgamma5, dbeta5,
+                eps=1e-5, scratch=None):
+    """Backward of cnn_enc_fwd (`fwd`: its dict) from da1 [G,16,4,8]: the eight gradients accumulate (+=); returns dc1, da0, dc0."""
+    dev = s.device
+    dc1 = torch.empty(G, 16, 4, 8, dtype=F32, device=dev)
+    da0 = torch.empty(G, 8, 4, 32, dtype=F32, device=dev)
+    dc0 = torch.empty(G, 8, 4, 32, dtype=F32, device=dev)
+    scratch = scratch if scratch is not None else bn_scratch(512, dev)      # (the step's at d = 256)
+    call("pm_cnn_enc_bwd", ptr(s), ptr(fwd["c0"]), ptr(fwd["a0"]), ptr(fwd["p0"]), ptr(fwd["c1"]), ptr(da1), ptr(fwd["m0"]),
+         ptr(fwd["v0"]), ptr(gamma1), ptr(beta1), ptr(fwd["m1"]), ptr(fwd["v1"]), ptr(gamma5), ptr(beta5), ptr(w4), G, eps,
+         ptr(dw0), ptr(db0), ptr(dgamma1), ptr(dbeta1), ptr(dw4), ptr(db4), ptr(dgamma5), ptr(dbeta5), ptr(dc1), ptr(da0), ptr(dc0),
+         ptr(scratch), scratch.numel(), stream())
+    return dc1, da0, dc0
+
+
 def content_ce(c_logits, plan: Plan, grad_scale=1.0, want_grad=True, out=None, dbias=None):
     """dbias = (d_bias_pitch_drum [131], d_bias_pitch_non_drum [131], d_bias_dur [99]) accumulates the
     un-embedding bias gradients inside the same pass (needs want_grad)."""
