@@ -65,7 +65,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   pm_train_metric_counts; no existing struct or argument list changed); gradient clipping by the global norm
  *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout); the
  *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap); sampled generation
- *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash). */
+ *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash); chord-aware sampling (pm_sample_chords, pm_node_tracks; the
+ *   PmChordRules struct). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -238,6 +239,55 @@ int pm_mtp_from_tokens(const int32_t* tokens /* [N,15,2] */, const float* s_tens
                        int32_t* bar_nodes /* [G] */, int32_t* node_ptr /* [G+1] */, float* mtp /* [G,4,32,15,230] */,
                        pm_stream_t stream);
 uint32_t pm_sample_hash(uint32_t seed, uint32_t row, uint32_t head, uint32_t token);
+
+/* Chord-aware sampling.  The reference reads a cell with `muspy_from_mtp` (utils.py:95-124): it walks the 15 slots in order,
+ * stops at the first slot whose pitch or duration is EOS / PAD and skips SOS.  pm_sample_chords draws a cell the way the
+ * training data lays one out (notes, one EOS, then PAD), under per-track rules.  Additive, same ABI version.
+ *
+ * For node n of track t = node_track[n] the slots s = 0..14 are decided in order, from the state count = 0, used = {},
+ * ended = false.  Per slot:
+ *   ended              : the slot's tokens are (PAD 130, PAD 98).
+ *   pitch candidates   : every pitch p < 128 whose pitch_mask[t] bit is set and that is not in `used`, but only while
+ *                        count < max_notes[t]; EOS (129) iff count >= min_notes[t] or there is no pitch candidate (the mask
+ *                        is exhausted, or count == max_notes[t]); SOS (128) and PAD (130) never.
+ *   pitch draw         : the pitch-head token of row r = n*15 + s by the definition above restricted to the candidates: rank,
+ *                        top_k, top_p and the Gumbel draw with the same key(seed, head, r) and per-token hash; a column that
+ *                        is no candidate is absent (it takes no rank, adds no mass to Z or to an outranking sum and cannot
+ *                        win); `max` in q_i is the maximum over the candidates; inv_T comes from temperature[0].  A single
+ *                        candidate is taken without a draw.
+ *   EOS drawn          : the slot's tokens are (129, 97), ended = true.
+ *   otherwise          : the duration head (head 1, same row) is drawn over the candidates 0..95 with temperature[1] (SOS 96,
+ *                        EOS 97 and PAD 98 never); the slot's tokens are (p, d), p joins `used`, count += 1.
+ * note_count[n] is the final count; max_notes <= 14 makes slot 14 at most the EOS.  The duration head has no say about the
+ * end of a chord.  Hence `muspy_from_mtp` on pm_mtp_from_tokens(tokens) yields exactly note_count[n] notes for node n, with
+ * distinct allowed pitches; and with the filters off the arg-max runs over a subset with the same fp32 scores, so where
+ * pm_sample_tokens (same seed, temperature == temperature[head]) draws a pitch token that is a candidate, or a duration token
+ * below 96, the chord's token at that slot is that token.
+ *   a temperature of 0 : the arg-max of that head's raw logits over its candidates, lowest index on ties; top_k == 1 gives
+ *                        that on both heads.
+ *   non-finite logits  : every token is in its head's range, note_count is in [0,14], nothing is written outside the outputs;
+ *                        which tokens come out is not promised.
+ * pm_sample_chords: one wave per node, at most the rows up to the chord's end (and one more) read; tokens [N,15,2] int32 and
+ *   note_count [N] (optional) written.  `rules` is read by the call.  PM_E_INVALID (before any launch): NULL c_logits,
+ *   node_track, rules or tokens; N <= 0 or N*15 >= 2^32; a temperature that is negative, NaN or inf; top_k < 0; top_p outside
+ *   (0, 1]; a track with min_notes < 0, max_notes outside [1,14] or min_notes > max_notes.
+ * pm_node_tracks: node_track[n] = the track index of node n's cell, nodes numbered in cell order as in pm_mtp_from_tokens;
+ *   entries n >= the number of active cells are written 0, nothing is written at or beyond N; node_ptr[G] returns the number
+ *   of active cells.  The workspaces and the argument checks are those of pm_mtp_from_tokens. */
+typedef struct PmChordRules {
+  float    temperature[2];   /* [0] pitch head, [1] duration head: finite, >= 0; 0 = arg-max over the candidates of that head */
+  int32_t  top_k;            /* as pm_sample_tokens (0 = off), applied to the candidates */
+  float    top_p;            /* as pm_sample_tokens, in (0, 1], applied to the candidates */
+  int32_t  min_notes[4];     /* per track (Drums, Bass, Guitar, Strings): 0 <= min_notes <= max_notes */
+  int32_t  max_notes[4];     /* 1 <= max_notes <= 14 */
+  uint32_t pitch_mask[4][4]; /* per track: bit (p & 31) of word (p >> 5) set = MIDI pitch p in [0,128) may be drawn */
+} PmChordRules;              /* 112 bytes, a HOST struct: read by the call, passed to the kernel by value */
+
+int pm_sample_chords(const float* c_logits /* [N,15,230] */, const uint8_t* node_track /* [N], values 0..3 */, int64_t N,
+                     const PmChordRules* rules, uint32_t seed, int32_t* tokens /* [N,15,2] */,
+                     int32_t* note_count /* [N] or NULL */, pm_stream_t stream);
+int pm_node_tracks(const float* s_tensor /* [G,4,32] 0/1 */, int32_t G, int64_t N, int32_t* bar_nodes /* [G] ws */,
+                   int32_t* node_ptr /* [G+1] ws; node_ptr[G] = active cells */, uint8_t* node_track /* [N] */, pm_stream_t stream);
 
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):

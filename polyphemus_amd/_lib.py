@@ -176,6 +176,8 @@ _SIGS = {
     "pm_buffer_swap": "ppls",
     "pm_sample_tokens": "plfifups",
     "pm_mtp_from_tokens": "ppilppps",
+    "pm_sample_chords": "pplpupps",
+    "pm_node_tracks": "pilppps",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",
@@ -183,6 +185,14 @@ _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_sta
 ABI_VERSION = 9          # PM_ABI_VERSION of include/polyphemus_hip.h this table was written against
 EXPORTED = sorted(list(_SIGS) + ["pm_abi_version", "pm_build_info", "pm_dropout_hash", "pm_sample_hash",
                                  "pm_vae_layout_bytes", "pm_vae_step_state_bytes"])
+
+
+
+class PmChordRules(C.Structure):
+    """ctypes mirror of PmChordRules (include/polyphemus_hip.h, "sampled generation"): a host struct, 112 bytes."""
+    _fields_ = [("temperature", C.c_float * 2), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_notes", C.c_int32 * 4),
+                ("max_notes", C.c_int32 * 4), ("pitch_mask", (C.c_uint32 * 4) * 4)]
+
 
 _lib: Optional[C.CDLL] = None
 

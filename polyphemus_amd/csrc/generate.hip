@@ -11,6 +11,7 @@
 //                           once, HBM-write bound: 13.8 KB per cell.
 //   pm_mtp_from_tokens    : the same pianoroll with an active cell holding the one-hot rows of its node's sampled tokens
 //                           (csrc/sample.hip) instead of its logits: the reference's arg-max decoding then returns the tokens.
+//   pm_node_tracks        : the track index of every node, in the same cell order (the per-track rules of chord-aware sampling).
 // Byte / index work, bit-exact against the oracle (tests/test_generate_gpu.py, tests/test_sampling_gpu.py).
 #include "common.h"
 
@@ -127,6 +128,24 @@ __global__ void __launch_bounds__(256) k_mtp_fill(const float* __restrict__ c_lo
   }
 }
 
+// the track of every node (pm_node_tracks): one wave per bar, lane l holds the cells l and l + 64 of the bar's 128 (track
+// k = cell >> 5); nodes are numbered in cell order, so a cell's node is node_ptr[g] + the active cells before it in the bar.
+// The tail [active, N) is zeroed by the same launch (grid-stride: no cell writes there).
+__global__ void __launch_bounds__(256) k_node_tracks(const float* __restrict__ s, const int* __restrict__ node_ptr, int G,
+                                                     int64_t N, uint8_t* __restrict__ node_track) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t active = node_ptr[G];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+    if (i >= active) node_track[i] = 0;
+  if (g >= G) return;                                                           // wave-uniform
+  const bool on0 = s[(int64_t)g * 128 + lane] != 0.f, on1 = s[(int64_t)g * 128 + 64 + lane] != 0.f;
+  const unsigned long long b0 = __ballot(on0), b1 = __ballot(on1), below = (1ull << lane) - 1ull;
+  const int64_t n0 = (int64_t)node_ptr[g] + __popcll(b0 & below), n1 = (int64_t)node_ptr[g] + __popcll(b0) + __popcll(b1 & below);
+  if (on0 && n0 < N) node_track[n0] = (uint8_t)(lane >> 5);
+  if (on1 && n1 < N) node_track[n1] = (uint8_t)(2 + (lane >> 5));
+}
+
 }  // namespace
 
 extern "C" int pm_binary_from_logits(const float* s_logits, int32_t G, float thresh, float* s_f32, uint8_t* s_u8,
@@ -158,5 +177,17 @@ extern "C" int pm_mtp_from_tokens(const int32_t* tokens, const float* s_tensor, 
   hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
   hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
   hipLaunchKernelGGL(k_mtp_fill<true>, dim3(G * 4), dim3(256), 0, st, nullptr, tokens, s_tensor, node_ptr, N, mtp);
+  return pm_check_launch();
+}
+
+extern "C" int pm_node_tracks(const float* s_tensor, int32_t G, int64_t N, int32_t* bar_nodes, int32_t* node_ptr,
+                              uint8_t* node_track, pm_stream_t stream) {
+  if ((!node_track && N > 0) || !s_tensor || !bar_nodes || !node_ptr || G <= 0 || N < 0 || bar_nodes == node_ptr)
+    return PM_E_INVALID;
+  if ((int64_t)G * 4 > 0x7fffffffLL) return PM_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
+  hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
+  hipLaunchKernelGGL(k_node_tracks, dim3(pm_cdiv(G, 4)), dim3(256), 0, st, s_tensor, node_ptr, G, N, node_track);
   return pm_check_launch();
 }

@@ -10,6 +10,9 @@
 //                     the lane's own columns of the same head, two vector instructions per pair and count): it counts the tokens that outrank a column (top-k) and
 //                     sums their softmax mass (top-p) in one go, exact under ties, with no LDS and no atomics.
 //                     MODE 0 greedy and MODE 1 unfiltered skip that pass altogether.
+//   k_sample_chords : chord-aware sampling (PmChordRules): one wave per node, its 15 slots decided in order as notes, one EOS,
+//                     then PAD, under per-track rules (note counts, a pitch mask, no pitch twice); the same lane layout, the
+//                     same noise stream and the same filters, applied to the candidates of each slot.
 #include "common.h"
 
 namespace {
@@ -156,6 +159,157 @@ __global__ void __launch_bounds__(256) k_sample_tokens(const float* __restrict__
   if (lane < 2) tokens[r * 2 + lane] = lane ? td : tp;
 }
 
+// ---- chord-aware sampling ("sampled generation", PmChordRules) -------------------------------------------------------
+constexpr int PITCH_EOS = 129, PITCH_PAD = 130, DUR_EOS = 97, DUR_PAD = 98, N_DUR_CAND = 96;
+
+// One head of one row.  NV registers per lane (v[j] = the logit of this lane's j-th column of the head, tok[j] its token,
+// cand[j] whether it is a candidate); the sources of the all-pairs pass are the candidates alone, taken in index order from
+// the ballots, so a column that is no candidate takes no rank and adds no mass.  Returns a candidate whenever there is one:
+// where no score wins (non-finite logits) the candidate of the lowest index.
+template <int MODE, int NV>
+__device__ static inline int draw_head(const float (&v)[NV], const int (&tok)[NV], const bool (&cand)[NV], bool greedy,
+                                       float inv_t, int top_k, float top_p, uint32_t key, int lane) {
+  unsigned long long bal[NV];
+  int ncand = 0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) { bal[j] = __ballot(cand[j]); ncand += __popcll(bal[j]); }
+  // the candidate of the lowest index: register by register, lane by lane (tok grows that way in both heads)
+  int first = 0;
+#pragma unroll
+  for (int j = NV - 1; j >= 0; --j)
+    if (bal[j]) first = __builtin_amdgcn_readlane(tok[j], (int)__builtin_ctzll(bal[j]));
+  if (ncand <= 1) return first;                                                 // (wave-uniform) no draw
+  bool live[NV];
+  float score[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) live[j] = cand[j];
+  if (MODE == SAMPLE_GREEDY || greedy) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) score[j] = v[j];
+  } else {
+    if (MODE != SAMPLE_PLAIN) {
+      float m = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) m = fmaxf(m, cand[j] ? v[j] : -INFINITY);
+      m = pm_wave_max(m);
+      float q[NV], mass[NV];
+      unsigned key_[NV];
+      int cnt[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        q[j] = cand[j] ? expf((v[j] - m) * inv_t) : 0.f;
+        key_[j] = ukey(v[j]);
+        cnt[j] = 0;
+        mass[j] = 0.f;
+      }
+      // source (register s, lane l) outranks target (register j, this lane) iff key(source) > thr: the target's key when the
+      // source comes later in index order, its key - 1 when it comes earlier (equal logits: the lower index outranks)
+#pragma unroll
+      for (int s = 0; s < NV; ++s) {
+        for (unsigned long long m_s = bal[s]; m_s; m_s &= m_s - 1) {
+          const int l = (int)__builtin_ctzll(m_s);
+          const unsigned sk = (unsigned)__builtin_amdgcn_readlane((int)key_[s], l);
+          const float sq = MODE == SAMPLE_TOPP ? bcast(q[s], l) : 0.f;
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const bool earlier = s < j || (s == j && l < lane);
+            const bool o = sk > key_[j] - (earlier ? 1u : 0u);
+            cnt[j] += o ? 1 : 0;
+            if (MODE == SAMPLE_TOPP) mass[j] += o ? sq : 0.f;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NV; ++j) live[j] = live[j] && cnt[j] < top_k;
+      if (MODE == SAMPLE_TOPP) {
+        float z = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) z += live[j] ? q[j] : 0.f;
+        z = pm_wave_sum(z);
+        const float edge = top_p * z;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) live[j] = live[j] && mass[j] < edge;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) score[j] = __fadd_rn(__fmul_rn(v[j], inv_t), gumbel(key, (uint32_t)tok[j]));
+  }
+  Cand b = {-INFINITY, 0x7fffffff};
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const Cand c = {live[j] ? score[j] : -INFINITY, live[j] ? tok[j] : 0x7fffffff};
+    b = cand_better(b, c);
+  }
+  b = cand_wave(b);
+  return b.c == 0x7fffffff ? first : b.c;
+}
+
+// One wave per node: the 15 slots in order, the state (count, ended) wave-uniform, `used` and the track's mask bits per-lane
+// predicates on the two registers that hold the pitches below 128 (pitch p = lane p & 63, register p >> 6).  The rows'
+// addresses depend on no decision: the row of slot s + 1 is in flight while slot s is decided, and nothing is read behind
+// the slot that draws the EOS.  Lane l < 30 keeps token l of the node (slot l / 2, head l & 1) and stores it at the end.
+template <int MODE>
+__global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__ c_logits, const uint8_t* __restrict__ node_track,
+                                                       int64_t N, const PmChordRules R, float inv_tp, float inv_td, int greedy_heads,
+                                                       int top_k, uint32_t seed, int* __restrict__ tokens, int* __restrict__ note_count) {
+  const int lane = threadIdx.x & 63;
+  const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;                                                           // wave-uniform
+  const int t = __builtin_amdgcn_readfirstlane((int)node_track[n]) & 3;
+  int min_n = 0, max_n = 1;
+  uint32_t w0 = 0, w1 = 0;                                                      // this lane's words of the track's mask
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (t == k) {
+      min_n = R.min_notes[k]; max_n = R.max_notes[k];
+      w0 = R.pitch_mask[k][lane >> 5]; w1 = R.pitch_mask[k][2 + (lane >> 5)];
+    }
+  const bool allow0 = (w0 >> (lane & 31)) & 1u, allow1 = (w1 >> (lane & 31)) & 1u;
+  const bool live3 = lane < PM_N_TOK - 192;
+  const float* x = c_logits + n * (PM_N_SLOTS * PM_N_TOK);
+  const int tokp[3] = {lane, lane + 64, lane + 128};
+  const int tokd[2] = {lane - 3, lane + 192 - PM_N_PITCH};
+  const bool candd[2] = {lane >= 3, lane + 192 - PM_N_PITCH < N_DUR_CAND};
+  bool used0 = false, used1 = false;
+  int count = 0, slot = 0;
+  int mine = (lane & 1) ? DUR_PAD : PITCH_PAD;
+  float v[4], nx[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) v[j] = x[lane + 64 * j];
+  v[3] = live3 ? x[lane + 192] : -INFINITY;
+  for (; slot < PM_N_SLOTS; ++slot) {
+    if (slot + 1 < PM_N_SLOTS) {
+      const float* y = x + (slot + 1) * PM_N_TOK;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) nx[j] = y[lane + 64 * j];
+      nx[3] = live3 ? y[lane + 192] : -INFINITY;
+    }
+    const uint32_t r = (uint32_t)(n * PM_N_SLOTS + slot);
+    const bool room = count < max_n;
+    bool candp[3] = {allow0 && !used0 && room, allow1 && !used1 && room, false};
+    const bool any = __ballot(candp[0] || candp[1]) != 0ull;
+    candp[2] = lane == PITCH_EOS - 128 && (count >= min_n || !any);
+    const float vp[3] = {v[0], v[1], v[2]};
+    const int p = draw_head<MODE, 3>(vp, tokp, candp, (greedy_heads & 1) != 0, inv_tp, top_k, R.top_p, pm_edge_key(seed, 0u, r), lane);
+    if (p >= 128) {                                                             // the EOS (nothing else is a candidate there)
+      if (lane == 2 * slot) mine = PITCH_EOS;
+      if (lane == 2 * slot + 1) mine = DUR_EOS;
+      break;
+    }
+    const float vd[2] = {v[2], v[3]};
+    const int d = draw_head<MODE, 2>(vd, tokd, candd, (greedy_heads & 2) != 0, inv_td, top_k, R.top_p, pm_edge_key(seed, 1u, r), lane);
+    if (lane == 2 * slot) mine = p;
+    if (lane == 2 * slot + 1) mine = d;
+    used0 = used0 || lane == p;
+    used1 = used1 || lane + 64 == p;
+    ++count;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = nx[j];
+  }
+  if (lane < 2 * PM_N_SLOTS) tokens[n * (2 * PM_N_SLOTS) + lane] = mine;
+  if (note_count && lane == 0) note_count[n] = count;
+}
+
 }  // namespace
 
 extern "C" uint32_t pm_sample_hash(uint32_t seed, uint32_t row, uint32_t head, uint32_t token) {
@@ -181,6 +335,40 @@ extern "C" int pm_sample_tokens(const float* c_logits, int64_t rows, float tempe
       hipLaunchKernelGGL(k_sample_tokens<SAMPLE_TOPK>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
     else
       hipLaunchKernelGGL(k_sample_tokens<SAMPLE_PLAIN>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
+  }
+  return pm_check_launch();
+}
+
+extern "C" int pm_sample_chords(const float* c_logits, const uint8_t* node_track, int64_t N, const PmChordRules* rules,
+                                uint32_t seed, int32_t* tokens, int32_t* note_count, pm_stream_t stream) {
+  if (!c_logits || !node_track || !rules || !tokens || N <= 0 || N * PM_N_SLOTS >= ((int64_t)1 << 32)) return PM_E_INVALID;
+  const PmChordRules R = *rules;
+  for (int h = 0; h < 2; ++h)
+    if (!(R.temperature[h] >= 0.f) || !(R.temperature[h] <= 3.4028234663852886e38f)) return PM_E_INVALID;   // NaN, inf, negative
+  if (R.top_k < 0 || !(R.top_p > 0.f) || !(R.top_p <= 1.f)) return PM_E_INVALID;
+  for (int k = 0; k < 4; ++k)
+    if (R.min_notes[k] < 0 || R.max_notes[k] < 1 || R.max_notes[k] > PM_N_SLOTS - 1 || R.min_notes[k] > R.max_notes[k])
+      return PM_E_INVALID;
+  const dim3 grid((unsigned)pm_cdiv(N, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const bool k_on = R.top_k > 0 && R.top_k < PM_N_PITCH, p_on = R.top_p < 1.f;
+  const int kk = R.top_k == 0 ? 0x7fffffff : R.top_k;
+  const int greedy = (R.temperature[0] == 0.f ? 1 : 0) | (R.temperature[1] == 0.f ? 2 : 0);
+  if (greedy == 3 || R.top_k == 1) {
+    hipLaunchKernelGGL(k_sample_chords<SAMPLE_GREEDY>, grid, block, 0, st, c_logits, node_track, N, R, 1.f, 1.f, 3, kk, seed,
+                       tokens, note_count);
+  } else {
+    const float inv_tp = (greedy & 1) ? 1.f : (float)(1.0 / (double)R.temperature[0]);
+    const float inv_td = (greedy & 2) ? 1.f : (float)(1.0 / (double)R.temperature[1]);
+    if (p_on)
+      hipLaunchKernelGGL(k_sample_chords<SAMPLE_TOPP>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
+                         seed, tokens, note_count);
+    else if (k_on)
+      hipLaunchKernelGGL(k_sample_chords<SAMPLE_TOPK>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
+                         seed, tokens, note_count);
+    else
+      hipLaunchKernelGGL(k_sample_chords<SAMPLE_PLAIN>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
+                         seed, tokens, note_count);
   }
   return pm_check_launch();
 }

@@ -4,6 +4,10 @@ without the reference's host synchronisations (`nonzero`, per-sample Python grap
 Converting the pianoroll to MIDI (muspy) is outside the hot path and stays with the caller."""
 from __future__ import annotations
 
+from dataclasses import dataclass
+from typing import Any
+
+import numpy as np
 import torch
 
 from . import ops
@@ -14,8 +18,41 @@ def generate_z(bs: int, d_model: int, device) -> torch.Tensor:
     return torch.randn(bs, d_model, device=device)
 
 
+@dataclass
+class ChordRules:
+    """The per-track rules of chord-aware sampling (`generate_music(chord_rules=...)`, `ops.sample_chords`): `min_notes` and
+    `max_notes` are an int or four ints (Drums, Bass, Guitar, Strings; 0 <= min_notes <= max_notes, 1 <= max_notes <= 14),
+    `allowed_pitches` None (every pitch) or a bool array-like [4,128] whose rows `pitch_mask` helps fill."""
+    min_notes: Any = 1
+    max_notes: Any = 14
+    allowed_pitches: Any = None
+
+
+def pitch_mask(lo: int = 0, hi: int = 127, pitch_classes=None) -> np.ndarray:
+    """bool [128]: the MIDI pitches lo..hi (inclusive) whose pitch class (pitch mod 12) is in `pitch_classes` (None = all):
+    one track's row of `ChordRules.allowed_pitches` (a range and a scale)."""
+    p = np.arange(128)
+    m = (p >= lo) & (p <= hi)
+    if pitch_classes is not None:
+        m &= np.isin(p % 12, np.asarray(list(pitch_classes), dtype=np.int64) % 12)
+    return m
+
+
+def _decode(vae, z, s_cond, s_tensor_cond):
+    """the decoder pass of `generate_music`: (c_logits [N,15,230] fp32, s_tensor)"""
+    vae.decoder.__dict__.pop("_last_structure", None)
+    s_logits, c_logits = vae.decoder(z, s_cond)
+    if s_tensor_cond is not None:
+        s_tensor = s_tensor_cond
+    elif s_cond is None:                 # the structure the decoder itself thresholded and built its graphs from
+        s_tensor = vae.decoder.__dict__["_last_structure"].view(s_logits.shape).bool()
+    else:
+        s_tensor = vae.decoder._binary_from_logits(s_logits)
+    return c_logits.detach().contiguous().float(), s_tensor
+
+
 def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
-                   return_tokens=False):
+                   return_tokens=False, chord_rules=None, return_note_counts=False):
     """generate.py:21-37.  `s_cond` is a batch of bar graphs (`vae.decoder._structure_from_binary`) or None (the
     structure then comes from the decoder's own thresholded logits); `s_tensor_cond` [B,n_bars,4,32] is the binary
     structure the pianoroll is laid out on when given.  Returns (mtp [B,n_bars,4,32,15,230], s_tensor bool).
@@ -26,18 +63,20 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     active cells hold their one-hot rows, so `muspy_from_mtp` decodes the drawn piece unchanged.  `seed` in [0, 2^32)
     makes the draw a pure function of the logits; None takes one from torch's CPU generator (`torch.manual_seed`
     repeats a run; no device synchronisation).  `return_tokens` appends the int32 [N,15,2] tokens (pitch, duration) to
-    the returned tuple; without sampling they are the arg-max tokens of the logits `mtp` holds."""
+    the returned tuple; without sampling they are the arg-max tokens of the logits `mtp` holds.
+
+    With `chord_rules` (a `ChordRules`) the call samples chord by chord (`ops.sample_chords`: notes, one EOS, then PAD; no
+    pitch twice in a chord; per-track note counts and allowed pitches), so `muspy_from_mtp` reads exactly the drawn notes.
+    `temperature` defaults to 1.0 and may be a pair (pitch, duration); 0 = arg-max under the rules.  `return_note_counts`
+    appends the int32 [N] note counts behind the tokens.  Bad rules raise before the model is touched."""
+    if chord_rules is not None:
+        return _generate_chords(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, return_tokens, chord_rules,
+                                return_note_counts)
+    if return_note_counts:
+        raise ValueError("return_note_counts needs chord_rules")
     ops.check_sampling_args(temperature, top_k, top_p, seed)
     sampled = temperature is not None or top_k is not None or top_p is not None
-    vae.decoder.__dict__.pop("_last_structure", None)
-    s_logits, c_logits = vae.decoder(z, s_cond)
-    if s_tensor_cond is not None:
-        s_tensor = s_tensor_cond
-    elif s_cond is None:                 # the structure the decoder itself thresholded and built its graphs from
-        s_tensor = vae.decoder.__dict__["_last_structure"].view(s_logits.shape).bool()
-    else:
-        s_tensor = vae.decoder._binary_from_logits(s_logits)
-    c_logits = c_logits.detach().contiguous().float()
+    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond)
     if not sampled:
         mtp = ops.mtp_from_logits(c_logits, s_tensor)
         return (mtp, s_tensor, ops.sample_tokens(c_logits, temperature=0.0)) if return_tokens else (mtp, s_tensor)
@@ -46,3 +85,24 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     tokens = ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed)
     mtp = ops.mtp_from_tokens(tokens, s_tensor)
     return (mtp, s_tensor, tokens) if return_tokens else (mtp, s_tensor)
+
+
+def _generate_chords(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, return_tokens, chord_rules,
+                     return_note_counts):
+    if not isinstance(chord_rules, ChordRules):
+        raise ValueError(f"chord_rules must be a ChordRules, got {chord_rules!r}")
+    ops.check_chord_args(temperature, top_k, top_p, seed, chord_rules.min_notes, chord_rules.max_notes,
+                         chord_rules.allowed_pitches)
+    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond)
+    if seed is None:
+        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+    track = ops.node_tracks(s_tensor, c_logits.shape[0], check=False)
+    tokens, note_count = ops.sample_chords(c_logits, track, 1.0 if temperature is None else temperature, top_k, top_p, seed,
+                                           chord_rules.min_notes, chord_rules.max_notes, chord_rules.allowed_pitches)
+    mtp = ops.mtp_from_tokens(tokens, s_tensor)                  # its check is the call's one host read
+    out = (mtp, s_tensor)
+    if return_tokens:
+        out += (tokens,)
+    if return_note_counts:
+        out += (note_count,)
+    return out

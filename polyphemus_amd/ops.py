@@ -256,6 +256,113 @@ def mtp_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool = 
     return mtp
 
 
+def node_tracks(s_tensor: torch.Tensor, N: int, check: bool = True) -> torch.Tensor:
+    """`pm_node_tracks`: uint8 [N], the track index (0 Drums .. 3 Strings) of every node of the binary structure `s_tensor`
+    ([...,4,32], any dtype), nodes numbered in cell order as in `mtp_from_tokens`.  Entries behind the active cells are 0.
+    `check` reads the active-cell count back (one host sync) and raises when it differs from `N`."""
+    if s_tensor.dim() < 3 or s_tensor.shape[-2:] != (4, 32):
+        raise ValueError("s_tensor must be [...,4,32]")
+    if not s_tensor.is_cuda:
+        raise HipExtensionError(f"s_tensor lives on {s_tensor.device}: the HIP path needs device tensors (no CPU fallback)")
+    N = int(N)
+    if N < 0:
+        raise ValueError(f"N must be >= 0, got {N}")
+    s = s_tensor.to(F32).contiguous()
+    G, dev = s.numel() // 128, s.device
+    out = torch.empty(N, dtype=U8, device=dev)
+    if G == 0:
+        if check and N:
+            raise ValueError(f"shape mismatch: s_tensor has 0 active cells, {N} nodes asked for")
+        return out.zero_()
+    bn, npt = torch.empty(G, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
+    call("pm_node_tracks", ptr(s), G, N, ptr(bn), ptr(npt), ptr(out) if N else None, stream())
+    if check:
+        active = int(npt[G])
+        if active != N:
+            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, {N} nodes asked for")
+    return out
+
+
+def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
+                     c_logits=None, node_track=None):
+    """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
+    ValueError naming the argument.  `temperature` is a number or a pair (pitch, duration); `min_notes` / `max_notes` an int
+    or four ints (Drums, Bass, Guitar, Strings) with 0 <= min_notes <= max_notes and 1 <= max_notes <= 14;
+    `allowed_pitches` None or a bool array-like [4,128]; `node_track`, when given, uint8 [N] on the device of `c_logits`.
+    Returns ((T_pitch, T_duration), min_notes [4], max_notes [4], pitch_mask: 4 x 4 words of 32 bits)."""
+    import math
+    import numbers
+    import numpy as np
+    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    integer = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if temperature is None:
+        temperature = 1.0
+    pair = tuple(temperature) if isinstance(temperature, (tuple, list)) else (temperature, temperature)
+    if len(pair) != 2 or not all(real(v) and math.isfinite(v) and v >= 0 for v in pair):
+        raise ValueError(f"temperature must be a finite number >= 0 or a pair (pitch, duration) of them, got {temperature!r}")
+    check_sampling_args(None, top_k, top_p, seed)
+
+    def four(v, name):
+        out = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else (v,) * 4
+        if len(out) != 4 or not all(integer(a) for a in out):
+            raise ValueError(f"{name} must be an int or four ints (one per track), got {v!r}")
+        return tuple(int(a) for a in out)
+    mx = four(max_notes, "max_notes")
+    if not all(1 <= a <= C.MAX_SIMU_TOKENS - 2 for a in mx):
+        raise ValueError(f"max_notes must be in [1, {C.MAX_SIMU_TOKENS - 2}], got {max_notes!r}")
+    mn = four(min_notes, "min_notes")
+    if not all(0 <= a <= b for a, b in zip(mn, mx)):
+        raise ValueError(f"min_notes must satisfy 0 <= min_notes <= max_notes = {max_notes!r}, got {min_notes!r}")
+    if allowed_pitches is None:
+        words = [[0xFFFFFFFF] * 4 for _ in range(4)]
+    else:
+        a = allowed_pitches.detach().cpu().numpy() if isinstance(allowed_pitches, torch.Tensor) else np.asarray(allowed_pitches)
+        if a.shape != (4, 128) or a.dtype != np.bool_:
+            raise ValueError(f"allowed_pitches must be a bool array of shape [4,128], got {a.dtype} {tuple(a.shape)}")
+        bits = a.reshape(4, 4, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
+        words = [[int(w) for w in row] for row in bits.sum(-1)]
+    if node_track is not None:
+        if not isinstance(node_track, torch.Tensor) or node_track.dtype != U8 or node_track.dim() != 1 or not node_track.is_contiguous():
+            raise ValueError("node_track must be a contiguous uint8 tensor [N]")
+        if c_logits is not None and (node_track.shape[0] != c_logits.shape[0] or node_track.device != c_logits.device):
+            raise ValueError(f"node_track must be uint8 [N = {c_logits.shape[0]}] on {c_logits.device}, got "
+                             f"[{node_track.shape[0]}] on {node_track.device}")
+    return (float(pair[0]), float(pair[1])), mn, mx, words
+
+
+def sample_chords(c_logits: torch.Tensor, node_track: torch.Tensor, temperature=1.0, top_k: Optional[int] = None,
+                  top_p: Optional[float] = None, seed: int = 0, min_notes=1, max_notes=14, allowed_pitches=None):
+    """`pm_sample_chords` (chord-aware sampling, "sampled generation" in include/polyphemus_hip.h): every node's 15 slots
+    drawn in order as notes, one EOS, then PAD.  A pitch is drawn from the pitches `allowed_pitches` ([4,128] bool, None =
+    all) gives the node's track (`node_track`, uint8 [N], see `node_tracks`) that the chord does not hold yet, while it has
+    fewer than `max_notes` notes; the EOS from `min_notes` notes on; the duration among 0..95.  `temperature` is a number or a
+    pair (pitch, duration), 0 = arg-max over the candidates; `top_k` / `top_p` apply to the candidates.  A pure function of
+    the logits, the rules and `seed`.  Returns (tokens int32 [N,15,2], note_count int32 [N])."""
+    from ._lib import PmChordRules
+    _chk(c_logits, F32, "c_logits")
+    if c_logits.dim() != 3 or c_logits.shape[1:] != (C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR):
+        raise ValueError("c_logits must be [N,15,230]")
+    temps, mn, mx, words = check_chord_args(temperature, top_k, top_p, seed, min_notes, max_notes, allowed_pitches,
+                                            c_logits=c_logits, node_track=node_track)
+    if node_track is None:
+        raise ValueError("node_track is None")
+    N = c_logits.shape[0]
+    tokens = torch.empty(N, C.MAX_SIMU_TOKENS - 1, 2, dtype=I32, device=c_logits.device)
+    note_count = torch.empty(N, dtype=I32, device=c_logits.device)
+    if N:
+        rules = PmChordRules()
+        rules.temperature[0], rules.temperature[1] = temps
+        rules.top_k = 0 if top_k is None else min(int(top_k), 1 << 30)
+        rules.top_p = 1.0 if top_p is None else float(top_p)
+        for k in range(4):
+            rules.min_notes[k], rules.max_notes[k] = mn[k], mx[k]
+            for w in range(4):
+                rules.pitch_mask[k][w] = words[k][w]
+        call("pm_sample_chords", ptr(c_logits), ptr(node_track), N, ctypes.addressof(rules), int(seed), ptr(tokens),
+             ptr(note_count), stream())
+    return tokens, note_count
+
+
 def gcl_forward_fused(x, T, plan: Plan, dropout_p: float, seed: int, layer_uid: int, w_frag, bias, col_stats=None,
                       planes=None, use_classes: bool = True):
     """`pm_gcl_forward_fused`: h = A'(x) @ [W_t; W_4; W_5; root] + bias of one GCL layer in one kernel (compact graphs,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time sampled generation (csrc/sample.hip, k_mtp_fill<true>) at the generation workload of DESIGN §5 (B = 256, two bars):
 `k_sample_tokens` on its greedy, unfiltered, top-k and top-p routes with its bytes over time against the 8 TB/s roof,
+`k_sample_chords` (chord-aware sampling) on the same routes beside it in the same run, on the same logits (chords that run to
+max_notes) and on logits with the EOS column raised (chords that end early), `node_tracks`,
 `mtp_from_tokens` against `mtp_from_logits`, and `generate_music` sampled against `generate_music` without sampling
 arguments (the call as it was), alternated in one process.  Device events around every call, medians.
 Usage: python tools/bench_sampling.py [B] [n_bars] [--json=FILE]"""
@@ -13,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from polyphemus_amd import ops  # noqa: E402
-from polyphemus_amd.generate import generate_music  # noqa: E402
+from polyphemus_amd.generate import ChordRules, generate_music  # noqa: E402
 
 ROOF = 8.0e12           # HBM3E bytes/s
 
@@ -64,6 +66,28 @@ def main():
         out["k_sample_tokens"][k] = r
         print(f"sample_tokens {k:24s} rows={rows}: {r['median_us']:8.1f} us (min {r['min_us']:.1f})  {r['TB_per_s']:6.3f} TB/s "
               f"= {100 * r['share_of_roof']:.1f} % of the roof ({byts / 1e6:.0f} MB)")
+    # chord-aware sampling beside it: the same logits (an EOS is one of 129 candidates: nearly every chord runs to max_notes =
+    # 14, all 15 rows read), and the EOS column raised by 6 (= 2 sigma, as in tests/test_chords_gpu.py: chords end early and the
+    # rows behind the end are not read).  Default rules: min_notes 1, max_notes 14, every pitch allowed.
+    track = ops.node_tracks(s, N)
+    c_eos = c.clone()
+    c_eos[:, :, 129] += 6.0
+    out["k_sample_chords"] = {}
+    for label, logits in (("chords run to max_notes", c), ("EOS raised by 6", c_eos)):
+        notes = float(ops.sample_chords(logits, track, seed=1)[1].float().mean())
+        calls = {}
+        for k, kw in routes.items():
+            calls[f"tokens {k}"] = lambda kw=kw, logits=logits: ops.sample_tokens(logits, seed=1, **kw)
+            calls[f"chords {k}"] = lambda kw=kw, logits=logits: ops.sample_chords(logits, track, seed=1, **kw)
+        ts = times(calls)
+        out["k_sample_chords"][label] = {"mean_notes_unfiltered": round(notes, 2), **{k: summary(v) for k, v in ts.items()}}
+        for k in routes:
+            a, b = summary(ts[f"tokens {k}"]), summary(ts[f"chords {k}"])
+            print(f"sample_chords [{label}, {notes:.2f} notes per node] {k:24s} N={N}: {b['median_us']:8.1f} us (min {b['min_us']:.1f}) "
+                  f"against sample_tokens {a['median_us']:8.1f} us (min {a['min_us']:.1f})")
+    ts = times({"node_tracks": lambda: ops.node_tracks(s, N, check=False)})
+    out["node_tracks"] = summary(ts["node_tracks"])
+    print(f"node_tracks      N={N}: {out['node_tracks']['median_us']:8.1f} us (min {out['node_tracks']['min_us']:.1f})")
     tok = ops.sample_tokens(c, seed=1)
     sf = s.float()
     ts = times({"mtp_from_logits": lambda: ops.mtp_from_logits(c, sf, check=False),
@@ -87,6 +111,9 @@ def main():
                      "sampled, temperature=1": lambda: generate_music(vae, z, *cond, temperature=1.0, seed=3),
                      "sampled, top_k=40": lambda: generate_music(vae, z, *cond, top_k=40, seed=3),
                      "sampled, top_k=40 top_p=0.9": lambda: generate_music(vae, z, *cond, top_k=40, top_p=0.9, seed=3),
+                     "chords, temperature=1": lambda: generate_music(vae, z, *cond, seed=3, chord_rules=ChordRules()),
+                     "chords, top_k=40 top_p=0.9": lambda: generate_music(vae, z, *cond, top_k=40, top_p=0.9, seed=3,
+                                                                          chord_rules=ChordRules()),
                      "decoder alone": lambda: vae.decoder(z, cond[0] if cond else None)}
             nodes = int(generate_music(vae, z, *cond, return_tokens=True)[2].shape[0])
             ts = times(calls, n=15)
