@@ -66,7 +66,7 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout); the
  *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap); sampled generation
  *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash); chord-aware sampling (pm_sample_chords, pm_node_tracks; the
- *   PmChordRules struct). */
+ *   PmChordRules struct); structure sampling (pm_sample_structure; the PmStructureRules struct). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -288,6 +288,59 @@ int pm_sample_chords(const float* c_logits /* [N,15,230] */, const uint8_t* node
                      int32_t* note_count /* [N] or NULL */, pm_stream_t stream);
 int pm_node_tracks(const float* s_tensor /* [G,4,32] 0/1 */, int32_t G, int64_t N, int32_t* bar_nodes /* [G] ws */,
                    int32_t* node_ptr /* [G+1] ws; node_ptr[G] = active cells */, uint8_t* node_track /* [N] */, pm_stream_t stream);
+
+/* Structure sampling.  The reference decides which of the 4 x 32 (track, timestep) cells of a bar are active by thresholding
+ * sigmoid(s_logits) (pm_binary_from_logits): one latent, one rhythm.  pm_sample_structure draws the cells from the model's own
+ * probabilities instead, under per-track rules: how many cells of a track may be active, and on which timesteps.  No line of
+ * the reference stands behind it.  Additive, same ABI version.
+ *
+ * s_logits is [G,4,32] fp32, contiguous: bar g, track k (Drums, Bass, Guitar, Strings), timestep t, cell index c = 32k + t.
+ * A cell is allowed iff bit t of step_mask[k] is set; a cell that is not allowed is off and takes no rank.
+ *   score   : of an allowed cell with logit x, in fp32, one rounding per operation, in exactly this order:
+ *               temperature == 0 : score = x - bias[k]                       (no noise)
+ *               otherwise        : score = (x - bias[k]) * inv_T + L
+ *                 inv_T = (float)(1.0 / (double)temperature)
+ *                 L     = logf(u) - logf(1.0f - u)             (logistic noise; 1.0f - u is exact)
+ *                 u     = ((h >> 9) + 0.5f) * 2^-23
+ *                 h     = pm_mix32(key(seed, head = 2, r = g) + c * 0xC2B2AE35u)
+ *             key and pm_mix32 are those of pm_sample_tokens, and pm_sample_hash(seed, g, 2, c) returns h >> 9.  Head 2 keeps
+ *             the structure stream apart from the pitch (0) and the duration (1) stream of the same seed.  The stream is a
+ *             pure function of (seed, g, c): it depends neither on the launch shape nor on the wave that has the bar.  With
+ *             no bound binding a cell is therefore on with probability sigmoid((x - bias[k]) / temperature); the host passes
+ *             bias = logit(threshold), so a threshold of 0.5 is a bias of 0.
+ *   rank    : within each (bar, track) the allowed cells are ordered by score, descending, equal scores by lower t first.  The
+ *             order is a total order on the bits of the score (the score as an unsigned key of the same order, -0 = +0, as
+ *             csrc/sample.hip orders logits), so the ranks are a permutation of 0 .. allowed - 1 even when a score is not finite.
+ *   on/off  : an allowed cell is on iff rank < min_active[k], or rank < max_active[k] and !(score < 0).  max_active[k] == 0
+ *             mutes the track; min_active[k] forces the best cells on whatever their scores.
+ *   no empty bar : where this leaves a bar without any cell, the allowed cell with the highest score among the tracks with
+ *             max_active > 0 is switched on, the lowest cell index on ties.  (The reference's fake drum hit at [0,0],
+ *             model.py:617-621, may be masked or muted here.)
+ *   outputs : s_f32 and / or s_u8 [G,4,32] hold 0 / 1 (either may be NULL, not both); track_count [G,4] (optional) holds the
+ *             active cells of every (bar, track), counted after the no-empty-bar step.
+ *   non-finite logits: every output is 0 or 1, every count is in [min_active, max_active] except for the one cell the
+ *             no-empty-bar step may add to a track with min_active == 0, no bar is empty and nothing is written outside the
+ *             outputs; which cells come out is not promised.
+ * Relation to pm_binary_from_logits: with temperature = 0, bias = 0, bounds 0 .. 32 and full masks a cell is on iff !(x < 0),
+ *   there iff !(sigmoid(x) < 0.5).  The two agree wherever |x| >= 1e-6 and the thresholded bar is not empty; they may differ
+ *   within a rounding of x = 0 (expf rounds, the comparison with 0 does not) and in the cell an empty bar gets ([0,0] there,
+ *   the best-scoring cell here).  They are not bit-identical.
+ * pm_sample_structure: one launch, a bar per half-wave, every logit read once, every output written once, no workspace.
+ *   `rules` is read by the call.  PM_E_INVALID (before any launch): NULL s_logits or rules, or both s_f32 and s_u8 NULL;
+ *   G <= 0; a temperature that is negative, NaN or inf; a bias that is not finite; a track with min_active < 0,
+ *   max_active > 32, min_active > max_active or min_active > popcount(step_mask); no track with both max_active > 0 and a
+ *   non-zero step_mask. */
+typedef struct PmStructureRules {
+  float    temperature;      /* finite, >= 0; 0 = no noise */
+  float    bias[4];          /* per track: logit(threshold), computed by the host in double */
+  int32_t  min_active[4];    /* 0 <= min_active <= max_active */
+  int32_t  max_active[4];    /* 0..32; 0 mutes the track */
+  uint32_t step_mask[4];     /* bit t set = timestep t of the track may be active */
+} PmStructureRules;          /* 68 bytes, a HOST struct: read by the call, passed to the kernel by value */
+
+int pm_sample_structure(const float* s_logits /* [G,4,32] */, int32_t G, const PmStructureRules* rules, uint32_t seed,
+                        float* s_f32 /* [G,4,32] or NULL */, uint8_t* s_u8 /* [G,4,32] or NULL */,
+                        int32_t* track_count /* [G,4] or NULL */, pm_stream_t stream);
 
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):

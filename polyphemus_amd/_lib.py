@@ -178,6 +178,7 @@ _SIGS = {
     "pm_mtp_from_tokens": "ppilppps",
     "pm_sample_chords": "pplpupps",
     "pm_node_tracks": "pilppps",
+    "pm_sample_structure": "pipuppps",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",
@@ -192,6 +193,12 @@ class PmChordRules(C.Structure):
     """ctypes mirror of PmChordRules (include/polyphemus_hip.h, "sampled generation"): a host struct, 112 bytes."""
     _fields_ = [("temperature", C.c_float * 2), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_notes", C.c_int32 * 4),
                 ("max_notes", C.c_int32 * 4), ("pitch_mask", (C.c_uint32 * 4) * 4)]
+
+
+class PmStructureRules(C.Structure):
+    """ctypes mirror of PmStructureRules (include/polyphemus_hip.h, "Structure sampling"): a host struct, 68 bytes."""
+    _fields_ = [("temperature", C.c_float), ("bias", C.c_float * 4), ("min_active", C.c_int32 * 4),
+                ("max_active", C.c_int32 * 4), ("step_mask", C.c_uint32 * 4)]
 
 
 _lib: Optional[C.CDLL] = None

@@ -1,5 +1,6 @@
-// sample.hip — stochastic decoding of the content logits on the device ("sampled generation", include/polyphemus_hip.h):
-// temperature, top-k and nucleus (top-p) sampling of the pitch and the duration token of every (node, slot) row.
+// sample.hip — stochastic decoding on the device ("sampled generation", include/polyphemus_hip.h): temperature, top-k and
+// nucleus (top-p) sampling of the pitch and the duration token of every (node, slot) row of the content logits, and sampling
+// of the bar structure from the structure logits.
 //
 //   k_sample_tokens : one wave per row of 230 logits (920 B, read once), 8 B of tokens written.  Lane l holds the columns
 //                     l, l + 64, l + 128, l + 192 (four coalesced 256-byte wave loads; the last one 38 lanes wide), so a
@@ -13,6 +14,17 @@
 //   k_sample_chords : chord-aware sampling (PmChordRules): one wave per node, its 15 slots decided in order as notes, one EOS,
 //                     then PAD, under per-track rules (note counts, a pitch mask, no pitch twice); the same lane layout, the
 //                     same noise stream and the same filters, applied to the candidates of each slot.
+//   k_sample_structure : structure sampling (PmStructureRules): which of the 4 x 32 (track, timestep) cells of every bar are active,
+//                     drawn from the structure logits under per-track rules (a bias, the least and the most active cells, the
+//                     allowed timesteps).  A bar per half-wave, as k_binary_from_logits (csrc/generate.hip): lane t of the half
+//                     holds the four cells of timestep t, one per track, so a track's 32 cells lie across the 32 lanes of the
+//                     half and a bar's logits are four coalesced 128-byte loads.  512 B read and 128 / 512 B (+ 16 B of counts)
+//                     written per bar, each once.  The rank of a cell is an all-pairs count inside the half: every allowed
+//                     timestep of the track is broadcast once (v_readlane of both halves, a select) and compared with the
+//                     lane's own cell; no LDS, no atomics.  The rules are launch constants, so the allowed timesteps are a
+//                     scalar loop over the bits of the mask, and a track whose bounds cannot bind (0 .. 32) skips the pass
+//                     wave-uniformly.  NOISE = false (temperature 0) compiles the hash and the two logf away.  The lanes of a
+//                     half without a bar (odd G, the last wave) take part in every cross-lane step and store nothing.
 #include "common.h"
 
 namespace {
@@ -310,6 +322,85 @@ __global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__
   if (note_count && lane == 0) note_count[n] = count;
 }
 
+// ---- structure sampling ("Structure sampling", PmStructureRules) -----------------------------------------------------
+template <bool NOISE>
+__global__ void __launch_bounds__(256) k_sample_structure(const float* __restrict__ s_logits, int G, const PmStructureRules R,
+                                                          float inv_t, uint32_t seed, float* __restrict__ s_f32,
+                                                          uint8_t* __restrict__ s_u8, int* __restrict__ track_count) {
+  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
+  const int64_t g = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
+  const bool valid = g < G;
+  const uint32_t key = NOISE ? pm_edge_key(seed, 2u, (uint32_t)g) : 0u;
+  bool allow[4], on[4];
+  unsigned sk[4];                                                               // ukey(score)
+  float x[4];
+  uint32_t any = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) x[k] = valid ? s_logits[(g * 4 + k) * 32 + t] : 0.f;   // four loads in flight
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    allow[k] = (R.step_mask[k] >> t) & 1u;
+    float score = __fsub_rn(x[k], R.bias[k]);
+    if (NOISE) {
+      const uint32_t h = pm_group_hash(key, (uint32_t)(32 * k + t));
+      const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23: exact, inside (0, 1)
+      score = __fadd_rn(__fmul_rn(score, inv_t), __fsub_rn(logf(u), logf(1.0f - u)));
+    }
+    sk[k] = ukey(score);
+    const bool nonneg = !(score < 0.f);
+    const int mn = R.min_active[k], mx = R.max_active[k];
+    if (mn == 0 && mx == 32) {                                                  // (wave-uniform) no bound can bind
+      on[k] = allow[k] && nonneg;
+    } else if (mx == 0) {                                                       // (wave-uniform) muted
+      on[k] = false;
+    } else {
+      // cells of the track that outrank this lane's: a higher key, or the same key at a lower timestep
+      int rank = 0;
+      for (uint32_t m = R.step_mask[k]; m; m &= m - 1u) {                       // (scalar loop: the allowed timesteps)
+        const int l = __builtin_ctz(m);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)sk[k], l);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)sk[k], l + 32);
+        const unsigned s = half ? hi : lo;
+        rank += (s > sk[k] || (s == sk[k] && l < t)) ? 1 : 0;
+      }
+      on[k] = allow[k] && (rank < mn || (rank < mx && nonneg));
+    }
+    any |= (uint32_t)(__ballot(valid && on[k]) >> (32 * half));
+  }
+  // no empty bar: the best allowed cell of the tracks that are not muted, the lowest cell index on ties
+  if (__ballot(valid && any == 0u) != 0ull) {                                   // (wave-uniform)
+    unsigned bk = 0u;
+    int bc = 0x7fffffff;
+#pragma unroll
+    for (int k = 3; k >= 0; --k)
+      if (allow[k] && R.max_active[k] > 0 && (bc == 0x7fffffff || sk[k] >= bk)) { bk = sk[k]; bc = 32 * k + t; }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {                                          // stays inside the half
+      const unsigned ok = (unsigned)__shfl_xor((int)bk, o, 64);
+      const int oc = __shfl_xor(bc, o, 64);
+      if (oc != 0x7fffffff && (bc == 0x7fffffff || ok > bk || (ok == bk && oc < bc))) { bk = ok; bc = oc; }
+    }
+    if (any == 0u && (bc & 31) == t) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) on[k] = on[k] || bc == 32 * k + t;
+    }
+  }
+  int mine = 0;                                                                 // lane k < 4 of the half: the count of track k
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int n = __popc((uint32_t)(__ballot(valid && on[k]) >> (32 * half)));
+    if (t == k) mine = n;
+  }
+  if (!valid) return;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t i = (g * 4 + k) * 32 + t;
+    if (s_f32) s_f32[i] = on[k] ? 1.0f : 0.0f;
+    if (s_u8) s_u8[i] = on[k] ? 1 : 0;
+  }
+  if (track_count && t < 4) track_count[g * 4 + t] = mine;
+}
+
 }  // namespace
 
 extern "C" uint32_t pm_sample_hash(uint32_t seed, uint32_t row, uint32_t head, uint32_t token) {
@@ -370,5 +461,29 @@ extern "C" int pm_sample_chords(const float* c_logits, const uint8_t* node_track
       hipLaunchKernelGGL(k_sample_chords<SAMPLE_PLAIN>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
                          seed, tokens, note_count);
   }
+  return pm_check_launch();
+}
+
+extern "C" int pm_sample_structure(const float* s_logits, int32_t G, const PmStructureRules* rules, uint32_t seed, float* s_f32,
+                                   uint8_t* s_u8, int32_t* track_count, pm_stream_t stream) {
+  if (!s_logits || !rules || (!s_f32 && !s_u8) || G <= 0) return PM_E_INVALID;
+  const PmStructureRules R = *rules;
+  const float FMAX = 3.4028234663852886e38f;
+  if (!(R.temperature >= 0.f) || !(R.temperature <= FMAX)) return PM_E_INVALID;                   // NaN, inf, negative
+  bool some = false;
+  for (int k = 0; k < 4; ++k) {
+    if (!(R.bias[k] >= -FMAX) || !(R.bias[k] <= FMAX)) return PM_E_INVALID;
+    if (R.min_active[k] < 0 || R.max_active[k] > 32 || R.min_active[k] > R.max_active[k]) return PM_E_INVALID;
+    if (R.min_active[k] > __builtin_popcount(R.step_mask[k])) return PM_E_INVALID;
+    some = some || (R.max_active[k] > 0 && R.step_mask[k] != 0u);
+  }
+  if (!some) return PM_E_INVALID;
+  const dim3 grid((unsigned)pm_cdiv(G, 8)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (R.temperature == 0.f)
+    hipLaunchKernelGGL(k_sample_structure<false>, grid, block, 0, st, s_logits, G, R, 1.f, seed, s_f32, s_u8, track_count);
+  else
+    hipLaunchKernelGGL(k_sample_structure<true>, grid, block, 0, st, s_logits, G, R, (float)(1.0 / (double)R.temperature), seed,
+                       s_f32, s_u8, track_count);
   return pm_check_launch();
 }

@@ -38,9 +38,40 @@ def pitch_mask(lo: int = 0, hi: int = 127, pitch_classes=None) -> np.ndarray:
     return m
 
 
-def _decode(vae, z, s_cond, s_tensor_cond):
-    """the decoder pass of `generate_music`: (c_logits [N,15,230] fp32, s_tensor)"""
+@dataclass
+class StructureRules:
+    """The per-track rules of structure sampling (`generate_music(structure_rules=...)`, `ops.sample_structure`): one
+    `temperature` (finite, >= 0; 0 = no noise), `threshold` a number or four numbers in (0, 1) (Drums, Bass, Guitar,
+    Strings), `min_active` and `max_active` an int or four ints (0 <= min_active <= max_active <= 32; max_active 0 mutes the
+    track), `allowed_steps` None (every step) or a bool array-like [4,32] whose rows `step_mask` helps fill."""
+    temperature: Any = 1.0
+    threshold: Any = 0.5
+    min_active: Any = 0
+    max_active: Any = 32
+    allowed_steps: Any = None
+
+
+def step_mask(every: int = 1, offset: int = 0, lo: int = 0, hi: int = 31) -> np.ndarray:
+    """bool [32]: the timesteps lo..hi (inclusive) of a bar that lie on the grid offset, offset + every, ...: one track's row
+    of `StructureRules.allowed_steps` (a grid and a window)."""
+    if int(every) < 1:
+        raise ValueError(f"every must be an int >= 1, got {every!r}")
+    t = np.arange(32)
+    return (t >= lo) & (t <= hi) & (t >= offset) & ((t - offset) % int(every) == 0)
+
+
+def _decode(vae, z, s_cond, s_tensor_cond, rules=None, seed=None):
+    """the decoder pass of `generate_music`: (c_logits [N,15,230] fp32, s_tensor).  With `rules` (a StructureRules) the
+    structure is drawn from the structure logits on the device under `seed` and the content decoder runs on its bar graphs."""
     vae.decoder.__dict__.pop("_last_structure", None)
+    if rules is not None:
+        with torch.no_grad():
+            s_logits = vae.engine.structure_only(z.contiguous().float(), vae.training)
+        s_tensor = ops.sample_structure(s_logits.detach().contiguous().float(), rules.temperature, rules.threshold,
+                                        rules.min_active, rules.max_active, rules.allowed_steps, seed)
+        graph = vae.decoder._structure_from_binary(s_tensor)     # (no bar is empty: s_tensor stays as drawn)
+        _, c_logits = vae.decoder(z, graph)
+        return c_logits.detach().contiguous().float(), s_tensor
     s_logits, c_logits = vae.decoder(z, s_cond)
     if s_tensor_cond is not None:
         s_tensor = s_tensor_cond
@@ -52,7 +83,7 @@ def _decode(vae, z, s_cond, s_tensor_cond):
 
 
 def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
-                   return_tokens=False, chord_rules=None, return_note_counts=False):
+                   return_tokens=False, chord_rules=None, return_note_counts=False, structure_rules=None):
     """generate.py:21-37.  `s_cond` is a batch of bar graphs (`vae.decoder._structure_from_binary`) or None (the
     structure then comes from the decoder's own thresholded logits); `s_tensor_cond` [B,n_bars,4,32] is the binary
     structure the pianoroll is laid out on when given.  Returns (mtp [B,n_bars,4,32,15,230], s_tensor bool).
@@ -68,15 +99,31 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     With `chord_rules` (a `ChordRules`) the call samples chord by chord (`ops.sample_chords`: notes, one EOS, then PAD; no
     pitch twice in a chord; per-track note counts and allowed pitches), so `muspy_from_mtp` reads exactly the drawn notes.
     `temperature` defaults to 1.0 and may be a pair (pitch, duration); 0 = arg-max under the rules.  `return_note_counts`
-    appends the int32 [N] note counts behind the tokens.  Bad rules raise before the model is touched."""
+    appends the int32 [N] note counts behind the tokens.  Bad rules raise before the model is touched.
+
+    With `structure_rules` (a `StructureRules`; needs `s_cond` and `s_tensor_cond` both None) the structure itself is drawn
+    on the device from the model's structure logits (`ops.sample_structure`: per-track threshold, least and most active
+    cells, allowed steps) instead of thresholded: the content decoder runs on the drawn structure, the pianoroll is laid out
+    on it and it is the `s_tensor` returned.  It combines with every content mode above.  One `seed` drives both levels
+    (None draws one, once); the bars are numbered along the batch, so a `z` that repeats one latent gives several takes
+    with different rhythms.  No host read is added to the one that sizes the bar graphs."""
+    if structure_rules is not None:
+        if not isinstance(structure_rules, StructureRules):
+            raise ValueError(f"structure_rules must be a StructureRules, got {structure_rules!r}")
+        if s_cond is not None or s_tensor_cond is not None:
+            raise ValueError("structure_rules draws the structure itself: it needs s_cond and s_tensor_cond both None")
+        ops.check_structure_args(structure_rules.temperature, structure_rules.threshold, structure_rules.min_active,
+                                 structure_rules.max_active, structure_rules.allowed_steps, seed)
     if chord_rules is not None:
         return _generate_chords(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, return_tokens, chord_rules,
-                                return_note_counts)
+                                return_note_counts, structure_rules)
     if return_note_counts:
         raise ValueError("return_note_counts needs chord_rules")
     ops.check_sampling_args(temperature, top_k, top_p, seed)
     sampled = temperature is not None or top_k is not None or top_p is not None
-    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond)
+    if structure_rules is not None and seed is None:
+        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
     if not sampled:
         mtp = ops.mtp_from_logits(c_logits, s_tensor)
         return (mtp, s_tensor, ops.sample_tokens(c_logits, temperature=0.0)) if return_tokens else (mtp, s_tensor)
@@ -88,12 +135,14 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
 
 
 def _generate_chords(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, return_tokens, chord_rules,
-                     return_note_counts):
+                     return_note_counts, structure_rules=None):
     if not isinstance(chord_rules, ChordRules):
         raise ValueError(f"chord_rules must be a ChordRules, got {chord_rules!r}")
     ops.check_chord_args(temperature, top_k, top_p, seed, chord_rules.min_notes, chord_rules.max_notes,
                          chord_rules.allowed_pitches)
-    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond)
+    if structure_rules is not None and seed is None:             # one seed for both levels, drawn before the structure
+        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
     if seed is None:
         seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
     track = ops.node_tracks(s_tensor, c_logits.shape[0], check=False)

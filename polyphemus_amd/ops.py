@@ -363,6 +363,80 @@ def sample_chords(c_logits: torch.Tensor, node_track: torch.Tensor, temperature=
     return tokens, note_count
 
 
+def check_structure_args(temperature=1.0, threshold=0.5, min_active=0, max_active=32, allowed_steps=None, seed=None):
+    """The argument rules of structure sampling (`sample_structure`, `generate.generate_music(structure_rules=...)`): raises
+    ValueError naming the argument, before anything touches the device.  `temperature` is a finite number >= 0; `threshold`
+    a number or four numbers (Drums, Bass, Guitar, Strings) in (0, 1); `min_active` / `max_active` an int or four ints with
+    0 <= min_active <= max_active <= 32 and min_active no larger than the track's allowed steps; `allowed_steps` None or a
+    bool array-like [4,32]; some track must keep max_active > 0 and an allowed step.
+    Returns (temperature, bias [4] = logit(threshold) in double, min_active [4], max_active [4], step_mask: 4 words of 32 bits)."""
+    import math
+    import numbers
+    import numpy as np
+    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    integer = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if not (real(temperature) and math.isfinite(temperature) and temperature >= 0):
+        raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
+    check_sampling_args(None, None, None, seed)
+    th = tuple(threshold) if isinstance(threshold, (tuple, list, np.ndarray)) else (threshold,) * 4
+    if len(th) != 4 or not all(real(v) and 0 < v < 1 for v in th):
+        raise ValueError(f"threshold must be a number or four numbers (one per track) in (0, 1), got {threshold!r}")
+    bias = tuple(math.log(float(v) / (1.0 - float(v))) for v in th)          # (finite in fp32 for every double in (0, 1))
+
+    def four(v, name):
+        out = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else (v,) * 4
+        if len(out) != 4 or not all(integer(a) for a in out):
+            raise ValueError(f"{name} must be an int or four ints (one per track), got {v!r}")
+        return tuple(int(a) for a in out)
+    mx = four(max_active, "max_active")
+    if not all(0 <= a <= 32 for a in mx):
+        raise ValueError(f"max_active must be in [0, 32], got {max_active!r}")
+    mn = four(min_active, "min_active")
+    if not all(0 <= a <= b for a, b in zip(mn, mx)):
+        raise ValueError(f"min_active must satisfy 0 <= min_active <= max_active = {max_active!r}, got {min_active!r}")
+    if allowed_steps is None:
+        words = [0xFFFFFFFF] * 4
+    else:
+        a = allowed_steps.detach().cpu().numpy() if isinstance(allowed_steps, torch.Tensor) else np.asarray(allowed_steps)
+        if a.shape != (4, 32) or a.dtype != np.bool_:
+            raise ValueError(f"allowed_steps must be a bool array of shape [4,32], got {a.dtype} {tuple(a.shape)}")
+        words = [int(w) for w in (a.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1)]
+    steps = [bin(w).count("1") for w in words]
+    if not all(a <= n for a, n in zip(mn, steps)):
+        raise ValueError(f"min_active must not exceed the allowed steps of its track ({steps} in allowed_steps), got {min_active!r}")
+    if not any(b > 0 and n > 0 for b, n in zip(mx, steps)):
+        raise ValueError(f"no track is left with max_active > 0 and an allowed step: max_active = {max_active!r}, "
+                         f"allowed_steps leaves {steps} steps")
+    return float(temperature), bias, mn, mx, words
+
+
+def sample_structure(s_logits: torch.Tensor, temperature: float = 1.0, threshold=0.5, min_active=0, max_active=32,
+                     allowed_steps=None, seed: int = 0, return_counts: bool = False):
+    """`pm_sample_structure` ("Structure sampling" in include/polyphemus_hip.h): the active cells of every bar of `s_logits`
+    ([...,4,32] fp32) drawn from the model's probabilities, a cell on with probability sigmoid((x - logit(threshold)) /
+    temperature) where no bound binds (temperature 0 = the thresholded structure), each track keeping between `min_active`
+    and `max_active` cells on the steps `allowed_steps` ([4,32] bool, None = all) gives it, and no bar left empty.  The bars
+    are numbered along the flattened leading dimensions; a pure function of the logits, the rules and `seed`.  Returns a
+    bool tensor of s_logits' shape, and with `return_counts` the int32 [...,4] active cells per (bar, track)."""
+    from ._lib import PmStructureRules
+    T, bias, mn, mx, words = check_structure_args(temperature, threshold, min_active, max_active, allowed_steps, seed)
+    _chk(s_logits, F32, "s_logits")
+    if s_logits.dim() < 2 or s_logits.shape[-2:] != (4, 32):
+        raise ValueError("s_logits must be [..., 4, 32]")
+    G, dev = s_logits.numel() // 128, s_logits.device
+    if G >= 1 << 31:
+        raise ValueError(f"s_logits holds {G} bars, the kernel takes fewer than 2^31")
+    out = torch.empty(s_logits.shape, dtype=U8, device=dev)
+    counts = torch.empty(*s_logits.shape[:-2], 4, dtype=I32, device=dev) if return_counts else None
+    if G:
+        rules = PmStructureRules()
+        rules.temperature = T
+        for k in range(4):
+            rules.bias[k], rules.min_active[k], rules.max_active[k], rules.step_mask[k] = bias[k], mn[k], mx[k], words[k]
+        call("pm_sample_structure", ptr(s_logits), G, ctypes.addressof(rules), int(seed), None, ptr(out), ptr(counts), stream())
+    return (out.view(torch.bool), counts) if return_counts else out.view(torch.bool)
+
+
 def gcl_forward_fused(x, T, plan: Plan, dropout_p: float, seed: int, layer_uid: int, w_frag, bias, col_stats=None,
                       planes=None, use_classes: bool = True):
     """`pm_gcl_forward_fused`: h = A'(x) @ [W_t; W_4; W_5; root] + bias of one GCL layer in one kernel (compact graphs,
