@@ -66,7 +66,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   (pm_grad_sumsq, pm_grad_nonfinite_check_sumsq, pm_grad_clip_finish, pm_adam_step_clipped; the PM_CLIP_* layout); the
  *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap); sampled generation
  *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash); chord-aware sampling (pm_sample_chords, pm_node_tracks; the
- *   PmChordRules struct); structure sampling (pm_sample_structure; the PmStructureRules struct). */
+ *   PmChordRules struct); structure sampling (pm_sample_structure; the PmStructureRules struct); note events
+ *   (pm_notes_from_tokens). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -341,6 +342,38 @@ typedef struct PmStructureRules {
 int pm_sample_structure(const float* s_logits /* [G,4,32] */, int32_t G, const PmStructureRules* rules, uint32_t seed,
                         float* s_f32 /* [G,4,32] or NULL */, uint8_t* s_u8 /* [G,4,32] or NULL */,
                         int32_t* track_count /* [G,4] or NULL */, pm_stream_t stream);
+
+/* ------------------------------------------------------------------ Note events
+ * The reference turns a generated pianoroll into notes on the host (`muspy_from_mtp`, utils.py:83-124): a Python loop over
+ * every (track, time, slot) with two arg-maxes and three `.item()` reads each.  pm_notes_from_tokens reads the same notes out
+ * of the tokens of sampled generation, on the device, without the pianoroll: the result is exactly
+ * muspy_from_mtp(pm_mtp_from_tokens(tokens, s_tensor)[i]) for every piece i.  Additive, same ABI version.
+ *
+ * s_tensor is [G,4,32] with G = B * n_bars: bar g = i * n_bars + b of piece i, track k, timestep s; the cell's time is
+ * t = 32 b + s.  Nodes are numbered in cell order as in pm_node_tracks.  The 15 slots of an active cell are walked in order:
+ *   stop   at a pitch of 129 (EOS) or 130 (PAD), or a duration token of 97 (EOS) or 98 (PAD);
+ *   skip   a pitch of 128 (SOS);
+ *   emit   otherwise the row (t, pitch, min(duration token + 1, 32 n_bars - t)).
+ * The reference never tests for a duration SOS (utils.py:114-115 tests the pitch twice), so a duration token of 96 is a note
+ * of length 97 before the clamp.  A token outside its head's range reads as 0, the arg-max of the all-zero head that
+ * pm_mtp_from_tokens leaves.  An inactive cell emits nothing, nor does a cell whose node index is >= N.
+ *   notes     [capacity,3] int32 (time, pitch, duration): the rows of (piece i, track k) are
+ *             notes[track_ptr[4i+k] : track_ptr[4i+k+1]], inside that range by time, then by slot — the order in which the
+ *             reference appends them.  Rows at M and beyond are not written.
+ *   track_ptr [4B+1]; track_ptr[4B] = totals[0] = M, the number of notes; totals[1] = the number of active cells, which the
+ *             caller compares with N as for pm_mtp_from_tokens.
+ *   scratch   seg_count [4G] and seg_ptr [4G+1] (segment (4i+k) * n_bars + b = one track of one bar), bar_nodes [G] and
+ *             node_ptr [G+1] as for pm_node_tracks.
+ * Five launches on the stream (cells per bar, their scan, notes per segment, their scan, the rows), no host read, no atomics:
+ * two calls on the same inputs write the same bytes.  120 B are read per node and at most 180 B written.
+ * PM_E_INVALID (before any launch, so no kernel can write past `notes`): capacity < 15 N; G <= 0, n_bars <= 0 or
+ *   G % n_bars != 0; N < 0 or 15 N >= 2^31; G * 128 >= 2^31; a NULL pointer (tokens and notes may be NULL when N == 0); tokens
+ *   not 8-byte aligned; any two of the scratch and output buffers overlapping. */
+int pm_notes_from_tokens(const int32_t* tokens /* [N,15,2] pitch, duration */, const float* s_tensor /* [G,4,32] 0/1 */,
+                         int32_t G, int32_t n_bars, int64_t N, int32_t* seg_count /* [4G] ws */,
+                         int32_t* seg_ptr /* [4G+1] ws */, int32_t* bar_nodes /* [G] ws */, int32_t* node_ptr /* [G+1] ws */,
+                         int32_t* notes /* [capacity,3] */, int64_t capacity, int32_t* track_ptr /* [4B+1] */,
+                         int32_t* totals /* [2]: notes M, active cells */, pm_stream_t stream);
 
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):

@@ -1,7 +1,8 @@
 """Host mirror of the reference's generation entry points (generate.py:21-37, 90-98) over the device kernels of
 csrc/generate.hip and csrc/graph.hip: the decoder pass, the thresholded structure, and the dense multitrack pianoroll,
 without the reference's host synchronisations (`nonzero`, per-sample Python graph building, three full-tensor writes).
-Converting the pianoroll to MIDI (muspy) is outside the hot path and stays with the caller."""
+Converting the pianoroll to MIDI (muspy) is outside the hot path and stays with the caller; `generate_notes` returns the
+pieces as ordered note events instead (`NoteBatch`, csrc/notes.hip), which is what that conversion reads out of the pianoroll."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -107,6 +108,26 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     on it and it is the `s_tensor` returned.  It combines with every content mode above.  One `seed` drives both levels
     (None draws one, once); the bars are numbered along the batch, so a `z` that repeats one latent gives several takes
     with different rhythms.  No host read is added to the one that sizes the bar graphs."""
+    tokens, s_tensor, note_count, c_logits = _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed,
+                                                              chord_rules, structure_rules, return_note_counts, return_tokens)
+    if c_logits is not None:                                     # the reference's call: the active cells hold the logits
+        mtp = ops.mtp_from_logits(c_logits, s_tensor)
+    else:
+        mtp = ops.mtp_from_tokens(tokens, s_tensor)              # its check is the call's one host read
+    out = (mtp, s_tensor)
+    if return_tokens:
+        out += (tokens,)
+    if return_note_counts:
+        out += (note_count,)
+    return out
+
+
+def _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules, structure_rules,
+                     return_note_counts=False, argmax_tokens=True):
+    """The part `generate_music` and `generate_notes` share: the argument checks, the seed, the decoder pass and the draw.
+    Returns (tokens int32 [N,15,2], s_tensor, note_count int32 [N] or None without chord rules, c_logits): c_logits is None
+    in every sampled mode; in the unsampled one it holds the content logits and `tokens` their arg-max (None when
+    `argmax_tokens` is off: the caller lays the logits out and wants no tokens)."""
     if structure_rules is not None:
         if not isinstance(structure_rules, StructureRules):
             raise ValueError(f"structure_rules must be a StructureRules, got {structure_rules!r}")
@@ -115,43 +136,87 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
         ops.check_structure_args(structure_rules.temperature, structure_rules.threshold, structure_rules.min_active,
                                  structure_rules.max_active, structure_rules.allowed_steps, seed)
     if chord_rules is not None:
-        return _generate_chords(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, return_tokens, chord_rules,
-                                return_note_counts, structure_rules)
-    if return_note_counts:
-        raise ValueError("return_note_counts needs chord_rules")
-    ops.check_sampling_args(temperature, top_k, top_p, seed)
-    sampled = temperature is not None or top_k is not None or top_p is not None
-    if structure_rules is not None and seed is None:
-        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
-    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
-    if not sampled:
-        mtp = ops.mtp_from_logits(c_logits, s_tensor)
-        return (mtp, s_tensor, ops.sample_tokens(c_logits, temperature=0.0)) if return_tokens else (mtp, s_tensor)
-    if seed is None:
-        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
-    tokens = ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed)
-    mtp = ops.mtp_from_tokens(tokens, s_tensor)
-    return (mtp, s_tensor, tokens) if return_tokens else (mtp, s_tensor)
-
-
-def _generate_chords(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, return_tokens, chord_rules,
-                     return_note_counts, structure_rules=None):
-    if not isinstance(chord_rules, ChordRules):
-        raise ValueError(f"chord_rules must be a ChordRules, got {chord_rules!r}")
-    ops.check_chord_args(temperature, top_k, top_p, seed, chord_rules.min_notes, chord_rules.max_notes,
-                         chord_rules.allowed_pitches)
+        if not isinstance(chord_rules, ChordRules):
+            raise ValueError(f"chord_rules must be a ChordRules, got {chord_rules!r}")
+        ops.check_chord_args(temperature, top_k, top_p, seed, chord_rules.min_notes, chord_rules.max_notes,
+                             chord_rules.allowed_pitches)
+        sampled = True
+    else:
+        if return_note_counts:
+            raise ValueError("return_note_counts needs chord_rules")
+        ops.check_sampling_args(temperature, top_k, top_p, seed)
+        sampled = temperature is not None or top_k is not None or top_p is not None
     if structure_rules is not None and seed is None:             # one seed for both levels, drawn before the structure
         seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
     c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
+    if not sampled:
+        return (ops.sample_tokens(c_logits, temperature=0.0) if argmax_tokens else None), s_tensor, None, c_logits
     if seed is None:
         seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+    if chord_rules is None:
+        tokens = ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed)
+        return tokens, s_tensor, None, None
     track = ops.node_tracks(s_tensor, c_logits.shape[0], check=False)
     tokens, note_count = ops.sample_chords(c_logits, track, 1.0 if temperature is None else temperature, top_k, top_p, seed,
                                            chord_rules.min_notes, chord_rules.max_notes, chord_rules.allowed_pitches)
-    mtp = ops.mtp_from_tokens(tokens, s_tensor)                  # its check is the call's one host read
-    out = (mtp, s_tensor)
-    if return_tokens:
-        out += (tokens,)
-    if return_note_counts:
-        out += (note_count,)
-    return out
+    return tokens, s_tensor, note_count, None
+
+
+TRACKS = ("Drums", "Bass", "Guitar", "Strings")                 # constants.py:5
+
+
+@dataclass
+class NoteBatch:
+    """A batch of generated pieces as note events on the device (`generate_notes`, `ops.notes_from_tokens`): `notes` int32
+    [15 N,3] rows (time, pitch, duration) in steps of a 1 / `resolution` beat, `track_ptr` int32 [4B+1] (the rows of piece i,
+    track k are notes[track_ptr[4i+k]:track_ptr[4i+k+1]], by time, then by slot), `totals` int32 [2] (notes M, active cells);
+    rows from M on are not written.  A piece is `n_bars` bars of 32 steps."""
+    notes: torch.Tensor
+    track_ptr: torch.Tensor
+    totals: torch.Tensor
+    n_bars: int
+    resolution: int = 8
+
+    def tolist(self):
+        """One host synchronisation: per piece, four lists (Drums, Bass, Guitar, Strings) of (time, pitch, duration)."""
+        ptr = self.track_ptr.cpu().tolist()
+        rows = list(zip(*self.notes[:ptr[-1]].cpu().t().tolist()))          # (time, pitch, duration) tuples of Python ints
+        return [[rows[ptr[4 * i + k]:ptr[4 * i + k + 1]] for k in range(4)] for i in range((len(ptr) - 1) // 4)]
+
+    def looped(self, n_loops: int):
+        """`loop_muspy_music` (utils.py:144-160) on the lists of `tolist()`: behind every track's notes come its copies
+        r = 1 .. n_loops - 1, each `r * 32 * n_bars` steps later."""
+        span = 32 * self.n_bars
+        return [[track + [(t + r * span, p, d) for r in range(1, int(n_loops)) for (t, p, d) in track] for track in piece]
+                for piece in self.tolist()]
+
+    def to_muspy(self, i: int, programs):
+        """The `muspy.Music` the reference's `muspy_from_mtp` (utils.py:126-141) builds for piece `i`: four tracks named as
+        TRACKS, Drums the drum track with program 0, the others with `programs[name]` (the caller's
+        `generation_config.MIDI_PROGRAMS`), velocity 64."""
+        try:
+            import muspy
+        except ImportError as e:
+            raise ImportError("NoteBatch.to_muspy needs the muspy package (`pip install muspy`); tolist() and looped() give "
+                              "the same notes as plain tuples without it") from e
+        piece = self.tolist()[i]
+        tracks = []
+        for name, rows in zip(TRACKS, piece):
+            is_drum = name == "Drums"
+            tracks.append(muspy.Track(name=name, is_drum=is_drum, program=0 if is_drum else programs[name],
+                                      notes=[muspy.Note(t, p, d, 64) for (t, p, d) in rows]))
+        return muspy.Music(tracks=tracks, metadata=muspy.Metadata(), resolution=self.resolution)
+
+
+def generate_notes(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
+                   chord_rules=None, structure_rules=None, return_tokens=False):
+    """`generate_music` without the pianoroll: the same arguments, checks, seed handling and draws in every mode (unsampled =
+    the arg-max tokens), but the pieces come back as a `NoteBatch` — the notes the reference's `muspy_from_mtp` would read out
+    of `generate_music`'s `mtp`, in its order — read from the tokens on the device (`ops.notes_from_tokens`).  Returns
+    (NoteBatch, s_tensor), with `return_tokens` the int32 [N,15,2] tokens appended.  One host read beyond the one that sizes
+    the bar graphs: the check that the structure has as many active cells as the decoder gave nodes."""
+    tokens, s_tensor, _, _ = _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules,
+                                              structure_rules)
+    notes, track_ptr, totals = ops.notes_from_tokens(tokens, s_tensor)
+    batch = NoteBatch(notes, track_ptr, totals, int(s_tensor.shape[1]))
+    return (batch, s_tensor, tokens) if return_tokens else (batch, s_tensor)

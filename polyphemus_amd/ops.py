@@ -283,6 +283,42 @@ def node_tracks(s_tensor: torch.Tensor, N: int, check: bool = True) -> torch.Ten
     return out
 
 
+def notes_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool = True):
+    """`pm_notes_from_tokens` ("Note events" in include/polyphemus_hip.h): the notes the reference's `muspy_from_mtp` reads out
+    of `mtp_from_tokens(tokens, s_tensor)`, without the pianoroll.  `tokens` int32 [N,15,2], `s_tensor` [B,n_bars,4,32] of any
+    dtype.  Returns (notes int32 [15 N,3] = time, pitch, duration; track_ptr int32 [4B+1]; totals int32 [2] = notes M, active
+    cells), all on the device: the rows of (piece i, track k) are notes[track_ptr[4i+k]:track_ptr[4i+k+1]] by time, then by
+    slot, and rows from M on are not written.  `check` reads `totals` back (one host sync) and raises like `mtp_from_tokens`
+    when the active cells differ from N."""
+    if not isinstance(tokens, torch.Tensor) or not isinstance(s_tensor, torch.Tensor):
+        raise ValueError("tokens and s_tensor must be tensors")
+    if tokens.dtype != I32 or tokens.dim() != 3 or tokens.shape[1:] != (C.MAX_SIMU_TOKENS - 1, 2):
+        raise ValueError(f"tokens must be int32 [N,15,2], got {tokens.dtype} {tuple(tokens.shape)}")
+    if s_tensor.dim() != 4 or s_tensor.shape[-2:] != (4, 32) or s_tensor.shape[0] == 0 or s_tensor.shape[1] == 0:
+        raise ValueError(f"s_tensor must be [B,n_bars,4,32] with B, n_bars >= 1, got {tuple(s_tensor.shape)}")
+    for t, name in ((tokens, "tokens"), (s_tensor, "s_tensor")):
+        if not t.is_cuda:
+            raise HipExtensionError(f"{name} lives on {t.device}: the HIP path needs device tensors (no CPU fallback)")
+    if s_tensor.device != tokens.device:
+        raise ValueError(f"s_tensor lives on {s_tensor.device}, tokens on {tokens.device}")
+    tokens = tokens.contiguous()
+    s = s_tensor.to(F32).contiguous()
+    B, n_bars = s_tensor.shape[:2]
+    G, N, dev = B * n_bars, tokens.shape[0], tokens.device
+    cap = (C.MAX_SIMU_TOKENS - 1) * N
+    ws = torch.empty(4 * G + (4 * G + 1) + G + (G + 1), dtype=I32, device=dev)
+    seg_count, seg_ptr, bn, npt = ws.split([4 * G, 4 * G + 1, G, G + 1])
+    notes = torch.empty(cap, 3, dtype=I32, device=dev)
+    track_ptr, totals = torch.empty(4 * B + 1, dtype=I32, device=dev), torch.empty(2, dtype=I32, device=dev)
+    call("pm_notes_from_tokens", ptr(tokens) if N else None, ptr(s), G, n_bars, N, ptr(seg_count), ptr(seg_ptr), ptr(bn), ptr(npt),
+         ptr(notes) if N else None, cap, ptr(track_ptr), ptr(totals), stream())
+    if check:
+        active = int(totals[1])
+        if active != N:
+            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, tokens has {N} nodes")
+    return notes, track_ptr, totals
+
+
 def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
                      c_logits=None, node_track=None):
     """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
