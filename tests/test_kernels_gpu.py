@@ -686,22 +686,29 @@ def test_chord_encoder_as_table_algebra(small, d, S):
 
 
 # ------------------------------------------------------------------ pooling / broadcast
-@pytest.mark.parametrize("d", [32, 256])
-def test_attention_pool_fwd_bwd(small, d):
+@pytest.mark.parametrize("d,gated", [(32, False), (256, False), (512, False), (1024, False), (256, True), (1024, True)],
+                         ids=["32", "256", "512", "1024", "256-x_gate", "1024-x_gate"])
+def test_attention_pool_fwd_bwd(small, d, gated):
+    """d = 512 / 1024: the second to fourth float4 of a lane's gate-weight accumulator in k_attnpool_bwd2 (1024 is the entry
+    point's maximum).  x_gate: the gate is computed from a second tensor xg != x (the gate input under dropout in the gate MLP),
+    the pool runs over x; dx and dx_gate against autograd with respect to x and xg separately."""
     b, plan = small
     torch.manual_seed(d)
     N, G = plan.N, plan.G
     x = torch.randn(N, d, device=DEV)
+    xg = ops.dropout_rows(x, d, 0.25, 99 + d, 3) if gated else x
+    assert not gated or (0 < int((xg == 0).sum()) < xg.numel())
     w, bb = torch.randn(d, device=DEV) * 0.2, torch.randn(1, device=DEV)
     bg, bbe = torch.rand(1, device=DEV) + 0.5, torch.randn(1, device=DEV)
     rm, rv = torch.zeros(1, device=DEV), torch.ones(1, device=DEV)
-    g = ops.gate_fwd(x, w, bb)
+    g = ops.gate_fwd(xg, w, bb)
     gm, gv = ops.bn_stats(g, N, 1, 1, rm, rv)
     alpha, out = ops.attnpool_fwd(x, g, gm, gv, bg, bbe, plan)
     seg = (b.bars + b.n_bars * b.batch)
     xr, wr, br = x.double().requires_grad_(True), w.double().requires_grad_(True), bb.double().requires_grad_(True)
+    xgr = xg.double().requires_grad_(True) if gated else xr
     bgr, bber = bg.double().requires_grad_(True), bbe.double().requires_grad_(True)
-    gr = F.batch_norm((xr @ wr + br).view(-1, 1), None, None, bgr, bber, True, 0.1, 1e-5)
+    gr = F.batch_norm((xgr @ wr + br).view(-1, 1), None, None, bgr, bber, True, 0.1, 1e-5)
     gmax = torch.full((G, 1), float("-inf"), dtype=torch.float64, device=DEV).scatter_reduce(0, seg.view(-1, 1), gr, "amax")
     e = (gr - gmax[seg]).exp()
     al = e / (torch.zeros(G, 1, dtype=torch.float64, device=DEV).index_add_(0, seg, e)[seg] + 1e-16)
@@ -710,7 +717,10 @@ def test_attention_pool_fwd_bwd(small, d):
     dout = torch.randn(G, d, device=DEV)
     ref.backward(dout.double())
     dw, db, dbg, dbb = (torch.zeros_like(t) for t in (w, bb, bg, bbe))
-    dx = ops.attnpool_bwd(x, g, gm, gv, bg, alpha, dout, w, plan, dw, db, dbg, dbb)
+    dx = ops.attnpool_bwd(x, g, gm, gv, bg, alpha, dout, w, plan, dw, db, dbg, dbb, x_gate=xg if gated else None)
+    if gated:
+        dx, dxg = dx
+        assert rel_err(dxg, xgr.grad) < 1e-5
     assert rel_err(dx, xr.grad) < 1e-5
     assert rel_err(dw, wr.grad) < 1e-4 and rel_err(dbg, bgr.grad) < 1e-4
     assert float((db.double() - br.grad).abs().max()) < 1e-4 and float((dbb.double() - bber.grad).abs().max()) < 1e-4
@@ -768,7 +778,8 @@ def test_losses_match_reference_formulas(small):
     torch.manual_seed(0)
     N = plan.N
     logits = torch.randn(N, 15, 230, device=DEV) * 2
-    out, dl = ops.content_ce(logits, plan, grad_scale=1.0)
+    dbias = [torch.zeros(v, device=DEV) for v in (131, 131, 99)]
+    out, dl = ops.content_ce(logits, plan, grad_scale=1.0, dbias=dbias)
     lr = logits.double().requires_grad_(True)
     tgt = b.tokens[:, 1:, :].long().reshape(-1, 2)
     lp = F.cross_entropy(lr.view(-1, 230)[:, :131], tgt[:, 0], ignore_index=130)
@@ -777,6 +788,24 @@ def test_losses_match_reference_formulas(small):
     o = out.cpu()
     assert abs(o[0] - lp.item()) < 1e-6 and abs(o[1] - ld.item()) < 1e-6
     assert rel_err(dl, lr.grad) < 1e-5
+    drum = b.is_drum.bool()
+    bias_grads = lambda g: (g[drum][..., :131].sum((0, 1)), g[~drum][..., :131].sum((0, 1)), g[..., 131:].sum((0, 1)))
+    for got, want in zip(dbias, bias_grads(lr.grad)):               # (the bar of the fused head's bias gradients)
+        assert rel_err(got, want) < 1e-4
+    # only the S active slots present in the logits (the others are PAD in every node: no loss, no gradient), S < 15
+    S = b.n_slots
+    assert 1 < S < 15 and bool((b.tokens[:, S + 1:, 0] == 130).all()) and bool((b.tokens[:, S + 1:, 1] == 98).all())
+    logits_s = logits[:, :S].contiguous()
+    out_s = torch.full((4,), float("nan"), dtype=torch.float64, device=DEV)
+    dl_s = torch.full_like(logits_s, float("nan"))
+    dbias_s = [torch.zeros(v, device=DEV) for v in (131, 131, 99)]
+    call("pm_content_ce", ptr(logits_s), ptr(plan.tokens), ptr(plan.tok_hist), ptr(plan.is_drum), N, S, 1.0, ptr(dl_s),
+         ptr(dbias_s[0]), ptr(dbias_s[1]), ptr(dbias_s[2]), ptr(out_s), stream())
+    o = out_s.cpu()
+    assert abs(o[0] - lp.item()) < 1e-6 and abs(o[1] - ld.item()) < 1e-6
+    assert rel_err(dl_s, lr.grad[:, :S]) < 1e-5 and float(lr.grad[:, S:].abs().max()) == 0
+    for got, want in zip(dbias_s, bias_grads(lr.grad)):
+        assert rel_err(got, want) < 1e-4
     mu, lv = torch.randn(16, 32, device=DEV), torch.randn(16, 32, device=DEV) * 0.3
     dmu, dlv = torch.zeros_like(mu), torch.zeros_like(lv)
     ops.kld(mu, lv, out, beta=0.5, dmu=dmu, dlog_var=dlv)

@@ -129,7 +129,7 @@ def _gtm_batch(rank):
     return synthetic_batch(4 + 4 * rank, 2, p=0.25, seed=60 + rank)      # 4 and 8 samples: different token counts
 
 
-def _gtm_worker(rank, world, backend):
+def _gtm_worker(rank, world, backend, d=64):
     import datetime
     import torch.distributed as dist
     dev = torch.device("cuda", rank % torch.cuda.device_count())
@@ -139,12 +139,12 @@ def _gtm_worker(rank, world, backend):
         from polyphemus_amd.model import VAE
         from polyphemus_amd.trainer import HipTrainer
         torch.manual_seed(100)
-        vae = VAE(**CFG, device=dev).to(dev)
+        vae = VAE(**{**CFG, "d": d}, device=dev).to(dev)
         vae.train()
         vae.msg_dropout = 0.0
         tr = HipTrainer(vae, lr=1e-3, global_token_mean=True)
         b = _gtm_batch(rank)
-        eps = torch.randn(b.s_tensor.shape[0] // 2, CFG["d"], generator=torch.Generator().manual_seed(7 + rank)).to(dev)
+        eps = torch.randn(b.s_tensor.shape[0] // 2, d, generator=torch.Generator().manual_seed(7 + rank)).to(dev)
         tr.train_step(b.to(dev), eps)
         torch.cuda.synchronize()
         return tr.grads.detach().cpu().numpy()
@@ -152,12 +152,16 @@ def _gtm_worker(rank, world, backend):
         dist.destroy_process_group()
 
 
-def test_global_token_mean_weights_the_ranks_by_their_token_counts():
+@pytest.mark.parametrize("d", [64, 128])
+def test_global_token_mean_weights_the_ranks_by_their_token_counts(d):
     """CE `ignore_index` means (training.py:316-323) under data parallelism: with `global_token_mean` the summed
     gradient equals sum_r (n_r * world / n_total) * g_r, g_r = the rank's own local-mean gradient — i.e. its mean over the
-    ranks is the gradient of the token mean over the global batch (per-replica BatchNorm statistics apart)."""
+    ranks is the gradient of the token mean over the global batch (per-replica BatchNorm statistics apart).  d = 128: d/2 = 64
+    is a width of the weight-plane kernel of the fused head (k_unembed_ce_planes), which then receives `ce_scale` in a real
+    two-rank run; at d = 64 the head takes the fp32-MFMA kernel."""
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
-    res = run_ranks_sharing_one_gpu(_gtm_worker, 2, (backend,), timeout=120.0)      # a rank that hangs or dies FAILS the test (RanksHung)
+    cfg = {**CFG, "d": d}
+    res = run_ranks_sharing_one_gpu(_gtm_worker, 2, (backend, d), timeout=120.0)      # a rank that hangs or dies FAILS the test (RanksHung)
     got = torch.from_numpy(res[0])
     assert torch.equal(got, torch.from_numpy(res[1]))
     from polyphemus_amd.model import VAE
@@ -165,12 +169,12 @@ def test_global_token_mean_weights_the_ranks_by_their_token_counts():
     grads, counts = [], []
     for rank in range(2):
         torch.manual_seed(100)
-        vae = VAE(**CFG, device="cuda").to("cuda")
+        vae = VAE(**cfg, device="cuda").to("cuda")
         vae.train()
         vae.msg_dropout = 0.0
         tr = HipTrainer(vae, lr=1e-3)
         b = _gtm_batch(rank)
-        eps = torch.randn(b.s_tensor.shape[0] // 2, CFG["d"], generator=torch.Generator().manual_seed(7 + rank)).cuda()
+        eps = torch.randn(b.s_tensor.shape[0] // 2, d, generator=torch.Generator().manual_seed(7 + rank)).cuda()
         tr.train_step(b.to("cuda"), eps)
         grads.append(tr.grads.detach().cpu().double())
         counts.append(float((b.tokens[:, 1:, 0] != 130).sum()))
