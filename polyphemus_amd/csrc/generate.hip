@@ -13,68 +13,43 @@
 //                           (csrc/sample.hip) instead of its logits: the reference's arg-max decoding then returns the tokens.
 //   pm_node_tracks        : the track index of every node, in the same cell order (the per-track rules of chord-aware sampling).
 // Byte / index work, bit-exact against the oracle (tests/test_generate_gpu.py, tests/test_sampling_gpu.py).
-#include "common.h"
+#include "bars.h"
 
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 constexpr int CELL = PM_N_SLOTS * PM_N_TOK;      // 3450 floats per cell
-constexpr int PITCH_EOS = 129, PITCH_PAD = 130;  // constants.py:22-25
 
 __global__ void __launch_bounds__(256) k_binary_from_logits(const float* __restrict__ s_logits, int G, float thresh,
                                                             float* __restrict__ s_f32, uint8_t* __restrict__ s_u8) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
-  const int g = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
-  const bool valid = g < G;
+  const HalfBar h(G);
   bool on[4];
   uint32_t any = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const float x = valid ? s_logits[((int64_t)g * 4 + k) * 32 + t] : 0.f;
-    on[k] = valid && !((1.0f / (1.0f + expf(-x))) < thresh);          // model.py:612-615 in fp32 (a NaN ends up True)
-    any |= (uint32_t)(__ballot(on[k]) >> (32 * half));
+    const float x = h.valid ? s_logits[h.cell(k)] : 0.f;
+    on[k] = h.valid && !((1.0f / (1.0f + expf(-x))) < thresh);        // model.py:612-615 in fp32 (a NaN ends up True)
+    any |= h.ballot(on[k]);
   }
-  if (!valid) return;
-  if (any == 0u && t == 0) on[0] = true;                               // model.py:617-621
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int64_t i = ((int64_t)g * 4 + k) * 32 + t;
-    if (s_f32) s_f32[i] = on[k] ? 1.0f : 0.0f;
-    if (s_u8) s_u8[i] = on[k] ? 1 : 0;
-  }
+  if (!h.valid) return;
+  if (any == 0u && h.t == 0) on[0] = true;                             // model.py:617-621
+  h.store(on, s_f32, s_u8);
 }
 
 // active cells per bar
 __global__ void __launch_bounds__(256) k_bar_cells(const float* __restrict__ s, int G, int* __restrict__ bar_nodes) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
-  const int g = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
-  const bool valid = g < G;
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool on = valid && s[((int64_t)g * 4 + k) * 32 + t] != 0.f;
-    n += __popc((uint32_t)(__ballot(on) >> (32 * half)));
-  }
-  if (valid && t == 0) bar_nodes[g] = n;
+  const HalfBar h(G);
+  const BarMasks b = h.masks(s);
+  if (h.valid && h.t == 0) bar_nodes[h.g] = __popc(b.m[0]) + __popc(b.m[1]) + __popc(b.m[2]) + __popc(b.m[3]);
 }
 
-// exclusive scan over the bars (one workgroup): ptr[0..G]
+// exclusive scan over the bars (one workgroup): ptr[0..G]  (a and ptr may not alias)
 __global__ void __launch_bounds__(1024) k_bar_scan(const int* __restrict__ a, int G, int* __restrict__ ptr) {
-  __shared__ int sa[1024];
-  const int per = (G + 1023) / 1024, lo = threadIdx.x * per, hi = min(lo + per, G);
-  int xa = 0;
-  for (int i = lo; i < hi; ++i) xa += a[i];
-  sa[threadIdx.x] = xa;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int ya = threadIdx.x >= o ? sa[threadIdx.x - o] : 0;
-    __syncthreads();
-    sa[threadIdx.x] += ya;
-    __syncthreads();
-  }
-  int ra = sa[threadIdx.x] - xa;
-  for (int i = lo; i < hi; ++i) { const int c = a[i]; ptr[i] = ra; ra += c; }      // (a and ptr may not alias)
-  if (threadIdx.x == 1023) ptr[G] = sa[1023];
+  const int* const in[1] = {a};
+  const BlockScan<1> sc(in, G);
+  int ra = sc.pre[0];
+  for (int i = sc.lo; i < sc.hi; ++i) { ptr[i] = ra; ra += a[i]; }
+  if (threadIdx.x == 1023) ptr[G] = sc.total[0];
 }
 
 // one workgroup per (bar, track): 32 cells of 13.8 KB, each wave takes 8 of them.  TOK: an active cell holds the one-hot
@@ -83,7 +58,7 @@ template <bool TOK>
 __global__ void __launch_bounds__(256) k_mtp_fill(const float* __restrict__ c_logits, const int* __restrict__ tokens,
                                                   const float* __restrict__ s, const int* __restrict__ node_ptr,
                                                   int64_t N, float* __restrict__ mtp) {
-  __shared__ uint32_t masks[4];
+  __shared__ uint32_t masks[4];                                                 // (the numbering of BarLanes, bars.h, per track)
   const int g = blockIdx.x >> 2, k = blockIdx.x & 3;
   if (threadIdx.x < 128) {
     const bool on = s[(int64_t)g * 128 + threadIdx.x] != 0.f;
@@ -128,9 +103,8 @@ __global__ void __launch_bounds__(256) k_mtp_fill(const float* __restrict__ c_lo
   }
 }
 
-// the track of every node (pm_node_tracks): one wave per bar, lane l holds the cells l and l + 64 of the bar's 128 (track
-// k = cell >> 5); nodes are numbered in cell order, so a cell's node is node_ptr[g] + the active cells before it in the bar.
-// The tail [active, N) is zeroed by the same launch (grid-stride: no cell writes there).
+// the track of every node (pm_node_tracks): one wave per bar (BarLanes).  The tail [active, N) is zeroed by the same launch
+// (grid-stride: no cell writes there).
 __global__ void __launch_bounds__(256) k_node_tracks(const float* __restrict__ s, const int* __restrict__ node_ptr, int G,
                                                      int64_t N, uint8_t* __restrict__ node_track) {
   const int lane = threadIdx.x & 63;
@@ -139,14 +113,20 @@ __global__ void __launch_bounds__(256) k_node_tracks(const float* __restrict__ s
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
     if (i >= active) node_track[i] = 0;
   if (g >= G) return;                                                           // wave-uniform
-  const bool on0 = s[(int64_t)g * 128 + lane] != 0.f, on1 = s[(int64_t)g * 128 + 64 + lane] != 0.f;
-  const unsigned long long b0 = __ballot(on0), b1 = __ballot(on1), below = (1ull << lane) - 1ull;
-  const int64_t n0 = (int64_t)node_ptr[g] + __popcll(b0 & below), n1 = (int64_t)node_ptr[g] + __popcll(b0) + __popcll(b1 & below);
-  if (on0 && n0 < N) node_track[n0] = (uint8_t)(lane >> 5);
-  if (on1 && n1 < N) node_track[n1] = (uint8_t)(2 + (lane >> 5));
+  const BarLanes bl(s, node_ptr, g, lane, N);
+  if (bl.on0) node_track[bl.n0] = (uint8_t)(lane >> 5);
+  if (bl.on1) node_track[bl.n1] = (uint8_t)(2 + (lane >> 5));
 }
 
 }  // namespace
+
+int pm_bar_node_ptr(hipStream_t st, const float* s_tensor, int32_t G, int32_t* bar_nodes, int32_t* node_ptr) {
+  if (!s_tensor || !bar_nodes || !node_ptr || G <= 0 || bar_nodes == node_ptr || (int64_t)G * 4 > 0x7fffffffLL)
+    return PM_E_INVALID;
+  hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
+  hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
+  return PM_OK;
+}
 
 extern "C" int pm_binary_from_logits(const float* s_logits, int32_t G, float thresh, float* s_f32, uint8_t* s_u8,
                                      pm_stream_t stream) {
@@ -158,36 +138,24 @@ extern "C" int pm_binary_from_logits(const float* s_logits, int32_t G, float thr
 
 extern "C" int pm_mtp_from_logits(const float* c_logits, const float* s_tensor, int32_t G, int64_t N, int32_t* bar_nodes,
                                   int32_t* node_ptr, float* mtp, pm_stream_t stream) {
-  if ((!c_logits && N > 0) || !s_tensor || !bar_nodes || !node_ptr || !mtp || G <= 0 || N < 0 || bar_nodes == node_ptr)
-    return PM_E_INVALID;
-  if ((int64_t)G * 4 > 0x7fffffffLL) return PM_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
-  hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
+  if ((!c_logits && N > 0) || !mtp || N < 0 || pm_bar_node_ptr(st, s_tensor, G, bar_nodes, node_ptr) != PM_OK) return PM_E_INVALID;
   hipLaunchKernelGGL(k_mtp_fill<false>, dim3(G * 4), dim3(256), 0, st, c_logits, nullptr, s_tensor, node_ptr, N, mtp);
   return pm_check_launch();
 }
 
 extern "C" int pm_mtp_from_tokens(const int32_t* tokens, const float* s_tensor, int32_t G, int64_t N, int32_t* bar_nodes,
                                   int32_t* node_ptr, float* mtp, pm_stream_t stream) {
-  if ((!tokens && N > 0) || !s_tensor || !bar_nodes || !node_ptr || !mtp || G <= 0 || N < 0 || bar_nodes == node_ptr)
-    return PM_E_INVALID;
-  if ((int64_t)G * 4 > 0x7fffffffLL) return PM_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
-  hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
+  if ((!tokens && N > 0) || !mtp || N < 0 || pm_bar_node_ptr(st, s_tensor, G, bar_nodes, node_ptr) != PM_OK) return PM_E_INVALID;
   hipLaunchKernelGGL(k_mtp_fill<true>, dim3(G * 4), dim3(256), 0, st, nullptr, tokens, s_tensor, node_ptr, N, mtp);
   return pm_check_launch();
 }
 
 extern "C" int pm_node_tracks(const float* s_tensor, int32_t G, int64_t N, int32_t* bar_nodes, int32_t* node_ptr,
                               uint8_t* node_track, pm_stream_t stream) {
-  if ((!node_track && N > 0) || !s_tensor || !bar_nodes || !node_ptr || G <= 0 || N < 0 || bar_nodes == node_ptr)
-    return PM_E_INVALID;
-  if ((int64_t)G * 4 > 0x7fffffffLL) return PM_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
-  hipLaunchKernelGGL(k_bar_scan, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr);
+  if ((!node_track && N > 0) || N < 0 || pm_bar_node_ptr(st, s_tensor, G, bar_nodes, node_ptr) != PM_OK) return PM_E_INVALID;
   hipLaunchKernelGGL(k_node_tracks, dim3(pm_cdiv(G, 4)), dim3(256), 0, st, s_tensor, node_ptr, G, N, node_track);
   return pm_check_launch();
 }

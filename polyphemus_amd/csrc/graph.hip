@@ -11,43 +11,22 @@
 //     next edges    consecutive active columns t1 < t2: a in tracks(t1), b in tracks(t2), a != b, forward only  :96-119
 //     an edgeless bar gets the self loop (0, 0, type 0, distance 0)                            data.py:173-176
 //   an empty bar gets cell [0,0] switched on IN PLACE                                          data.py:152-153
-// Integer / bit work, one half-wave (32 lanes = 32 timesteps) per bar: counts -> exclusive scan over bars -> emit.
-#include "common.h"
+// Integer / bit work, one half-wave (32 lanes = 32 timesteps) per bar (HalfBar of bars.h, which also holds the half-wave sums
+// and the one-workgroup scan): counts -> exclusive scan over bars -> emit.
+#include "bars.h"
 
 namespace {
-
-struct BarMasks { uint32_t m[4]; };     // bit t of m[k]: track k active at timestep t
 
 __device__ inline int pc(uint32_t v) { return __popc(v); }
 
 // masks of the bar handled by this half-wave; `fix` switches cell [0,0] on for an empty bar (lane t == 0 writes)
-__device__ inline BarMasks load_bar(float* s, int g, int t, int half, bool valid, bool fix) {
-  BarMasks b;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool on = valid && s[((int64_t)g * 4 + k) * 32 + t] != 0.f;
-    const unsigned long long bal = __ballot(on);
-    b.m[k] = (uint32_t)(bal >> (32 * half));
-  }
-  if (valid && (b.m[0] | b.m[1] | b.m[2] | b.m[3]) == 0u) {
+__device__ inline BarMasks load_bar(float* s, const HalfBar& h, bool fix) {
+  BarMasks b = h.masks(s);
+  if (h.valid && (b.m[0] | b.m[1] | b.m[2] | b.m[3]) == 0u) {
     b.m[0] = 1u;
-    if (fix && t == 0) s[(int64_t)g * 128] = 1.0f;
+    if (fix && h.t == 0) s[h.g * 128] = 1.0f;
   }
   return b;
-}
-__device__ inline int half_sum(int v) {
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-  return v;
-}
-__device__ inline int half_excl_scan(int v, int t) {     // exclusive prefix over the 32 lanes of a half-wave
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) {
-    const int y = __shfl_up(x, o, 32);
-    if (t >= o) x += y;
-  }
-  return x - v;
 }
 // per-lane (timestep t) quantities of a bar
 struct Lane {
@@ -76,39 +55,27 @@ __device__ inline Lane lane_info(const BarMasks& b, int t) {
 
 __global__ void __launch_bounds__(256) k_graph_count(float* __restrict__ s, int G, int* __restrict__ bar_nodes,
                                                      int* __restrict__ bar_edges) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
-  const int g = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
-  const bool valid = g < G;
-  const BarMasks b = load_bar(s, g, t, half, valid, true);
-  const Lane L = lane_info(b, t);
+  const HalfBar h(G);
+  const BarMasks b = load_bar(s, h, true);
+  const Lane L = lane_info(b, h.t);
   const int onset = half_sum(L.pt), next = half_sum(L.ct);
-  if (!valid || t != 0) return;
+  if (!h.valid || h.t != 0) return;
   int nodes = 0, track = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) { const int c = pc(b.m[k]); nodes += c; track += c > 1 ? c - 1 : 0; }
   const int e = 2 * track + 2 * onset + next;
-  bar_nodes[g] = nodes;
-  bar_edges[g] = e > 0 ? e : 1;                              // the self loop of an edgeless bar
+  bar_nodes[h.g] = nodes;
+  bar_edges[h.g] = e > 0 ? e : 1;                              // the self loop of an edgeless bar
 }
 
 // exclusive scan of two int arrays over the bars (one workgroup): ptr[0..G], totals[0..1]
 __global__ void __launch_bounds__(1024) k_graph_scan(const int* __restrict__ a, const int* __restrict__ b, int G,
                                                      int* __restrict__ pa, int* __restrict__ pb, int* __restrict__ totals) {
-  __shared__ int sa[1024], sb[1024];
-  const int per = (G + 1023) / 1024, lo = threadIdx.x * per, hi = min(lo + per, G);
-  int xa = 0, xb = 0;
-  for (int i = lo; i < hi; ++i) { xa += a[i]; xb += b[i]; }
-  sa[threadIdx.x] = xa; sb[threadIdx.x] = xb;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int ya = threadIdx.x >= o ? sa[threadIdx.x - o] : 0, yb = threadIdx.x >= o ? sb[threadIdx.x - o] : 0;
-    __syncthreads();
-    sa[threadIdx.x] += ya; sb[threadIdx.x] += yb;
-    __syncthreads();
-  }
-  int ra = sa[threadIdx.x] - xa, rb = sb[threadIdx.x] - xb;   // exclusive prefix of this thread's chunk
-  for (int i = lo; i < hi; ++i) { pa[i] = ra; pb[i] = rb; ra += a[i]; rb += b[i]; }
-  if (threadIdx.x == 1023) { pa[G] = sa[1023]; pb[G] = sb[1023]; totals[0] = sa[1023]; totals[1] = sb[1023]; }
+  const int* const in[2] = {a, b};
+  const BlockScan<2> sc(in, G);
+  int ra = sc.pre[0], rb = sc.pre[1];
+  for (int i = sc.lo; i < sc.hi; ++i) { pa[i] = ra; pb[i] = rb; ra += a[i]; rb += b[i]; }
+  if (threadIdx.x == 1023) { pa[G] = sc.total[0]; pb[G] = sc.total[1]; totals[0] = sc.total[0]; totals[1] = sc.total[1]; }
 }
 
 __global__ void __launch_bounds__(256) k_graph_emit(float* __restrict__ s, int G, int n_bars,
@@ -117,14 +84,13 @@ __global__ void __launch_bounds__(256) k_graph_emit(float* __restrict__ s, int G
                                                     int* __restrict__ edge_type, int* __restrict__ edge_dist,
                                                     int64_t* __restrict__ bars, int64_t* __restrict__ batch,
                                                     uint8_t* __restrict__ is_drum, int* __restrict__ node_cell) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
-  const int g = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
-  const bool valid = g < G;
-  const BarMasks b = load_bar(s, g, t, half, valid, false);
+  const HalfBar h(G);
+  const int t = h.t, g = (int)h.g;
+  const BarMasks b = load_bar(s, h, false);
   const Lane L = lane_info(b, t);
-  const int pre_p = half_excl_scan(L.pt, t), pre_c = half_excl_scan(L.ct, t);
+  const int pre_p = half_exclusive(L.pt, t), pre_c = half_exclusive(L.ct, t);
   const int onset_tot = half_sum(L.pt), next_tot = half_sum(L.ct);
-  if (!valid) return;
+  if (!h.valid) return;
   const int64_t n0 = node_ptr[g], e0 = edge_ptr[g];
   int cnt[4], pre[4];
   int acc = 0, track_tot = 0;

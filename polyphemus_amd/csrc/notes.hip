@@ -3,7 +3,7 @@
 // (13.8 KB per cell, active or not) is never written: 120 B of tokens are read per node, at most 15 rows of 12 B written.
 //
 //   cell order  : bar g = i * n_bars + b of piece i, track k, timestep s; an active cell's node is node_ptr[g] + the active
-//                 cells before it in the bar (k_node_tracks of generate.hip), its time t = 32 b + s.
+//                 cells before it in the bar (BarLanes of bars.h), its time t = 32 b + s.
 //   slot loop   : the 15 (pitch, duration) pairs in order; stop at pitch EOS / PAD or duration EOS / PAD, skip pitch SOS,
 //                 otherwise the note (t, pitch, min(duration + 1, 32 n_bars - t)).  The reference never tests for a duration
 //                 SOS (utils.py:114-115 tests the pitch twice): token 96 is a note of length 97 before the clamp.  A token
@@ -11,13 +11,13 @@
 //   order       : the reference appends per track, by time, then by slot: the rows of (piece i, track k) are one range, inside
 //                 it bar after bar, inside a bar timestep after timestep.  A segment is one (piece, track, bar), numbered
 //                 (4 i + k) * n_bars + b; its rows start at the exclusive scan of the segments' note counts.
-// Launches: the bars' active cells and their scan (node_ptr), the segments' note counts, their scan (seg_ptr, track_ptr,
-// totals), the rows.  No atomics: every row's position is a function of the inputs.  Integer work, exact.
-#include "common.h"
+// Launches: the bars' active cells and their scan (pm_bar_node_ptr), the segments' note counts, their scan (seg_ptr,
+// track_ptr, totals), the rows.  The bar per wave (BarLanes), the half-wave sums and the scan are those of bars.h.
+// No atomics: every row's position is a function of the inputs.  Integer work, exact.
+#include "bars.h"
 
 namespace {
 
-constexpr int PITCH_SOS = 128, PITCH_EOS = 129, PITCH_PAD = 130, DUR_EOS = 97, DUR_PAD = 98;   // constants.py:22-35
 constexpr int TOK_PER_NODE = 2 * PM_N_SLOTS;
 
 // One cell's 15 token pairs in registers (read once, 8-byte loads), read the way the reference reads the cell.
@@ -61,85 +61,25 @@ struct Cell {
   }
 };
 
-// A wave per bar, lane l holds the cells l (track l >> 5) and l + 64 (track 2 + (l >> 5)), as k_node_tracks.
-struct BarLanes {
-  bool on0, on1;
-  int64_t n0, n1;
-  __device__ BarLanes(const float* __restrict__ s, const int* __restrict__ node_ptr, int g, int lane, int64_t N) {
-    const bool a0 = s[(int64_t)g * 128 + lane] != 0.f, a1 = s[(int64_t)g * 128 + 64 + lane] != 0.f;
-    const unsigned long long b0 = __ballot(a0), b1 = __ballot(a1), below = (1ull << lane) - 1ull;
-    n0 = (int64_t)node_ptr[g] + __popcll(b0 & below);
-    n1 = (int64_t)node_ptr[g] + __popcll(b0) + __popcll(b1 & below);
-    on0 = a0 && n0 < N;
-    on1 = a1 && n1 < N;
-  }
-};
-
-// active cells per bar (k_bar_cells of generate.hip)
-__global__ void __launch_bounds__(256) k_notes_bar_cells(const float* __restrict__ s, int G, int* __restrict__ bar_nodes) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
-  const int g = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
-  const bool valid = g < G;
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool on = valid && s[((int64_t)g * 4 + k) * 32 + t] != 0.f;
-    n += __popc((uint32_t)(__ballot(on) >> (32 * half)));
-  }
-  if (valid && t == 0) bar_nodes[g] = n;
-}
-
-// exclusive scan of a[0..n) into ptr[0..n] (one workgroup, the pattern of k_bar_scan).  SEG: a is seg_count; every
-// n_bars-th entry of the scan is a track's first row, and the totals are written.
-template <bool SEG>
-__global__ void __launch_bounds__(1024) k_notes_scan(const int* __restrict__ a, int n, int* __restrict__ ptr, int n_bars,
-                                                     int* __restrict__ track_ptr, const int* __restrict__ node_ptr, int G,
-                                                     int* __restrict__ totals) {
-  __shared__ int sa[1024];
-  const int per = (n + 1023) / 1024, lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-  int xa = 0;
-  for (int i = lo; i < hi; ++i) xa += a[i];
-  sa[threadIdx.x] = xa;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int ya = threadIdx.x >= o ? sa[threadIdx.x - o] : 0;
-    __syncthreads();
-    sa[threadIdx.x] += ya;
-    __syncthreads();
-  }
-  int ra = sa[threadIdx.x] - xa;
-  for (int i = lo; i < hi; ++i) {
-    const int c = a[i];
+// exclusive scan of the segments' note counts into seg_ptr[0..n] (one workgroup); every n_bars-th entry of the scan is a
+// track's first row, and the totals are written.
+__global__ void __launch_bounds__(1024) k_notes_seg_scan(const int* __restrict__ a, int n, int* __restrict__ ptr, int n_bars,
+                                                         int* __restrict__ track_ptr, const int* __restrict__ node_ptr, int G,
+                                                         int* __restrict__ totals) {
+  const int* const in[1] = {a};
+  const BlockScan<1> sc(in, n);
+  int ra = sc.pre[0];
+  for (int i = sc.lo; i < sc.hi; ++i) {
     ptr[i] = ra;
-    if (SEG && i % n_bars == 0) track_ptr[i / n_bars] = ra;
-    ra += c;
+    if (i % n_bars == 0) track_ptr[i / n_bars] = ra;
+    ra += a[i];
   }
   if (threadIdx.x == 1023) {
-    ptr[n] = sa[1023];
-    if (SEG) {
-      track_ptr[n / n_bars] = sa[1023];
-      totals[0] = sa[1023];
-      totals[1] = node_ptr[G];
-    }
+    ptr[n] = sc.total[0];
+    track_ptr[n / n_bars] = sc.total[0];
+    totals[0] = sc.total[0];
+    totals[1] = node_ptr[G];
   }
-}
-
-// sum over the 32 lanes of a half-wave, in every lane of it
-__device__ inline int half_sum(int x) {
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-
-// exclusive prefix sum over the 32 lanes of a half-wave
-__device__ inline int half_exclusive(int x, int t) {
-  int inc = x;
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) {
-    const int y = __shfl_up(inc, o, 32);
-    if (t >= o) inc += y;
-  }
-  return inc - x;
 }
 
 __global__ void __launch_bounds__(256) k_notes_count(const int32_t* __restrict__ tokens, const float* __restrict__ s,
@@ -209,11 +149,10 @@ extern "C" int pm_notes_from_tokens(const int32_t* tokens, const float* s_tensor
     for (int b = a + 1; b < 7; ++b)
       if (buf[a] && buf[b] && overlap(buf[a], len[a], buf[b], len[b])) return PM_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_notes_bar_cells, dim3(pm_cdiv(G, 8)), dim3(256), 0, st, s_tensor, G, bar_nodes);
-  hipLaunchKernelGGL(k_notes_scan<false>, dim3(1), dim3(1024), 0, st, bar_nodes, G, node_ptr, 1, nullptr, nullptr, 0, nullptr);
+  if (pm_bar_node_ptr(st, s_tensor, G, bar_nodes, node_ptr) != PM_OK) return PM_E_INVALID;
   hipLaunchKernelGGL(k_notes_count, dim3(pm_cdiv(G, 4)), dim3(256), 0, st, tokens, s_tensor, node_ptr, G, n_bars, N, seg_count);
-  hipLaunchKernelGGL(k_notes_scan<true>, dim3(1), dim3(1024), 0, st, seg_count, (int)S, seg_ptr, n_bars, track_ptr, node_ptr, G,
-                     totals);
+  hipLaunchKernelGGL(k_notes_seg_scan, dim3(1), dim3(1024), 0, st, seg_count, (int)S, seg_ptr, n_bars, track_ptr, node_ptr,
+                     G, totals);
   hipLaunchKernelGGL(k_notes_emit, dim3(pm_cdiv(G, 4)), dim3(256), 0, st, tokens, s_tensor, node_ptr, seg_ptr, G, n_bars, N,
                      notes, capacity);
   return pm_check_launch();

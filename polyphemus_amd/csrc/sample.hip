@@ -2,21 +2,17 @@
 // nucleus (top-p) sampling of the pitch and the duration token of every (node, slot) row of the content logits, and sampling
 // of the bar structure from the structure logits.
 //
-//   k_sample_tokens : one wave per row of 230 logits (920 B, read once), 8 B of tokens written.  Lane l holds the columns
-//                     l, l + 64, l + 128, l + 192 (four coalesced 256-byte wave loads; the last one 38 lanes wide), so a
-//                     token's place in index order is (slot, lane) and the head of a column is known per slot except for
-//                     slot 2, where the lanes 0..2 end the pitch head and the lanes 3..63 begin the duration head.
-//                     The draw is a Gumbel arg-max, so no cumulative sum and no second random number per row; the filters
-//                     are an all-pairs pass over the row (every column broadcast once with v_readlane, compared against
-//                     the lane's own columns of the same head, two vector instructions per pair and count): it counts the tokens that outrank a column (top-k) and
-//                     sums their softmax mass (top-p) in one go, exact under ties, with no LDS and no atomics.
-//                     MODE 0 greedy and MODE 1 unfiltered skip that pass altogether.
+//   the core        : the row layout (load_row), the noise of the stream (seed, head, row, token) (unit_noise, gumbel), the
+//                     arg-max (cand_better, cand_wave) and head_filter, the top-k / top-p pass of one head of one row over a
+//                     set of candidate columns.
+//   k_sample_tokens : one wave per row of 230 logits (920 B, read once), 8 B of tokens written: both heads at once, every live
+//                     column a candidate of its head's head_filter.
 //   k_sample_chords : chord-aware sampling (PmChordRules): one wave per node, its 15 slots decided in order as notes, one EOS,
-//                     then PAD, under per-track rules (note counts, a pitch mask, no pitch twice); the same lane layout, the
-//                     same noise stream and the same filters, applied to the candidates of each slot.
+//                     then PAD, under per-track rules (note counts, a pitch mask, no pitch twice): draw_head draws each head
+//                     among the candidates of the slot.
 //   k_sample_structure : structure sampling (PmStructureRules): which of the 4 x 32 (track, timestep) cells of every bar are active,
 //                     drawn from the structure logits under per-track rules (a bias, the least and the most active cells, the
-//                     allowed timesteps).  A bar per half-wave, as k_binary_from_logits (csrc/generate.hip): lane t of the half
+//                     allowed timesteps).  A bar per half-wave (HalfBar of bars.h, as k_binary_from_logits): lane t of the half
 //                     holds the four cells of timestep t, one per track, so a track's 32 cells lie across the 32 lanes of the
 //                     half and a bar's logits are four coalesced 128-byte loads.  512 B read and 128 / 512 B (+ 16 B of counts)
 //                     written per bar, each once.  The rank of a cell is an all-pairs count inside the half: every allowed
@@ -25,7 +21,8 @@
 //                     scalar loop over the bits of the mask, and a track whose bounds cannot bind (0 .. 32) skips the pass
 //                     wave-uniformly.  NOISE = false (temperature 0) compiles the hash and the two logf away.  The lanes of a
 //                     half without a bar (odd G, the last wave) take part in every cross-lane step and store nothing.
-#include "common.h"
+#include <type_traits>
+#include "bars.h"
 
 namespace {
 
@@ -50,12 +47,13 @@ __device__ static inline float bcast(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
-// Gumbel noise of (key, token): the header's u, g
-__device__ static inline float gumbel(uint32_t key, uint32_t token) {
+// the uniform u in (0, 1) of (key, token): the header's u
+__device__ static inline float unit_noise(uint32_t key, uint32_t token) {
   const uint32_t h = pm_group_hash(key, token);
-  const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;          // 2^-23: exact, inside (0, 1)
-  return -logf(-logf(u));
+  return ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;                   // 2^-23: exact, inside (0, 1)
 }
+// Gumbel noise of (key, token): the header's g
+__device__ static inline float gumbel(uint32_t key, uint32_t token) { return -logf(-logf(unit_noise(key, token))); }
 
 // the logit as an unsigned word of the same order; -0 and +0 share one key (they are equal logits)
 __device__ static inline unsigned ukey(float x) {
@@ -63,20 +61,84 @@ __device__ static inline unsigned ukey(float x) {
   return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
 
+// A row of 230 logits (920 B, read once) across the wave: lane l holds the columns l, l + 64, l + 128, l + 192 (four coalesced
+// 256-byte wave loads; the last one 38 lanes wide, -inf behind it).  Registers 0, 1 and the lanes 0..2 of register 2 are the
+// pitch head (token = column), the lanes 3..63 of register 2 and register 3 the duration head (token = column - 131).
+__device__ static inline void load_row(const float* __restrict__ x, int lane, float (&v)[4]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) v[j] = x[lane + 64 * j];
+  v[3] = lane < PM_N_TOK - 192 ? x[lane + 192] : -INFINITY;
+}
+
+// ---- the sampling core.  The draw is a Gumbel arg-max (gumbel, cand_better, cand_wave above), so no cumulative sum and no
+// second random number per row, and head_filter is its one top-k / top-p pass.
+
+// One head of one row.  NV registers per lane: v[j] = the logit of this lane's j-th column of the head, cand[j] whether it is a
+// candidate, bal[j] = __ballot(cand[j]), live[j] (= cand[j] on entry) whether it stays in the draw.  An all-pairs pass whose
+// sources are the candidates alone, taken in index order from the ballots (every one broadcast once with v_readlane and
+// compared against the lane's own columns): it counts the candidates that outrank a column (top-k) and sums their softmax mass
+// (top-p) in one go, exact under ties, with no LDS and no atomics.  A column that is no candidate takes no rank and adds no
+// mass.  MODE 0 greedy and MODE 1 unfiltered have no pass.
+template <int MODE, int NV>
+__device__ static inline void head_filter(const float (&v)[NV], const bool (&cand)[NV], const unsigned long long (&bal)[NV],
+                                          float inv_t, int top_k, float top_p, int lane, bool (&live)[NV]) {
+  if (MODE != SAMPLE_TOPK && MODE != SAMPLE_TOPP) return;
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) m = fmaxf(m, cand[j] ? v[j] : -INFINITY);
+  m = pm_wave_max(m);
+  float q[NV], mass[NV];
+  unsigned key_[NV];
+  int cnt[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    q[j] = cand[j] ? expf((v[j] - m) * inv_t) : 0.f;
+    key_[j] = ukey(v[j]);
+    cnt[j] = 0;
+    mass[j] = 0.f;
+  }
+  // source (register s, lane l) outranks target (register j, this lane) iff key(source) > thr: the target's key when the
+  // source comes later in index order, its key - 1 when it comes earlier (equal logits: the lower index outranks)
+#pragma unroll
+  for (int s = 0; s < NV; ++s) {
+    for (unsigned long long m_s = bal[s]; m_s; m_s &= m_s - 1) {
+      const int l = (int)__builtin_ctzll(m_s);
+      const unsigned sk = (unsigned)__builtin_amdgcn_readlane((int)key_[s], l);
+      const float sq = MODE == SAMPLE_TOPP ? bcast(q[s], l) : 0.f;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const bool earlier = s < j || (s == j && l < lane);
+        const bool o = sk > key_[j] - (earlier ? 1u : 0u);
+        cnt[j] += o ? 1 : 0;
+        if (MODE == SAMPLE_TOPP) mass[j] += o ? sq : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) live[j] = live[j] && cnt[j] < top_k;
+  if (MODE == SAMPLE_TOPP) {
+    float z = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) z += live[j] ? q[j] : 0.f;
+    z = pm_wave_sum(z);
+    const float edge = top_p * z;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) live[j] = live[j] && mass[j] < edge;
+  }
+}
+
+// One wave per row, both heads at once, every live column a candidate: the head of a column is known per register except for
+// register 2, where the lanes 0..2 end the pitch head and the lanes 3..63 begin the duration head.
 template <int MODE>
 __global__ void __launch_bounds__(256) k_sample_tokens(const float* __restrict__ c_logits, int64_t rows, float inv_t,
                                                        int top_k, float top_p, uint32_t seed, int* __restrict__ tokens) {
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;                                                        // wave-uniform
-  const float* x = c_logits + r * PM_N_TOK;
-  // slot j = column lane + 64 j; head and token of the slot
-  const bool p2 = lane < 3;                                                     // slot 2: columns 128..130 are pitch
+  const bool p2 = lane < 3;                                                     // register 2: columns 128..130 are pitch
   const bool live3 = lane < PM_N_TOK - 192;
   float v[4];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) v[j] = x[lane + 64 * j];
-  v[3] = live3 ? x[lane + 192] : -INFINITY;
+  load_row(c_logits + r * PM_N_TOK, lane, v);
   const int tok[4] = {lane, lane + 64, p2 ? lane + 128 : lane - 3, lane + 192 - PM_N_PITCH};
 
   bool live[4] = {true, true, true, live3};
@@ -86,68 +148,13 @@ __global__ void __launch_bounds__(256) k_sample_tokens(const float* __restrict__
     for (int j = 0; j < 4; ++j) score[j] = v[j];
   } else {
     if (MODE != SAMPLE_PLAIN) {
-      // rank (tokens that outrank the column) and the softmax mass of those tokens, per column of this lane
-      float mp = fmaxf(fmaxf(v[0], v[1]), p2 ? v[2] : -INFINITY), md = fmaxf(p2 ? -INFINITY : v[2], v[3]);
-      mp = pm_wave_max(mp); md = pm_wave_max(md);
-      float q[4];
-      q[0] = expf((v[0] - mp) * inv_t); q[1] = expf((v[1] - mp) * inv_t);
-      q[2] = expf((v[2] - (p2 ? mp : md)) * inv_t);
-      q[3] = live3 ? expf((v[3] - md) * inv_t) : 0.f;
-      // Branch-free: a column's logit as an unsigned key of the same order (-0 = +0), and per target a threshold `thr` such
-      // that "the source outranks it" is key(source) > thr: its own key when the source comes later in index order, its
-      // key - 1 when it comes earlier (equal logits: the lower index outranks), the largest word when the source is of the
-      // other head (slot 2 holds both).  Within one slot the source lane l comes earlier for the lanes above l.
-      const unsigned NONE = 0xffffffffu;
-      unsigned key[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) key[j] = ukey(v[j]);
-      const unsigned k2p = p2 ? key[2] : NONE, k2p1 = p2 ? key[2] - 1u : NONE;      // slot 2 as a pitch / a duration target
-      const unsigned k2d = p2 ? NONE : key[2], k2d1 = p2 ? NONE : key[2] - 1u;
-      int cnt[4] = {0, 0, 0, 0};
-      float mass[4] = {0.f, 0.f, 0.f, 0.f};
-      auto pair = [&](unsigned sk, float sq, unsigned thr, int t) {
-        const bool o = sk > thr;
-        cnt[t] += o ? 1 : 0;
-        if (MODE == SAMPLE_TOPP) mass[t] += o ? sq : 0.f;
-      };
-      auto src = [&](int s, int l, unsigned& sk, float& sq) {
-        sk = (unsigned)__builtin_amdgcn_readlane((int)key[s], l);
-        sq = MODE == SAMPLE_TOPP ? bcast(q[s], l) : 0.f;
-      };
-      unsigned sk;
-      float sq;
-      // pitch columns 0..130 against this lane's pitch columns
-      for (int l = 0; l < 64; ++l) {
-        src(0, l, sk, sq);
-        pair(sk, sq, key[0] - (l < lane ? 1u : 0u), 0); pair(sk, sq, key[1] - 1u, 1); pair(sk, sq, k2p1, 2);
-      }
-      for (int l = 0; l < 64; ++l) {
-        src(1, l, sk, sq);
-        pair(sk, sq, key[0], 0); pair(sk, sq, key[1] - (l < lane ? 1u : 0u), 1); pair(sk, sq, k2p1, 2);
-      }
-      for (int l = 0; l < 3; ++l) {
-        src(2, l, sk, sq);
-        pair(sk, sq, key[0], 0); pair(sk, sq, key[1], 1); pair(sk, sq, l < lane ? k2p1 : k2p, 2);
-      }
-      // duration columns 131..229 against this lane's duration columns
-      for (int l = 3; l < 64; ++l) {
-        src(2, l, sk, sq);
-        pair(sk, sq, l < lane ? k2d1 : k2d, 2); pair(sk, sq, key[3] - 1u, 3);
-      }
-      for (int l = 0; l < PM_N_TOK - 192; ++l) {
-        src(3, l, sk, sq);
-        pair(sk, sq, k2d, 2); pair(sk, sq, key[3] - (l < lane ? 1u : 0u), 3);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) live[j] = live[j] && cnt[j] < top_k;
-      if (MODE == SAMPLE_TOPP) {
-        float zp = (live[0] ? q[0] : 0.f) + (live[1] ? q[1] : 0.f) + (live[2] && p2 ? q[2] : 0.f);
-        float zd = (live[2] && !p2 ? q[2] : 0.f) + (live[3] ? q[3] : 0.f);
-        zp = pm_wave_sum(zp); zd = pm_wave_sum(zd);
-        const float ep = top_p * zp, ed = top_p * zd;
-        live[0] = live[0] && mass[0] < ep; live[1] = live[1] && mass[1] < ep;
-        live[2] = live[2] && mass[2] < (p2 ? ep : ed); live[3] = live[3] && mass[3] < ed;
-      }
+      const float vp[3] = {v[0], v[1], v[2]}, vd[2] = {v[2], v[3]};
+      const bool candp[3] = {true, true, p2}, candd[2] = {!p2, live3};
+      const unsigned long long balp[3] = {~0ull, ~0ull, 7ull}, bald[2] = {~7ull, (1ull << (PM_N_TOK - 192)) - 1ull};
+      bool livep[3] = {true, true, p2}, lived[2] = {!p2, live3};
+      head_filter<MODE, 3>(vp, candp, balp, inv_t, top_k, top_p, lane, livep);
+      head_filter<MODE, 2>(vd, candd, bald, inv_t, top_k, top_p, lane, lived);
+      live[0] = livep[0]; live[1] = livep[1]; live[2] = p2 ? livep[2] : lived[0]; live[3] = lived[1];
     }
     const uint32_t kp = pm_edge_key(seed, 0u, (uint32_t)r), kd = pm_edge_key(seed, 1u, (uint32_t)r);
 #pragma unroll
@@ -172,12 +179,10 @@ __global__ void __launch_bounds__(256) k_sample_tokens(const float* __restrict__
 }
 
 // ---- chord-aware sampling ("sampled generation", PmChordRules) -------------------------------------------------------
-constexpr int PITCH_EOS = 129, PITCH_PAD = 130, DUR_EOS = 97, DUR_PAD = 98, N_DUR_CAND = 96;
+constexpr int N_DUR_CAND = 96;
 
-// One head of one row.  NV registers per lane (v[j] = the logit of this lane's j-th column of the head, tok[j] its token,
-// cand[j] whether it is a candidate); the sources of the all-pairs pass are the candidates alone, taken in index order from
-// the ballots, so a column that is no candidate takes no rank and adds no mass.  Returns a candidate whenever there is one:
-// where no score wins (non-finite logits) the candidate of the lowest index.
+// One head of one slot among its candidates (`greedy`: this head at temperature 0).  Returns a candidate whenever there is
+// one: where no score wins (non-finite logits) the candidate of the lowest index.
 template <int MODE, int NV>
 __device__ static inline int draw_head(const float (&v)[NV], const int (&tok)[NV], const bool (&cand)[NV], bool greedy,
                                        float inv_t, int top_k, float top_p, uint32_t key, int lane) {
@@ -199,50 +204,7 @@ __device__ static inline int draw_head(const float (&v)[NV], const int (&tok)[NV
 #pragma unroll
     for (int j = 0; j < NV; ++j) score[j] = v[j];
   } else {
-    if (MODE != SAMPLE_PLAIN) {
-      float m = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < NV; ++j) m = fmaxf(m, cand[j] ? v[j] : -INFINITY);
-      m = pm_wave_max(m);
-      float q[NV], mass[NV];
-      unsigned key_[NV];
-      int cnt[NV];
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        q[j] = cand[j] ? expf((v[j] - m) * inv_t) : 0.f;
-        key_[j] = ukey(v[j]);
-        cnt[j] = 0;
-        mass[j] = 0.f;
-      }
-      // source (register s, lane l) outranks target (register j, this lane) iff key(source) > thr: the target's key when the
-      // source comes later in index order, its key - 1 when it comes earlier (equal logits: the lower index outranks)
-#pragma unroll
-      for (int s = 0; s < NV; ++s) {
-        for (unsigned long long m_s = bal[s]; m_s; m_s &= m_s - 1) {
-          const int l = (int)__builtin_ctzll(m_s);
-          const unsigned sk = (unsigned)__builtin_amdgcn_readlane((int)key_[s], l);
-          const float sq = MODE == SAMPLE_TOPP ? bcast(q[s], l) : 0.f;
-#pragma unroll
-          for (int j = 0; j < NV; ++j) {
-            const bool earlier = s < j || (s == j && l < lane);
-            const bool o = sk > key_[j] - (earlier ? 1u : 0u);
-            cnt[j] += o ? 1 : 0;
-            if (MODE == SAMPLE_TOPP) mass[j] += o ? sq : 0.f;
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < NV; ++j) live[j] = live[j] && cnt[j] < top_k;
-      if (MODE == SAMPLE_TOPP) {
-        float z = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) z += live[j] ? q[j] : 0.f;
-        z = pm_wave_sum(z);
-        const float edge = top_p * z;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) live[j] = live[j] && mass[j] < edge;
-      }
-    }
+    head_filter<MODE, NV>(v, cand, bal, inv_t, top_k, top_p, lane, live);
 #pragma unroll
     for (int j = 0; j < NV; ++j) score[j] = __fadd_rn(__fmul_rn(v[j], inv_t), gumbel(key, (uint32_t)tok[j]));
   }
@@ -277,7 +239,6 @@ __global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__
       w0 = R.pitch_mask[k][lane >> 5]; w1 = R.pitch_mask[k][2 + (lane >> 5)];
     }
   const bool allow0 = (w0 >> (lane & 31)) & 1u, allow1 = (w1 >> (lane & 31)) & 1u;
-  const bool live3 = lane < PM_N_TOK - 192;
   const float* x = c_logits + n * (PM_N_SLOTS * PM_N_TOK);
   const int tokp[3] = {lane, lane + 64, lane + 128};
   const int tokd[2] = {lane - 3, lane + 192 - PM_N_PITCH};
@@ -286,16 +247,9 @@ __global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__
   int count = 0, slot = 0;
   int mine = (lane & 1) ? DUR_PAD : PITCH_PAD;
   float v[4], nx[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 3; ++j) v[j] = x[lane + 64 * j];
-  v[3] = live3 ? x[lane + 192] : -INFINITY;
+  load_row(x, lane, v);
   for (; slot < PM_N_SLOTS; ++slot) {
-    if (slot + 1 < PM_N_SLOTS) {
-      const float* y = x + (slot + 1) * PM_N_TOK;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) nx[j] = y[lane + 64 * j];
-      nx[3] = live3 ? y[lane + 192] : -INFINITY;
-    }
+    if (slot + 1 < PM_N_SLOTS) load_row(x + (slot + 1) * PM_N_TOK, lane, nx);
     const uint32_t r = (uint32_t)(n * PM_N_SLOTS + slot);
     const bool room = count < max_n;
     bool candp[3] = {allow0 && !used0 && room, allow1 && !used1 && room, false};
@@ -327,23 +281,23 @@ template <bool NOISE>
 __global__ void __launch_bounds__(256) k_sample_structure(const float* __restrict__ s_logits, int G, const PmStructureRules R,
                                                           float inv_t, uint32_t seed, float* __restrict__ s_f32,
                                                           uint8_t* __restrict__ s_u8, int* __restrict__ track_count) {
-  const int lane = threadIdx.x & 63, half = lane >> 5, t = lane & 31;
-  const int64_t g = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 2 + half;
-  const bool valid = g < G;
+  const HalfBar h(G);
+  const int half = h.half, t = h.t;
+  const int64_t g = h.g;
+  const bool valid = h.valid;
   const uint32_t key = NOISE ? pm_edge_key(seed, 2u, (uint32_t)g) : 0u;
   bool allow[4], on[4];
   unsigned sk[4];                                                               // ukey(score)
   float x[4];
   uint32_t any = 0;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) x[k] = valid ? s_logits[(g * 4 + k) * 32 + t] : 0.f;   // four loads in flight
+  for (int k = 0; k < 4; ++k) x[k] = valid ? s_logits[h.cell(k)] : 0.f;         // four loads in flight
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     allow[k] = (R.step_mask[k] >> t) & 1u;
     float score = __fsub_rn(x[k], R.bias[k]);
     if (NOISE) {
-      const uint32_t h = pm_group_hash(key, (uint32_t)(32 * k + t));
-      const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23: exact, inside (0, 1)
+      const float u = unit_noise(key, (uint32_t)(32 * k + t));
       score = __fadd_rn(__fmul_rn(score, inv_t), __fsub_rn(logf(u), logf(1.0f - u)));
     }
     sk[k] = ukey(score);
@@ -365,7 +319,7 @@ __global__ void __launch_bounds__(256) k_sample_structure(const float* __restric
       }
       on[k] = allow[k] && (rank < mn || (rank < mx && nonneg));
     }
-    any |= (uint32_t)(__ballot(valid && on[k]) >> (32 * half));
+    any |= h.ballot(valid && on[k]);
   }
   // no empty bar: the best allowed cell of the tracks that are not muted, the lowest cell index on ties
   if (__ballot(valid && any == 0u) != 0ull) {                                   // (wave-uniform)
@@ -388,20 +342,26 @@ __global__ void __launch_bounds__(256) k_sample_structure(const float* __restric
   int mine = 0;                                                                 // lane k < 4 of the half: the count of track k
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int n = __popc((uint32_t)(__ballot(valid && on[k]) >> (32 * half)));
+    const int n = __popc(h.ballot(valid && on[k]));
     if (t == k) mine = n;
   }
   if (!valid) return;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int64_t i = (g * 4 + k) * 32 + t;
-    if (s_f32) s_f32[i] = on[k] ? 1.0f : 0.0f;
-    if (s_u8) s_u8[i] = on[k] ? 1 : 0;
-  }
+  h.store(on, s_f32, s_u8);
   if (track_count && t < 4) track_count[g * 4 + t] = mine;
 }
 
 }  // namespace
+
+// The kernel form MODE of (every head greedy, top_k, top_p), handed to `launch` as a compile-time constant, and the rank
+// bound kk of the filter pass.
+template <class F>
+static void sample_dispatch(bool all_greedy, int top_k, float top_p, F&& launch) {
+  const int kk = top_k == 0 ? 0x7fffffff : top_k;
+  if (all_greedy || top_k == 1) launch(std::integral_constant<int, SAMPLE_GREEDY>(), kk);
+  else if (top_p < 1.f) launch(std::integral_constant<int, SAMPLE_TOPP>(), kk);
+  else if (top_k > 0 && top_k < PM_N_PITCH) launch(std::integral_constant<int, SAMPLE_TOPK>(), kk);
+  else launch(std::integral_constant<int, SAMPLE_PLAIN>(), kk);
+}
 
 extern "C" uint32_t pm_sample_hash(uint32_t seed, uint32_t row, uint32_t head, uint32_t token) {
   return pm_group_hash(pm_edge_key(seed, head, row), token) >> 9;
@@ -412,21 +372,11 @@ extern "C" int pm_sample_tokens(const float* c_logits, int64_t rows, float tempe
   if (!c_logits || !tokens || rows <= 0 || rows >= ((int64_t)1 << 32)) return PM_E_INVALID;
   if (!(temperature >= 0.f) || !(temperature <= 3.4028234663852886e38f)) return PM_E_INVALID;      // NaN, inf, negative
   if (top_k < 0 || !(top_p > 0.f) || !(top_p <= 1.f)) return PM_E_INVALID;
-  const dim3 grid((unsigned)pm_cdiv(rows, 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const bool k_on = top_k > 0 && top_k < PM_N_PITCH, p_on = top_p < 1.f;
-  const int kk = top_k == 0 ? 0x7fffffff : top_k;
-  if (temperature == 0.f || top_k == 1) {
-    hipLaunchKernelGGL(k_sample_tokens<SAMPLE_GREEDY>, grid, block, 0, st, c_logits, rows, 1.f, kk, top_p, seed, tokens);
-  } else {
-    const float inv_t = (float)(1.0 / (double)temperature);
-    if (p_on)
-      hipLaunchKernelGGL(k_sample_tokens<SAMPLE_TOPP>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
-    else if (k_on)
-      hipLaunchKernelGGL(k_sample_tokens<SAMPLE_TOPK>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
-    else
-      hipLaunchKernelGGL(k_sample_tokens<SAMPLE_PLAIN>, grid, block, 0, st, c_logits, rows, inv_t, kk, top_p, seed, tokens);
-  }
+  sample_dispatch(temperature == 0.f, top_k, top_p, [&](auto mode, int kk) {
+    const float inv_t = decltype(mode)::value == SAMPLE_GREEDY ? 1.f : (float)(1.0 / (double)temperature);
+    hipLaunchKernelGGL(k_sample_tokens<decltype(mode)::value>, dim3((unsigned)pm_cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream,
+                       c_logits, rows, inv_t, kk, top_p, seed, tokens);
+  });
   return pm_check_launch();
 }
 
@@ -440,27 +390,14 @@ extern "C" int pm_sample_chords(const float* c_logits, const uint8_t* node_track
   for (int k = 0; k < 4; ++k)
     if (R.min_notes[k] < 0 || R.max_notes[k] < 1 || R.max_notes[k] > PM_N_SLOTS - 1 || R.min_notes[k] > R.max_notes[k])
       return PM_E_INVALID;
-  const dim3 grid((unsigned)pm_cdiv(N, 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const bool k_on = R.top_k > 0 && R.top_k < PM_N_PITCH, p_on = R.top_p < 1.f;
-  const int kk = R.top_k == 0 ? 0x7fffffff : R.top_k;
-  const int greedy = (R.temperature[0] == 0.f ? 1 : 0) | (R.temperature[1] == 0.f ? 2 : 0);
-  if (greedy == 3 || R.top_k == 1) {
-    hipLaunchKernelGGL(k_sample_chords<SAMPLE_GREEDY>, grid, block, 0, st, c_logits, node_track, N, R, 1.f, 1.f, 3, kk, seed,
-                       tokens, note_count);
-  } else {
+  const int zero_t = (R.temperature[0] == 0.f ? 1 : 0) | (R.temperature[1] == 0.f ? 2 : 0);
+  sample_dispatch(zero_t == 3, R.top_k, R.top_p, [&](auto mode, int kk) {
+    const int greedy = decltype(mode)::value == SAMPLE_GREEDY ? 3 : zero_t;
     const float inv_tp = (greedy & 1) ? 1.f : (float)(1.0 / (double)R.temperature[0]);
     const float inv_td = (greedy & 2) ? 1.f : (float)(1.0 / (double)R.temperature[1]);
-    if (p_on)
-      hipLaunchKernelGGL(k_sample_chords<SAMPLE_TOPP>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
-                         seed, tokens, note_count);
-    else if (k_on)
-      hipLaunchKernelGGL(k_sample_chords<SAMPLE_TOPK>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
-                         seed, tokens, note_count);
-    else
-      hipLaunchKernelGGL(k_sample_chords<SAMPLE_PLAIN>, grid, block, 0, st, c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk,
-                         seed, tokens, note_count);
-  }
+    hipLaunchKernelGGL(k_sample_chords<decltype(mode)::value>, dim3((unsigned)pm_cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream,
+                       c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk, seed, tokens, note_count);
+  });
   return pm_check_launch();
 }
 

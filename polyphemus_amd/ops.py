@@ -9,7 +9,10 @@ from __future__ import annotations
 from typing import Optional
 
 import ctypes
+import math
+import numbers
 
+import numpy as np
 import torch
 
 from . import constants as C
@@ -179,6 +182,37 @@ def binary_from_logits(s_logits: torch.Tensor, thresh: float = 0.5) -> torch.Ten
     return out.view(torch.bool)
 
 
+def _structure_prologue(s_tensor: torch.Tensor, dev, shape_ok: bool, message: str, segments: bool = False):
+    """What the entry points that number the nodes of a structure share: the shape check (`shape_ok` and [...,4,32], else
+    ValueError(message)), the structure as fp32 contiguous, its bar count G and the int32 scratch bar_nodes [G] and
+    node_ptr [G+1] on `dev`; with `segments` also seg_count [4G] and seg_ptr [4G+1], the four cut from one allocation (a
+    split costs about what an allocation does, so two pieces are two allocations).  Returns (s, G, *scratch)."""
+    if not shape_ok or s_tensor.shape[-2:] != (4, 32):
+        raise ValueError(message)
+    s = s_tensor.to(F32).contiguous()
+    G = s.numel() // 128
+    if segments:
+        return (s, G, *torch.empty(10 * G + 2, dtype=I32, device=dev).split([G, G + 1, 4 * G, 4 * G + 1]))
+    return s, G, torch.empty(G, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
+
+
+def _check_active(active: torch.Tensor, N: int, asked: str) -> None:
+    """The node-count check of those entry points: reads the active-cell count back (the call's one host sync)."""
+    active = int(active)
+    if active != N:
+        raise ValueError(f"shape mismatch: s_tensor has {active} active cells, {asked}")
+
+
+def _mtp(entry: str, operand: torch.Tensor, name: str, s_tensor: torch.Tensor, check: bool) -> torch.Tensor:
+    s, G, bn, npt = _structure_prologue(s_tensor, operand.device, s_tensor.dim() == 4, "s_tensor must be [B,n_bars,4,32]")
+    N = operand.shape[0]
+    mtp = torch.empty(*s_tensor.shape, C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR, dtype=F32, device=operand.device)
+    call(entry, ptr(operand), ptr(s), G, N, ptr(bn), ptr(npt), ptr(mtp), stream())
+    if check:
+        _check_active(npt[G], N, f"{name} has {N} nodes")
+    return mtp
+
+
 def mtp_from_logits(c_logits: torch.Tensor, s_tensor: torch.Tensor, check: bool = True) -> torch.Tensor:
     """`mtp_from_logits` (utils.py:59-79): [B,nb,4,32,15,230] with the nodes' logits on the active cells of `s_tensor`
     ([B,nb,4,32], any dtype) and hard silences elsewhere.  `check` reads the active-cell count back (one host sync) and
@@ -186,33 +220,46 @@ def mtp_from_logits(c_logits: torch.Tensor, s_tensor: torch.Tensor, check: bool 
     _chk(c_logits, F32, "c_logits")
     if c_logits.dim() != 3 or c_logits.shape[1:] != (C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR):
         raise ValueError("c_logits must be [N,15,230]")
-    if s_tensor.dim() != 4 or s_tensor.shape[-2:] != (4, 32):
-        raise ValueError("s_tensor must be [B,n_bars,4,32]")
-    s = s_tensor.to(F32).contiguous()
-    G, N, dev = s.numel() // 128, c_logits.shape[0], c_logits.device
-    bn, npt = torch.empty(G, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
-    mtp = torch.empty(*s_tensor.shape, C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR, dtype=F32, device=dev)
-    call("pm_mtp_from_logits", ptr(c_logits), ptr(s), G, N, ptr(bn), ptr(npt), ptr(mtp), stream())
-    if check:
-        active = int(npt[G])
-        if active != N:
-            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, c_logits has {N} nodes")
-    return mtp
+    return _mtp("pm_mtp_from_logits", c_logits, "c_logits", s_tensor, check)
+
+
+def _real(v) -> bool:
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def _integer(v) -> bool:
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _four(v, name: str):
+    """An int or four ints (one per track) as a tuple of four ints."""
+    out = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else (v,) * 4
+    if len(out) != 4 or not all(_integer(a) for a in out):
+        raise ValueError(f"{name} must be an int or four ints (one per track), got {v!r}")
+    return tuple(int(a) for a in out)
+
+
+def _mask_words(array, shape, name: str):
+    """A bool array-like of `shape` = (4, 32 w) as 4 x w words of 32 bits (bit b of word j = element 32 j + b); None = all set."""
+    if array is None:
+        return [[0xFFFFFFFF] * (shape[1] // 32) for _ in range(4)]
+    a = array.detach().cpu().numpy() if isinstance(array, torch.Tensor) else np.asarray(array)
+    if a.shape != shape or a.dtype != np.bool_:
+        raise ValueError(f"{name} must be a bool array of shape [{shape[0]},{shape[1]}], got {a.dtype} {tuple(a.shape)}")
+    bits = a.reshape(4, -1, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
+    return [[int(w) for w in row] for row in bits.sum(-1)]
 
 
 def check_sampling_args(temperature=None, top_k=None, top_p=None, seed=None) -> None:
     """The argument rules of sampled generation (`sample_tokens`, `generate.generate_music`); None = left at its default.
     Raises ValueError naming the argument."""
-    import math
-    import numbers
-    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    if temperature is not None and not (real(temperature) and math.isfinite(temperature) and temperature >= 0):
+    if temperature is not None and not (_real(temperature) and math.isfinite(temperature) and temperature >= 0):
         raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
-    if top_k is not None and not (isinstance(top_k, numbers.Integral) and not isinstance(top_k, bool) and top_k >= 1):
+    if top_k is not None and not (_integer(top_k) and top_k >= 1):
         raise ValueError(f"top_k must be an int >= 1, got {top_k!r}")
-    if top_p is not None and not (real(top_p) and 0 < top_p <= 1):
+    if top_p is not None and not (_real(top_p) and 0 < top_p <= 1):
         raise ValueError(f"top_p must be a number in (0, 1], got {top_p!r}")
-    if seed is not None and not (isinstance(seed, numbers.Integral) and not isinstance(seed, bool) and 0 <= seed < 1 << 32):
+    if seed is not None and not (_integer(seed) and 0 <= seed < 1 << 32):
         raise ValueError(f"seed must be an int in [0, 2^32), got {seed!r}")
 
 
@@ -242,44 +289,27 @@ def mtp_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool = 
     _chk(tokens, I32, "tokens")
     if tokens.dim() != 3 or tokens.shape[1:] != (C.MAX_SIMU_TOKENS - 1, 2):
         raise ValueError("tokens must be [N,15,2]")
-    if s_tensor.dim() != 4 or s_tensor.shape[-2:] != (4, 32):
-        raise ValueError("s_tensor must be [B,n_bars,4,32]")
-    s = s_tensor.to(F32).contiguous()
-    G, N, dev = s.numel() // 128, tokens.shape[0], tokens.device
-    bn, npt = torch.empty(G, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
-    mtp = torch.empty(*s_tensor.shape, C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR, dtype=F32, device=dev)
-    call("pm_mtp_from_tokens", ptr(tokens), ptr(s), G, N, ptr(bn), ptr(npt), ptr(mtp), stream())
-    if check:
-        active = int(npt[G])
-        if active != N:
-            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, tokens has {N} nodes")
-    return mtp
+    return _mtp("pm_mtp_from_tokens", tokens, "tokens", s_tensor, check)
 
 
 def node_tracks(s_tensor: torch.Tensor, N: int, check: bool = True) -> torch.Tensor:
     """`pm_node_tracks`: uint8 [N], the track index (0 Drums .. 3 Strings) of every node of the binary structure `s_tensor`
     ([...,4,32], any dtype), nodes numbered in cell order as in `mtp_from_tokens`.  Entries behind the active cells are 0.
     `check` reads the active-cell count back (one host sync) and raises when it differs from `N`."""
-    if s_tensor.dim() < 3 or s_tensor.shape[-2:] != (4, 32):
-        raise ValueError("s_tensor must be [...,4,32]")
+    s, G, bn, npt = _structure_prologue(s_tensor, s_tensor.device, s_tensor.dim() >= 3, "s_tensor must be [...,4,32]")
     if not s_tensor.is_cuda:
         raise HipExtensionError(f"s_tensor lives on {s_tensor.device}: the HIP path needs device tensors (no CPU fallback)")
     N = int(N)
     if N < 0:
         raise ValueError(f"N must be >= 0, got {N}")
-    s = s_tensor.to(F32).contiguous()
-    G, dev = s.numel() // 128, s.device
-    out = torch.empty(N, dtype=U8, device=dev)
+    out = torch.empty(N, dtype=U8, device=s.device)
     if G == 0:
         if check and N:
             raise ValueError(f"shape mismatch: s_tensor has 0 active cells, {N} nodes asked for")
         return out.zero_()
-    bn, npt = torch.empty(G, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
     call("pm_node_tracks", ptr(s), G, N, ptr(bn), ptr(npt), ptr(out) if N else None, stream())
     if check:
-        active = int(npt[G])
-        if active != N:
-            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, {N} nodes asked for")
+        _check_active(npt[G], N, f"{N} nodes asked for")
     return out
 
 
@@ -294,28 +324,24 @@ def notes_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool 
         raise ValueError("tokens and s_tensor must be tensors")
     if tokens.dtype != I32 or tokens.dim() != 3 or tokens.shape[1:] != (C.MAX_SIMU_TOKENS - 1, 2):
         raise ValueError(f"tokens must be int32 [N,15,2], got {tokens.dtype} {tuple(tokens.shape)}")
-    if s_tensor.dim() != 4 or s_tensor.shape[-2:] != (4, 32) or s_tensor.shape[0] == 0 or s_tensor.shape[1] == 0:
-        raise ValueError(f"s_tensor must be [B,n_bars,4,32] with B, n_bars >= 1, got {tuple(s_tensor.shape)}")
+    s, G, bn, npt, seg_count, seg_ptr = _structure_prologue(
+        s_tensor, tokens.device, s_tensor.dim() == 4 and 0 not in s_tensor.shape[:2],
+        f"s_tensor must be [B,n_bars,4,32] with B, n_bars >= 1, got {tuple(s_tensor.shape)}", segments=True)
     for t, name in ((tokens, "tokens"), (s_tensor, "s_tensor")):
         if not t.is_cuda:
             raise HipExtensionError(f"{name} lives on {t.device}: the HIP path needs device tensors (no CPU fallback)")
     if s_tensor.device != tokens.device:
         raise ValueError(f"s_tensor lives on {s_tensor.device}, tokens on {tokens.device}")
     tokens = tokens.contiguous()
-    s = s_tensor.to(F32).contiguous()
     B, n_bars = s_tensor.shape[:2]
-    G, N, dev = B * n_bars, tokens.shape[0], tokens.device
+    N, dev = tokens.shape[0], tokens.device
     cap = (C.MAX_SIMU_TOKENS - 1) * N
-    ws = torch.empty(4 * G + (4 * G + 1) + G + (G + 1), dtype=I32, device=dev)
-    seg_count, seg_ptr, bn, npt = ws.split([4 * G, 4 * G + 1, G, G + 1])
     notes = torch.empty(cap, 3, dtype=I32, device=dev)
     track_ptr, totals = torch.empty(4 * B + 1, dtype=I32, device=dev), torch.empty(2, dtype=I32, device=dev)
     call("pm_notes_from_tokens", ptr(tokens) if N else None, ptr(s), G, n_bars, N, ptr(seg_count), ptr(seg_ptr), ptr(bn), ptr(npt),
          ptr(notes) if N else None, cap, ptr(track_ptr), ptr(totals), stream())
     if check:
-        active = int(totals[1])
-        if active != N:
-            raise ValueError(f"shape mismatch: s_tensor has {active} active cells, tokens has {N} nodes")
+        _check_active(totals[1], N, f"tokens has {N} nodes")
     return notes, track_ptr, totals
 
 
@@ -326,37 +352,19 @@ def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_no
     or four ints (Drums, Bass, Guitar, Strings) with 0 <= min_notes <= max_notes and 1 <= max_notes <= 14;
     `allowed_pitches` None or a bool array-like [4,128]; `node_track`, when given, uint8 [N] on the device of `c_logits`.
     Returns ((T_pitch, T_duration), min_notes [4], max_notes [4], pitch_mask: 4 x 4 words of 32 bits)."""
-    import math
-    import numbers
-    import numpy as np
-    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    integer = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
     if temperature is None:
         temperature = 1.0
     pair = tuple(temperature) if isinstance(temperature, (tuple, list)) else (temperature, temperature)
-    if len(pair) != 2 or not all(real(v) and math.isfinite(v) and v >= 0 for v in pair):
+    if len(pair) != 2 or not all(_real(v) and math.isfinite(v) and v >= 0 for v in pair):
         raise ValueError(f"temperature must be a finite number >= 0 or a pair (pitch, duration) of them, got {temperature!r}")
     check_sampling_args(None, top_k, top_p, seed)
-
-    def four(v, name):
-        out = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else (v,) * 4
-        if len(out) != 4 or not all(integer(a) for a in out):
-            raise ValueError(f"{name} must be an int or four ints (one per track), got {v!r}")
-        return tuple(int(a) for a in out)
-    mx = four(max_notes, "max_notes")
+    mx = _four(max_notes, "max_notes")
     if not all(1 <= a <= C.MAX_SIMU_TOKENS - 2 for a in mx):
         raise ValueError(f"max_notes must be in [1, {C.MAX_SIMU_TOKENS - 2}], got {max_notes!r}")
-    mn = four(min_notes, "min_notes")
+    mn = _four(min_notes, "min_notes")
     if not all(0 <= a <= b for a, b in zip(mn, mx)):
         raise ValueError(f"min_notes must satisfy 0 <= min_notes <= max_notes = {max_notes!r}, got {min_notes!r}")
-    if allowed_pitches is None:
-        words = [[0xFFFFFFFF] * 4 for _ in range(4)]
-    else:
-        a = allowed_pitches.detach().cpu().numpy() if isinstance(allowed_pitches, torch.Tensor) else np.asarray(allowed_pitches)
-        if a.shape != (4, 128) or a.dtype != np.bool_:
-            raise ValueError(f"allowed_pitches must be a bool array of shape [4,128], got {a.dtype} {tuple(a.shape)}")
-        bits = a.reshape(4, 4, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
-        words = [[int(w) for w in row] for row in bits.sum(-1)]
+    words = _mask_words(allowed_pitches, (4, 128), "allowed_pitches")
     if node_track is not None:
         if not isinstance(node_track, torch.Tensor) or node_track.dtype != U8 or node_track.dim() != 1 or not node_track.is_contiguous():
             raise ValueError("node_track must be a contiguous uint8 tensor [N]")
@@ -406,37 +414,21 @@ def check_structure_args(temperature=1.0, threshold=0.5, min_active=0, max_activ
     0 <= min_active <= max_active <= 32 and min_active no larger than the track's allowed steps; `allowed_steps` None or a
     bool array-like [4,32]; some track must keep max_active > 0 and an allowed step.
     Returns (temperature, bias [4] = logit(threshold) in double, min_active [4], max_active [4], step_mask: 4 words of 32 bits)."""
-    import math
-    import numbers
-    import numpy as np
-    real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    integer = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
-    if not (real(temperature) and math.isfinite(temperature) and temperature >= 0):
+    if not (_real(temperature) and math.isfinite(temperature) and temperature >= 0):
         raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
     check_sampling_args(None, None, None, seed)
     th = tuple(threshold) if isinstance(threshold, (tuple, list, np.ndarray)) else (threshold,) * 4
-    if len(th) != 4 or not all(real(v) and 0 < v < 1 for v in th):
+    if len(th) != 4 or not all(_real(v) and 0 < v < 1 for v in th):
         raise ValueError(f"threshold must be a number or four numbers (one per track) in (0, 1), got {threshold!r}")
     bias = tuple(math.log(float(v) / (1.0 - float(v))) for v in th)          # (finite in fp32 for every double in (0, 1))
 
-    def four(v, name):
-        out = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else (v,) * 4
-        if len(out) != 4 or not all(integer(a) for a in out):
-            raise ValueError(f"{name} must be an int or four ints (one per track), got {v!r}")
-        return tuple(int(a) for a in out)
-    mx = four(max_active, "max_active")
+    mx = _four(max_active, "max_active")
     if not all(0 <= a <= 32 for a in mx):
         raise ValueError(f"max_active must be in [0, 32], got {max_active!r}")
-    mn = four(min_active, "min_active")
+    mn = _four(min_active, "min_active")
     if not all(0 <= a <= b for a, b in zip(mn, mx)):
         raise ValueError(f"min_active must satisfy 0 <= min_active <= max_active = {max_active!r}, got {min_active!r}")
-    if allowed_steps is None:
-        words = [0xFFFFFFFF] * 4
-    else:
-        a = allowed_steps.detach().cpu().numpy() if isinstance(allowed_steps, torch.Tensor) else np.asarray(allowed_steps)
-        if a.shape != (4, 32) or a.dtype != np.bool_:
-            raise ValueError(f"allowed_steps must be a bool array of shape [4,32], got {a.dtype} {tuple(a.shape)}")
-        words = [int(w) for w in (a.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1)]
+    words = [row[0] for row in _mask_words(allowed_steps, (4, 32), "allowed_steps")]
     steps = [bin(w).count("1") for w in words]
     if not all(a <= n for a, n in zip(mn, steps)):
         raise ValueError(f"min_active must not exceed the allowed steps of its track ({steps} in allowed_steps), got {min_active!r}")

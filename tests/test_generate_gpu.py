@@ -74,6 +74,44 @@ def test_mtp_from_logits_matches_oracle(G, p):
     assert torch.equal(got, vae_cpu.mtp_from_logits(c, s))
 
 
+@pytest.mark.parametrize("G", [9, 1025])
+def test_node_numbering_is_one_across_the_entry_points(G):
+    """`graph_build`, `node_tracks` and `notes_from_tokens` number the nodes of one structure alike: the active cells in cell
+    order, as numpy counts them.  G = 9: an odd bar count, a partly filled block; G = 1025: the one-workgroup scans with two
+    bars for a thread.  About 10 % of the cells active; every fourth bar holds a single cell (an empty bar would be changed in
+    place by `graph_build` alone)."""
+    rng = np.random.default_rng(G)
+    s = rng.random((G, 4, 32)) < 0.1
+    s[::4] = False
+    for g in range(0, G, 4):
+        s[g, g % 4, (5 * g) % 32] = True
+    cells = np.flatnonzero(s)                                        # node n sits on cell cells[n]
+    N = len(cells)
+    assert G < N <= 128 * 128 and (s.reshape(G, -1).sum(1) == 1).sum() >= G // 4
+    sd = torch.from_numpy(s).to(DEV)
+
+    g = ops.graph_build(sd.float(), G)
+    assert g["num_nodes"] == N and np.array_equal(g["node_cell"].cpu().numpy(), cells)
+    assert np.array_equal(g["node_ptr"].cpu().numpy(), np.concatenate([[0], np.cumsum(s.reshape(G, -1).sum(1))]))
+    assert np.array_equal(g["bars"].cpu().numpy(), cells // 128) and not g["batch"].any()
+
+    assert np.array_equal(ops.node_tracks(sd, N).cpu().numpy(), (cells // 32) % 4)
+
+    # node n holds the two notes of pitch n % 128 and n // 128, then the EOS: the notes name the node they came from
+    tok = np.zeros((N, 15, 2), dtype=np.int32)
+    tok[:, 0, 0], tok[:, 1, 0], tok[:, 2] = np.arange(N) % 128, np.arange(N) // 128, (129, 97)
+    notes, track_ptr, totals = ops.notes_from_tokens(torch.from_numpy(tok).to(DEV), sd.view(1, G, 4, 32))
+    assert totals.tolist() == [2 * N, N]
+    notes, track_ptr = notes[:2 * N].cpu().numpy(), track_ptr.cpu().numpy()
+    for k in range(4):                                               # a track's rows: by bar, then by timestep, two per node
+        n = np.flatnonzero((cells // 32) % 4 == k)
+        rows = notes[track_ptr[k]:track_ptr[k + 1]]
+        assert len(rows) == 2 * len(n), k
+        assert np.array_equal(rows[:, 0], np.repeat(cells[n] // 128 * 32 + cells[n] % 32, 2)), k
+        assert np.array_equal(rows[0::2, 1], n % 128) and np.array_equal(rows[1::2, 1], n // 128), k
+        assert (rows[:, 2] == 1).all(), k
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_generate_music_matches_reference(case):
     """generate.py:21-37 with s_cond = None: decoder -> thresholded structure -> device graph build -> content decoder
