@@ -375,6 +375,46 @@ int pm_notes_from_tokens(const int32_t* tokens /* [N,15,2] pitch, duration */, c
                          int32_t* notes /* [capacity,3] */, int64_t capacity, int32_t* track_ptr /* [4B+1] */,
                          int32_t* totals /* [2]: notes M, active cells */, pm_stream_t stream);
 
+/* ------------------------------------------------------------------ Notes in
+ * The inverse of pm_notes_from_tokens: pieces held as note events become the structure tensor and the node tokens the encoder
+ * consumes.  The reference does this on the host, one track at a time, while it preprocesses MIDI files (preprocess.py:118-157),
+ * and switches cell [0,0] of an empty bar on when it builds the bar graphs (data.py:148-153); pm_tokens_from_notes does both
+ * for a batch of pieces on the device.  Additive, same ABI version.
+ *
+ * notes is [M,3] int32 (time, pitch, duration) and track_ptr [4B+1] int32, as pm_notes_from_tokens writes them: the rows of
+ * (piece i, track k) are notes[track_ptr[4i+k] : track_ptr[4i+k+1]].  Contract: track_ptr starts at 0, does not decrease and
+ * ends at or below M (rows behind its last entry belong to no track: the notes buffer of pm_notes_from_tokens is sized for
+ * the worst case); inside a track's range the times do not decrease and lie in [0, 32 n_bars).  Cell (bar g = i * n_bars + b, track k,
+ * timestep s) holds the rows of its track whose time is 32 b + s, in row order:
+ *   slots    : slot 0 is (SOS 128, SOS 96); the first 14 rows take the slots 1..14 as (clamp(pitch, 0, 127),
+ *              clamp(duration, 1, 96) - 1); later rows are dropped (preprocess.py:136-138); the slot behind the last kept row is
+ *              (EOS 129, EOS 97), the rest (PAD 130, PAD 98).
+ *   activity : a cell is active iff it holds a row; a bar without an active cell gets cell [0,0] switched on with no note.
+ *   s_tensor [G,4,32] fp32 0 / 1, G = B * n_bars; every entry is written.
+ *   tokens   [capacity,16,2] int32 (pitch, duration): node n is the n-th active cell in cell order, as in pm_graph_emit and
+ *            pm_node_tracks.  Nodes at `capacity` and beyond are not written, nor are rows of `tokens` behind the last node;
+ *            min(M + G, 128 G) nodes always suffice for input that keeps the contract.
+ *   status   [5]: rows whose time is outside [0, 32 n_bars); rows whose time is above the next row's of the same track;
+ *            track_ptr entries that break the contract (entry 0 unless it is 0; a later entry outside [0, M] or below the
+ *            entry before it); notes dropped for lack of slots; the number of nodes N.
+ *   scratch  PM_NOTES_IN_SCRATCH(B, n_bars) int32.
+ * Input that breaks the contract is counted, never followed: every track's range is clamped into [0, M] before a row is read
+ * and every cell's rows are found by binary search inside that range, so nothing outside notes[0:M] and track_ptr[0:4B+1] is
+ * read; what s_tensor and tokens then hold is still a function of the input alone.  The counts cover the rows inside the
+ * clamped ranges.
+ * Six launches on the stream (the check, the cells' rows, active cells per bar, their scan, the nodes, the status sums), no
+ * host read, no atomics: two calls on the same inputs write the same bytes.  12 B are read per note by the check, and per
+ * cell about 4 log2(notes of the track) rows by each of the two search passes; 128 B are written per node and 512 B per bar.
+ * PM_E_INVALID (before any launch): a NULL pointer (notes may be NULL when M == 0, tokens when capacity == 0); B <= 0,
+ *   n_bars <= 0, M < 0 or capacity < 0; 128 G, 3 M or 32 capacity >= 2^31; a pointer not 4-byte aligned, tokens not 16-byte
+ *   aligned; any two buffers overlapping except the two inputs. */
+#define PM_NOTES_IN_SCRATCH(B, n_bars) (3 * (int64_t)(B) * (n_bars) + 1 + 12 * (int64_t)(B))
+int pm_tokens_from_notes(const int32_t* notes /* [M,3] time, pitch, duration */, const int32_t* track_ptr /* [4B+1] */,
+                         int32_t B, int32_t n_bars, int64_t M, float* s_tensor /* [B*n_bars,4,32] */,
+                         int32_t* tokens /* [capacity,16,2] */, int64_t capacity,
+                         int32_t* scratch /* [PM_NOTES_IN_SCRATCH(B, n_bars)] */, int32_t* status /* [5] */,
+                         pm_stream_t stream);
+
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):
  *   A[n, r*d:(r+1)*d] = mean_{e: dst=n, type=r} keep_e * relu(x[src_e] * T[dist_e]) / (1-p)

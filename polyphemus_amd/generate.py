@@ -2,7 +2,9 @@
 csrc/generate.hip and csrc/graph.hip: the decoder pass, the thresholded structure, and the dense multitrack pianoroll,
 without the reference's host synchronisations (`nonzero`, per-sample Python graph building, three full-tensor writes).
 Converting the pianoroll to MIDI (muspy) is outside the hot path and stays with the caller; `generate_notes` returns the
-pieces as ordered note events instead (`NoteBatch`, csrc/notes.hip), which is what that conversion reads out of the pianoroll."""
+pieces as ordered note events instead (`NoteBatch`, csrc/notes.hip), which is what that conversion reads out of the pianoroll.
+The other direction has no entry point in the reference: `NoteBatch.from_lists` / `to_graph` (csrc/notes_in.hip) turn notes into the
+batch the encoder consumes, `encode_notes` and `vary_notes` encode a piece and decode around it."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -207,6 +209,40 @@ class NoteBatch:
                                       notes=[muspy.Note(t, p, d, 64) for (t, p, d) in rows]))
         return muspy.Music(tracks=tracks, metadata=muspy.Metadata(), resolution=self.resolution)
 
+    @classmethod
+    def from_lists(cls, pieces, n_bars: int, device="cuda", resolution: int = 8) -> "NoteBatch":
+        """The inverse of `tolist()`: `pieces` holds, per piece, four lists (Drums, Bass, Guitar, Strings) of (time, pitch,
+        duration) ints, times in steps of a 1 / `resolution` beat inside [0, 32 n_bars).  Every track is stable-sorted by
+        time on the host, so the list order of the notes of one timestep is kept: it decides which slots they take, and past
+        the 14th which are dropped (the reference's "lowest position available", preprocess.py:131-144).  Raises ValueError,
+        before the device is touched, on a piece without exactly four tracks, a row that is not three ints or a time outside
+        the piece.  `totals` holds the notes M and the distinct (piece, track, time) cells."""
+        if not (ops._integer(n_bars) and n_bars >= 1):
+            raise ValueError(f"n_bars must be an int >= 1, got {n_bars!r}")
+        if not isinstance(pieces, (list, tuple)) or len(pieces) == 0:
+            raise ValueError("pieces must be a non-empty list of pieces")
+        rows, track_ptr, cells, lim = [], [0], 0, 1 << 31
+        for i, piece in enumerate(pieces):
+            if not isinstance(piece, (list, tuple)) or len(piece) != 4 or not all(isinstance(t, (list, tuple)) for t in piece):
+                raise ValueError(f"piece {i} must be four lists of notes (Drums, Bass, Guitar, Strings)")
+            for k, track in enumerate(piece):
+                for r in track:
+                    if not isinstance(r, (list, tuple)) or len(r) != 3 or not all(ops._integer(v) and -lim <= v < lim for v in r):
+                        raise ValueError(f"piece {i}, track {TRACKS[k]}: a note must be three ints (time, pitch, duration), got {r!r}")
+                    if not 0 <= r[0] < 32 * n_bars:
+                        raise ValueError(f"piece {i}, track {TRACKS[k]}: time {r[0]} is outside the piece [0, {32 * n_bars})")
+                rows.extend(sorted((tuple(int(v) for v in r) for r in track), key=lambda r: r[0]))
+                cells += len({r[0] for r in track})
+                track_ptr.append(len(rows))
+        notes = torch.from_numpy(np.asarray(rows, np.int32).reshape(-1, 3))
+        return cls(notes.to(device), torch.tensor(track_ptr, dtype=torch.int32).to(device),
+                   torch.tensor([len(rows), cells], dtype=torch.int32).to(device), int(n_bars), int(resolution))
+
+    def to_graph(self):
+        """The pieces as the `BarGraphBatch` the encoder consumes (`graphs.device_batch_from_notes`): two host reads."""
+        from .graphs import device_batch_from_notes
+        return device_batch_from_notes(self.notes, self.track_ptr, self.n_bars)
+
 
 def generate_notes(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
                    chord_rules=None, structure_rules=None, return_tokens=False):
@@ -220,3 +256,56 @@ def generate_notes(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     notes, track_ptr, totals = ops.notes_from_tokens(tokens, s_tensor)
     batch = NoteBatch(notes, track_ptr, totals, int(s_tensor.shape[1]))
     return (batch, s_tensor, tokens) if return_tokens else (batch, s_tensor)
+
+
+def _encode(vae, batch):
+    """(mu, log_var, graph) of a NoteBatch: the encoder in eval mode without gradients, the mode it found restored."""
+    if not isinstance(batch, NoteBatch):
+        raise ValueError(f"batch must be a NoteBatch, got {type(batch).__name__}")
+    if batch.n_bars != vae.cfg["n_bars"]:
+        raise ValueError(f"batch holds pieces of n_bars = {batch.n_bars}, the model takes n_bars = {vae.cfg['n_bars']}")
+    graph = batch.to_graph()
+    was_training = vae.training
+    vae.eval()
+    try:
+        with torch.no_grad():
+            mu, log_var = vae.encoder(graph)
+    finally:
+        vae.train(was_training)
+    return mu, log_var, graph
+
+
+def encode_notes(vae, batch):
+    """The latent of pieces held as notes: (mu, log_var) [B,d] of `vae.encoder` on `batch.to_graph()` (a `NoteBatch`, from
+    `generate_notes` or `NoteBatch.from_lists`), in eval mode and without gradients; `vae.training` is left as found.  Raises
+    ValueError when `batch.n_bars` is not the model's."""
+    return _encode(vae, batch)[:2]
+
+
+def vary_notes(vae, batch, strength=1.0, keep_structure=False, seed=None, return_z=False, **generate_notes_kwargs):
+    """Variations of pieces held as notes: `batch` is encoded (`encode_notes`) and `generate_notes` decodes
+    z = mu + strength * exp(log_var / 2) * eps.  `eps` is drawn on the CPU from a generator seeded with `seed`, None takes
+    torch's global generator; the same `seed` goes on to `generate_notes` for all its levels.  `strength` is finite and >= 0;
+    0 is the reconstruction at mu.  `keep_structure` decodes on the input's own structure (its bar graphs as `s_cond`, its
+    cells as `s_tensor_cond`): same rhythm, new notes; it excludes `structure_rules` with the error `generate_music` raises.
+    Every other keyword is `generate_notes`'.  Returns what `generate_notes` returns, (NoteBatch, s_tensor[, tokens]), with
+    `return_z` the latent appended."""
+    if not (ops._real(strength) and np.isfinite(strength) and strength >= 0):
+        raise ValueError(f"strength must be a finite number >= 0, got {strength!r}")
+    ops.check_sampling_args(seed=seed)
+    for k in ("s_cond", "s_tensor_cond"):
+        if k in generate_notes_kwargs:
+            raise ValueError(f"{k} is not an argument of vary_notes: keep_structure=True passes the input's structure")
+    if keep_structure and generate_notes_kwargs.get("structure_rules") is not None:
+        raise ValueError("structure_rules draws the structure itself: it needs s_cond and s_tensor_cond both None")
+    mu, log_var, graph = _encode(vae, batch)
+    z = mu
+    if strength != 0:
+        gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+        eps = torch.randn(mu.shape, generator=gen, dtype=torch.float32).to(mu.device)
+        z = mu + float(strength) * torch.exp(0.5 * log_var) * eps
+    s_cond = s_tensor_cond = None
+    if keep_structure:
+        s_cond, s_tensor_cond = graph, graph.s_tensor.view(-1, batch.n_bars, 4, 32).bool()
+    out = generate_notes(vae, z, s_cond, s_tensor_cond, seed=seed, **generate_notes_kwargs)
+    return out + (z,) if return_z else out

@@ -242,3 +242,16 @@ def device_batch_from_structure(s_tensor: torch.Tensor, n_bars: int, token_grid:
     if token_grid is not None:
         kw["tokens"] = token_grid.reshape(-1, C.MAX_SIMU_TOKENS, 2).to(torch.int32)[g["node_cell"].long()].contiguous()
     return BarGraphBatch(**kw)
+
+
+def device_batch_from_notes(notes: torch.Tensor, track_ptr: torch.Tensor, n_bars: int) -> BarGraphBatch:
+    """The batch of `device_batch_from_structure(s_tensor, n_bars, token_grid)` for pieces held as note events (the
+    `NoteBatch` layout: `notes` int32 [M,3] rows (time, pitch, duration), `track_ptr` int32 [4B+1], cuda), without the
+    token grid: `ops.tokens_from_notes` (csrc/notes_in.hip) writes the structure and the nodes' token rows, `ops.graph_build`
+    the graphs of that structure.  Same keys and flags.  Two host reads: the node count with the input check, and
+    `graph_build`'s (N, E)."""
+    from . import ops
+    s, tokens, _ = ops.tokens_from_notes(notes, track_ptr, n_bars)
+    batch = device_batch_from_structure(s, n_bars)
+    batch.tokens = tokens
+    return batch

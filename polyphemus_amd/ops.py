@@ -345,6 +345,54 @@ def notes_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool 
     return notes, track_ptr, totals
 
 
+def tokens_from_notes(notes: torch.Tensor, track_ptr: torch.Tensor, n_bars: int, check: bool = True):
+    """`pm_tokens_from_notes` ("Notes in" in include/polyphemus_hip.h), the inverse of `notes_from_tokens`: pieces held as note
+    events become what the encoder consumes.  `notes` int32 [M,3] rows (time, pitch, duration) and `track_ptr` int32 [4B+1]
+    are the `NoteBatch` layout (rows behind track_ptr[4B] are ignored); a piece is `n_bars` bars of 32 steps.  Returns
+    (s_tensor fp32 [B n_bars,4,32] 0/1, tokens int32 [N,16,2], info): the nodes are the active cells in cell order, the rows
+    `graph_build(s_tensor, n_bars)` numbers; a cell keeps its first 14 notes in row order and a bar without a note gets cell
+    [0,0] with none (preprocess.py:118-157, data.py:148-153).  ONE host read brings the node count N, which sizes `tokens`,
+    and the input check with it: info = {"dropped": notes that found no slot, "out_of_range", "out_of_order",
+    "bad_track_ptr", "num_nodes"}.  With `check` rows whose time is outside the piece or out of order and bad `track_ptr`
+    entries raise ValueError with their count; without it they are only counted (the kernels never follow them)."""
+    for t, name in ((notes, "notes"), (track_ptr, "track_ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if notes.dtype != I32 or notes.dim() != 2 or notes.shape[1] != 3:
+        raise ValueError(f"notes must be int32 [M,3], got {notes.dtype} {tuple(notes.shape)}")
+    if track_ptr.dtype != I32 or track_ptr.dim() != 1 or track_ptr.shape[0] < 5 or track_ptr.shape[0] % 4 != 1:
+        raise ValueError(f"track_ptr must be int32 [4B+1] with B >= 1, got {track_ptr.dtype} {tuple(track_ptr.shape)}")
+    if not (_integer(n_bars) and n_bars >= 1):
+        raise ValueError(f"n_bars must be an int >= 1, got {n_bars!r}")
+    for t, name in ((notes, "notes"), (track_ptr, "track_ptr")):
+        if not t.is_cuda:
+            raise HipExtensionError(f"{name} lives on {t.device}: the HIP path needs device tensors (no CPU fallback)")
+    if track_ptr.device != notes.device:
+        raise ValueError(f"track_ptr lives on {track_ptr.device}, notes on {notes.device}")
+    notes, track_ptr, n_bars = notes.contiguous(), track_ptr.contiguous(), int(n_bars)
+    B, M, dev = track_ptr.shape[0] // 4, notes.shape[0], notes.device
+    G = B * n_bars
+    cap = min(M + G, 128 * G)                        # every node but an empty bar's has a note of its own
+    s = torch.empty(G, 4, 32, dtype=F32, device=dev)
+    buf = torch.empty(cap, C.MAX_SIMU_TOKENS, 2, dtype=I32, device=dev)
+    scratch, status = torch.empty(3 * G + 1 + 12 * B + 5, dtype=I32, device=dev).split([3 * G + 1 + 12 * B, 5])
+    call("pm_tokens_from_notes", ptr(notes) if M else None, ptr(track_ptr), B, n_bars, M, ptr(s), ptr(buf), cap, ptr(scratch),
+         ptr(status), stream())
+    out_of_range, out_of_order, bad_ptr, dropped, N = status.tolist()             # the one host read
+    if check or N > cap:
+        for count, what in ((bad_ptr, f"track_ptr: {{}} bad entries (below the entry before them, outside [0, {M}] or, the "
+                                      "first, not 0)"),
+                            (out_of_range, f"notes: {{}} rows out of range (a time outside [0, {32 * n_bars}))"),
+                            (out_of_order, "notes: {} rows out of order (a time above the next row's of the same track)")):
+            if count:
+                raise ValueError(what.format(count))
+    if N > cap:                                      # (only input that breaks the contract gets here)
+        raise ValueError(f"notes: {N} active cells out of {M} rows and {G} bars")
+    tokens = buf if N == cap else buf[:N].clone()    # (the clone lets the worst-case buffer go)
+    return s, tokens, dict(dropped=dropped, out_of_range=out_of_range, out_of_order=out_of_order, bad_track_ptr=bad_ptr,
+                           num_nodes=N)
+
+
 def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
                      c_logits=None, node_track=None):
     """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
