@@ -415,6 +415,63 @@ int pm_tokens_from_notes(const int32_t* notes /* [M,3] time, pitch, duration */,
                          int32_t* scratch /* [PM_NOTES_IN_SCRATCH(B, n_bars)] */, int32_t* status /* [5] */,
                          pm_stream_t stream);
 
+/* ------------------------------------------------------------------ Infill
+ * Regenerate chosen tracks, bars and steps of a piece around the notes that are kept: the input's structure and node tokens
+ * (pm_tokens_from_notes) are merged with what the model gives for the same latent, under a region mask.  The decoder is not
+ * autoregressive, so kept and regenerated cells are independent given z and the bar graph: the merge is two passes over the
+ * bar layout, one for the structure before the content decoder runs and one for the tokens after the draw.  Additive, same
+ * ABI version.
+ *
+ * region is uint8 [R,4,32] (0 / non-zero: the model rewrites the cell) in the cell layout of a structure tensor; bar g reads
+ * region row g % R.  R is G (a mask per piece and bar) or a divisor of G (R = n_bars: one mask shared by all pieces).
+ *
+ * pm_infill_structure: a cell is on iff (region ? s_model != 0 : s_in != 0).
+ *   s_in     fp32 [G,4,32] 0 / 1, the input's structure as pm_tokens_from_notes wrote it;
+ *   s_model  uint8 [G,4,32], what pm_binary_from_logits or pm_sample_structure wrote;
+ *   no empty bar : where that leaves a bar without a cell, cell [0,0] is switched on (data.py:152-153, the rule
+ *            pm_tokens_from_notes and pm_graph_count apply), whether or not [0,0] lies in the region; bar_forced[g] = 1
+ *            there, else 0;
+ *   outputs  s_f32 and / or s_u8 [G,4,32] hold 0 / 1 (either may be NULL, not both); bar_forced int32 [G].
+ *   One launch, a bar per half-wave, every input read once, every output written once, no atomics, no LDS, no workspace.
+ *   768 B are read per bar (s_in 512, s_model 128, region 128) and up to 644 B written.
+ *
+ * pm_infill_tokens: the kept cells' tokens go from the input's node numbering into the merged structure's.
+ *   s_out    fp32 [G,4,32], the merged structure after the decoder's graph build; its nodes and those of s_in are the active
+ *            cells in cell order, as in pm_node_tracks;
+ *   tokens_in int32 [N_in,16,2], the input's node tokens (slot 0 = SOS) as pm_tokens_from_notes wrote them;
+ *   tokens   int32 [N,15,2], in / out: on entry the drawn tokens of every node of s_out, the form pm_notes_from_tokens reads.
+ *   A cell that is on in s_out and
+ *     inside the region                  : its row stays as drawn;
+ *     outside the region, on in s_in     : tokens[n_out, j] = tokens_in[n_in, j + 1] for j = 0..14 (the SOS slot is dropped);
+ *     outside the region, off in s_in    : (the forced [0,0]) slot 0 is (EOS 129, EOS 97), slots 1..14 are (PAD 130, PAD 98):
+ *                                          the chord of a cell without a note (preprocess.py:118-157), which
+ *                                          pm_tokens_from_notes gives an empty bar's cell.
+ *   Nothing is read at or beyond node N_in and nothing is written at or beyond node N: a mismatch is counted, never followed.
+ *   A kept cell whose input node lies at or beyond N_in has no source and takes the chord without a note; a cell whose node
+ *   in s_out lies at or beyond N is neither written nor counted as kept.
+ *   bar_forced int32 [G] as pm_infill_structure wrote it, or NULL (no bar counted).
+ *   status   [5]: active cells of s_out; active cells of s_in; kept nodes; kept nodes without a source; bars forced (the sum
+ *            of bar_forced).  Built from per-bar counts in scratch and summed by one wave.
+ *   scratch  PM_INFILL_SCRATCH(G) int32: active cells per bar and node_ptr of both structures, two counts per bar.
+ *   Six launches on the stream (active cells per bar and their scan for each structure, the rows, the status sums), no host
+ *   read, no atomics: two calls on the same inputs write the same bytes.  A row of tokens is 120 B, so rows are 8-byte
+ *   aligned, not 16: a kept node is fifteen 8-byte loads and fifteen 8-byte stores, 120 B each way; per bar 1152 B of
+ *   structure and region are read by the rows launch and 1024 B by the two counts.
+ *
+ * PM_E_INVALID (both entries, before any launch): a NULL pointer where one is needed (tokens_in may be NULL iff N_in == 0,
+ *   tokens iff N == 0); G <= 0, R <= 0 or G % R != 0; N < 0 or N_in < 0; 128 G, 30 N or 32 N_in >= 2^31; an fp32 or int32
+ *   buffer not 4-byte aligned, tokens not 8-byte, tokens_in not 16-byte aligned (the uint8 buffers need no alignment); any
+ *   output or workspace overlapping any other buffer (inputs may share memory with each other). */
+#define PM_INFILL_SCRATCH(G) (6 * (int64_t)(G) + 2)
+int pm_infill_structure(const float* s_in /* [G,4,32] 0/1 */, const uint8_t* s_model /* [G,4,32] */,
+                        const uint8_t* region /* [R,4,32] */, int32_t G, int32_t R, float* s_f32 /* [G,4,32] or NULL */,
+                        uint8_t* s_u8 /* [G,4,32] or NULL */, int32_t* bar_forced /* [G] */, pm_stream_t stream);
+int pm_infill_tokens(const float* s_in /* [G,4,32] 0/1 */, const float* s_out /* [G,4,32] 0/1 */,
+                     const uint8_t* region /* [R,4,32] */, int32_t G, int32_t R, const int32_t* tokens_in /* [N_in,16,2] */,
+                     int64_t N_in, int32_t* tokens /* [N,15,2] in/out */, int64_t N,
+                     const int32_t* bar_forced /* [G] or NULL */, int32_t* scratch /* [PM_INFILL_SCRATCH(G)] */,
+                     int32_t* status /* [5] */, pm_stream_t stream);
+
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):
  *   A[n, r*d:(r+1)*d] = mean_{e: dst=n, type=r} keep_e * relu(x[src_e] * T[dist_e]) / (1-p)

@@ -4,7 +4,8 @@ without the reference's host synchronisations (`nonzero`, per-sample Python grap
 Converting the pianoroll to MIDI (muspy) is outside the hot path and stays with the caller; `generate_notes` returns the
 pieces as ordered note events instead (`NoteBatch`, csrc/notes.hip), which is what that conversion reads out of the pianoroll.
 The other direction has no entry point in the reference: `NoteBatch.from_lists` / `to_graph` (csrc/notes_in.hip) turn notes into the
-batch the encoder consumes, `encode_notes` and `vary_notes` encode a piece and decode around it."""
+batch the encoder consumes, `encode_notes` and `vary_notes` encode a piece and decode around it, `infill_notes` regenerates the
+cells of a region (`region_mask`) and keeps the other notes (csrc/infill.hip)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -63,15 +64,24 @@ def step_mask(every: int = 1, offset: int = 0, lo: int = 0, hi: int = 31) -> np.
     return (t >= lo) & (t <= hi) & (t >= offset) & ((t - offset) % int(every) == 0)
 
 
+def _model_structure(vae, z, rules, seed):
+    """the model's own structure for z, bool [B,n_bars,4,32]: drawn on the device from the structure logits under `rules` (a
+    StructureRules) and `seed`, or, without rules, thresholded as `Decoder.forward` does it"""
+    with torch.no_grad():
+        s_logits = vae.engine.structure_only(z.contiguous().float(), vae.training)
+    s_logits = s_logits.detach().contiguous().float()
+    if rules is None:
+        return vae.decoder._binary_from_logits(s_logits)
+    return ops.sample_structure(s_logits, rules.temperature, rules.threshold, rules.min_active, rules.max_active,
+                                rules.allowed_steps, seed)
+
+
 def _decode(vae, z, s_cond, s_tensor_cond, rules=None, seed=None):
     """the decoder pass of `generate_music`: (c_logits [N,15,230] fp32, s_tensor).  With `rules` (a StructureRules) the
     structure is drawn from the structure logits on the device under `seed` and the content decoder runs on its bar graphs."""
     vae.decoder.__dict__.pop("_last_structure", None)
     if rules is not None:
-        with torch.no_grad():
-            s_logits = vae.engine.structure_only(z.contiguous().float(), vae.training)
-        s_tensor = ops.sample_structure(s_logits.detach().contiguous().float(), rules.temperature, rules.threshold,
-                                        rules.min_active, rules.max_active, rules.allowed_steps, seed)
+        s_tensor = _model_structure(vae, z, rules, seed)
         graph = vae.decoder._structure_from_binary(s_tensor)     # (no bar is empty: s_tensor stays as drawn)
         _, c_logits = vae.decoder(z, graph)
         return c_logits.detach().contiguous().float(), s_tensor
@@ -130,6 +140,16 @@ def _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, s
     Returns (tokens int32 [N,15,2], s_tensor, note_count int32 [N] or None without chord rules, c_logits): c_logits is None
     in every sampled mode; in the unsampled one it holds the content logits and `tokens` their arg-max (None when
     `argmax_tokens` is off: the caller lays the logits out and wants no tokens)."""
+    sampled = _check_draw(s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules, structure_rules, return_note_counts)
+    if structure_rules is not None and seed is None:             # one seed for both levels, drawn before the structure
+        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
+    tokens, note_count, c_logits = _draw(c_logits, s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules, argmax_tokens)
+    return tokens, s_tensor, note_count, c_logits
+
+
+def _check_draw(s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules, structure_rules, return_note_counts=False):
+    """The argument checks of `_decode_and_draw`, before the model is touched.  Returns whether the content is sampled."""
     if structure_rules is not None:
         if not isinstance(structure_rules, StructureRules):
             raise ValueError(f"structure_rules must be a StructureRules, got {structure_rules!r}")
@@ -142,26 +162,26 @@ def _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, s
             raise ValueError(f"chord_rules must be a ChordRules, got {chord_rules!r}")
         ops.check_chord_args(temperature, top_k, top_p, seed, chord_rules.min_notes, chord_rules.max_notes,
                              chord_rules.allowed_pitches)
-        sampled = True
-    else:
-        if return_note_counts:
-            raise ValueError("return_note_counts needs chord_rules")
-        ops.check_sampling_args(temperature, top_k, top_p, seed)
-        sampled = temperature is not None or top_k is not None or top_p is not None
-    if structure_rules is not None and seed is None:             # one seed for both levels, drawn before the structure
-        seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
-    c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
+        return True
+    if return_note_counts:
+        raise ValueError("return_note_counts needs chord_rules")
+    ops.check_sampling_args(temperature, top_k, top_p, seed)
+    return temperature is not None or top_k is not None or top_p is not None
+
+
+def _draw(c_logits, s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules, argmax_tokens=True):
+    """The draw of `_decode_and_draw` on the content logits of the nodes of `s_tensor`, in the mode `_check_draw` found:
+    (tokens, note_count, c_logits) as `_decode_and_draw` returns them.  A `seed` of None is drawn here."""
     if not sampled:
-        return (ops.sample_tokens(c_logits, temperature=0.0) if argmax_tokens else None), s_tensor, None, c_logits
+        return (ops.sample_tokens(c_logits, temperature=0.0) if argmax_tokens else None), None, c_logits
     if seed is None:
         seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
     if chord_rules is None:
-        tokens = ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed)
-        return tokens, s_tensor, None, None
+        return ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed), None, None
     track = ops.node_tracks(s_tensor, c_logits.shape[0], check=False)
     tokens, note_count = ops.sample_chords(c_logits, track, 1.0 if temperature is None else temperature, top_k, top_p, seed,
                                            chord_rules.min_notes, chord_rules.max_notes, chord_rules.allowed_pitches)
-    return tokens, s_tensor, note_count, None
+    return tokens, note_count, None
 
 
 TRACKS = ("Drums", "Bass", "Guitar", "Strings")                 # constants.py:5
@@ -258,12 +278,16 @@ def generate_notes(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     return (batch, s_tensor, tokens) if return_tokens else (batch, s_tensor)
 
 
-def _encode(vae, batch):
-    """(mu, log_var, graph) of a NoteBatch: the encoder in eval mode without gradients, the mode it found restored."""
+def _check_batch(vae, batch):
     if not isinstance(batch, NoteBatch):
         raise ValueError(f"batch must be a NoteBatch, got {type(batch).__name__}")
     if batch.n_bars != vae.cfg["n_bars"]:
         raise ValueError(f"batch holds pieces of n_bars = {batch.n_bars}, the model takes n_bars = {vae.cfg['n_bars']}")
+
+
+def _encode(vae, batch):
+    """(mu, log_var, graph) of a NoteBatch: the encoder in eval mode without gradients, the mode it found restored."""
+    _check_batch(vae, batch)
     graph = batch.to_graph()
     was_training = vae.training
     vae.eval()
@@ -309,3 +333,109 @@ def vary_notes(vae, batch, strength=1.0, keep_structure=False, seed=None, return
         s_cond, s_tensor_cond = graph, graph.s_tensor.view(-1, batch.n_bars, 4, 32).bool()
     out = generate_notes(vae, z, s_cond, s_tensor_cond, seed=seed, **generate_notes_kwargs)
     return out + (z,) if return_z else out
+
+
+def region_mask(n_bars: int, tracks=None, bars=None, steps=None) -> np.ndarray:
+    """bool [n_bars,4,32]: the region of an infill (`infill_notes`), True = the model rewrites the cell.  `tracks` holds names
+    from TRACKS or indices 0..3, `bars` indices 0..n_bars-1, `steps` is a bool [32] array as `step_mask` returns; None means
+    all, and the three are ANDed together.  Bad values raise ValueError naming the argument."""
+    if not (ops._integer(n_bars) and n_bars >= 1):
+        raise ValueError(f"n_bars must be an int >= 1, got {n_bars!r}")
+    on_track, on_bar, on_step = np.ones(4, bool), np.ones(int(n_bars), bool), np.ones(32, bool)
+    if tracks is not None:
+        if isinstance(tracks, (str, bytes)) or not isinstance(tracks, (list, tuple, set, frozenset, np.ndarray)):
+            raise ValueError(f"tracks must be a list of names from {TRACKS} or indices 0..3, got {tracks!r}")
+        on_track[:] = False
+        for k in tracks:
+            if isinstance(k, str) and k in TRACKS:
+                k = TRACKS.index(k)
+            if not (ops._integer(k) and 0 <= k < 4):
+                raise ValueError(f"tracks must hold names from {TRACKS} or indices 0..3, got {k!r}")
+            on_track[int(k)] = True
+    if bars is not None:
+        if not isinstance(bars, (list, tuple, set, frozenset, range, np.ndarray)):
+            raise ValueError(f"bars must be a list of indices 0..{n_bars - 1}, got {bars!r}")
+        on_bar[:] = False
+        for b in bars:
+            if not (ops._integer(b) and 0 <= b < n_bars):
+                raise ValueError(f"bars must hold indices 0..{n_bars - 1}, got {b!r}")
+            on_bar[int(b)] = True
+    if steps is not None:
+        a = steps.detach().cpu().numpy() if isinstance(steps, torch.Tensor) else np.asarray(steps)
+        if a.dtype != np.bool_ or a.shape != (32,):
+            raise ValueError(f"steps must be a bool array of shape [32], got {a.dtype} {tuple(a.shape)}")
+        on_step = a
+    return np.ascontiguousarray(on_bar[:, None, None] & on_track[None, :, None] & on_step[None, None, :])
+
+
+def infill_notes(vae, batch, region, strength=0.0, keep_structure=False, seed=None, return_z=False, return_info=False,
+                 **generate_notes_kwargs):
+    """Regenerate part of pieces held as notes and keep the rest: `region` (bool [n_bars,4,32] for all pieces or
+    [B,n_bars,4,32], see `region_mask`; True = the model rewrites the cell) says which (bar, track, step) cells are written
+    anew, every other cell comes back with the notes the encoder saw.  `batch` (a `NoteBatch`, checked as by `encode_notes`)
+    is encoded once and the fill is decoded at z = mu + strength * exp(log_var / 2) * eps, `eps` and `seed` handled as in
+    `vary_notes`; the default `strength` 0 decodes at the piece's own latent.
+
+    Structure: the model's structure for z is thresholded, or drawn under `structure_rules=` (the draw `generate_notes`
+    makes), and merged with the input's on the device (`ops.infill_structure`): a cell is on iff (region ? model : input), a
+    bar that comes out empty gets cell [0,0].  The per-track bounds of `structure_rules` hold for the model's structure: inside
+    a region that covers only part of a track just `max_active` is guaranteed, `min_active` cells may fall outside it.  With
+    `keep_structure=True` the merged structure is the input's own and only the notes inside the region change; it excludes
+    `structure_rules` with the error `vary_notes` raises.
+
+    Decoding: the content decoder runs on the merged structure's bar graphs and the tokens of every node are drawn in the
+    mode the keywords select, with `generate_notes`' arguments and checks (unsampled = arg-max, `temperature` / `top_k` /
+    `top_p`, `chord_rules`); `ops.infill_tokens` puts the kept cells' tokens back and `ops.notes_from_tokens` reads the piece.
+    The decoder is not autoregressive: given z and the bar graph the regenerated cells do not depend on the kept notes.
+    `s_cond` / `s_tensor_cond` are rejected as in `vary_notes`.
+
+    Outside the region the result holds what the encoder saw, not the raw input: pitches clamped to 0..127, durations to
+    1..96, the first 14 notes of a cell, and durations cut at the piece's end by the reader.
+
+    Returns (NoteBatch, s_tensor bool [B,n_bars,4,32]) and then, as asked, `return_tokens` the int32 [N,15,2] tokens,
+    `return_z` the latent, `return_info` the int32 [5] status of `ops.infill_tokens`, left on the device (merged cells, input
+    cells, kept nodes, kept nodes without a source, bars forced).  No host read beyond those of `to_graph`, the graph build
+    of the merged structure and the `notes_from_tokens` check."""
+    if not (ops._real(strength) and np.isfinite(strength) and strength >= 0):
+        raise ValueError(f"strength must be a finite number >= 0, got {strength!r}")
+    ops.check_sampling_args(seed=seed)
+    kw = dict(generate_notes_kwargs)
+    for k in ("s_cond", "s_tensor_cond"):
+        if k in kw:
+            raise ValueError(f"{k} is not an argument of infill_notes: keep_structure=True keeps the input's structure")
+    temperature, top_k, top_p = kw.pop("temperature", None), kw.pop("top_k", None), kw.pop("top_p", None)
+    chord_rules, structure_rules = kw.pop("chord_rules", None), kw.pop("structure_rules", None)
+    return_tokens = kw.pop("return_tokens", False)
+    if kw:
+        raise TypeError(f"infill_notes got an unexpected keyword argument {sorted(kw)[0]!r}")
+    if keep_structure and structure_rules is not None:
+        raise ValueError("structure_rules draws the structure itself: it needs s_cond and s_tensor_cond both None")
+    _check_batch(vae, batch)
+    B, n_bars = (batch.track_ptr.shape[0] - 1) // 4, batch.n_bars
+    region = ops.check_region(region, B, n_bars)
+    sampled = _check_draw(None, None, temperature, top_k, top_p, seed, chord_rules, structure_rules)
+    mu, log_var, graph = _encode(vae, batch)
+    z = mu
+    if strength != 0:
+        gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+        eps = torch.randn(mu.shape, generator=gen, dtype=torch.float32).to(mu.device)
+        z = mu + float(strength) * torch.exp(0.5 * log_var) * eps
+    s_in = graph.s_tensor
+    region = torch.from_numpy(region.reshape(-1, 4, 32)).to(s_in.device)
+    if keep_structure:
+        merged, bar_forced = graph, None
+    else:
+        if structure_rules is not None and seed is None:         # one seed for both levels, drawn before the structure
+            seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
+        s_bool, bar_forced = ops.infill_structure(s_in, _model_structure(vae, z, structure_rules, seed), region)
+        merged = vae.decoder._structure_from_binary(s_bool)      # (no bar is empty: the structure stays as merged)
+    s_tensor = merged.s_tensor.view(B, n_bars, 4, 32).bool()
+    _, c_logits = vae.decoder(z, merged)
+    tokens, _, _ = _draw(c_logits.detach().contiguous().float(), s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules)
+    info = ops.infill_tokens(s_in, merged.s_tensor, region, graph.tokens, tokens, bar_forced)
+    notes, track_ptr, totals = ops.notes_from_tokens(tokens, s_tensor)
+    out = (NoteBatch(notes, track_ptr, totals, n_bars, batch.resolution), s_tensor)
+    for wanted, value in ((return_tokens, tokens), (return_z, z), (return_info, info)):
+        if wanted:
+            out += (value,)
+    return out

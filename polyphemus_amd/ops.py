@@ -393,6 +393,107 @@ def tokens_from_notes(notes: torch.Tensor, track_ptr: torch.Tensor, n_bars: int,
                            num_nodes=N)
 
 
+def check_region(region, B: int, n_bars: int) -> np.ndarray:
+    """The region of an infill ("Infill" in include/polyphemus_hip.h) as a contiguous bool numpy array: `region` is a bool
+    array-like or bool tensor [n_bars,4,32] (one mask for all pieces) or [B,n_bars,4,32] (one per piece), True = the model
+    rewrites the cell.  Anything else raises ValueError, before a device is touched."""
+    if isinstance(region, torch.Tensor):
+        if region.dtype != torch.bool:
+            raise ValueError(f"region must be a bool array [n_bars,4,32] or [B,n_bars,4,32], got a {region.dtype} tensor")
+        a = region.detach().cpu().numpy()
+    else:
+        try:
+            a = np.asarray(region)
+        except Exception:
+            a = np.empty(0, np.object_)
+    if a.dtype != np.bool_ or tuple(a.shape) not in ((n_bars, 4, 32), (B, n_bars, 4, 32)):
+        raise ValueError(f"region must be a bool array [n_bars,4,32] = [{n_bars},4,32] or [B,n_bars,4,32] = "
+                         f"[{B},{n_bars},4,32], got {a.dtype} {tuple(a.shape)}")
+    return np.ascontiguousarray(a)
+
+
+def _infill_args(named, region):
+    """The checks `infill_structure` and `infill_tokens` share: every (tensor, name, dtype, trailing shape) of `named` is a
+    tensor of that dtype and shape (ValueError), on the device (HipExtensionError), all on one device (ValueError); the
+    structures agree in their bar count G; `region` is bool / uint8 [R,4,32] or [B,n_bars,4,32] with R = G or a divisor of
+    G, a tensor on that device or an array-like that is uploaded.  Returns (contiguous tensors, region uint8 [R,4,32], G, R)."""
+    for t, name, dtype, tail in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != dtype or t.dim() < len(tail) + 1 or tuple(t.shape[-len(tail):]) != tail:
+            raise ValueError(f"{name} must be {dtype} [...,{','.join(map(str, tail))}], got {t.dtype} {tuple(t.shape)}")
+    if not isinstance(region, torch.Tensor):
+        region = np.asarray(region)
+        if region.dtype != np.bool_:
+            raise ValueError(f"region must be a bool array [R,4,32], got {region.dtype} {tuple(region.shape)}")
+        region = torch.from_numpy(np.ascontiguousarray(region))
+        if named[0][0].is_cuda:
+            region = region.to(named[0][0].device)
+    if region.dtype not in (torch.bool, U8) or region.dim() < 3 or tuple(region.shape[-2:]) != (4, 32):
+        raise ValueError(f"region must be bool [R,4,32] or [B,n_bars,4,32], got {region.dtype} {tuple(region.shape)}")
+    structures = [t for t, _, _, tail in named if tail == (4, 32)]
+    G, R = structures[0].numel() // 128, region.numel() // 128
+    for t, name, _, tail in named:
+        if tail == (4, 32) and t.numel() != 128 * G:
+            raise ValueError(f"{name} holds {t.numel() // 128} bars, {named[0][1]} holds {G}")
+    if G == 0 or R == 0 or G % R != 0:
+        raise ValueError(f"region holds {R} bars: it must hold the structures' {G} bars or a divisor of them, and at least one")
+    for t, name in [(t, name) for t, name, _, _ in named] + [(region, "region")]:
+        if not t.is_cuda:
+            raise HipExtensionError(f"{name} lives on {t.device}: the HIP path needs device tensors (no CPU fallback)")
+    for t, name in [(t, name) for t, name, _, _ in named[1:]] + [(region, "region")]:
+        if t.device != named[0][0].device:
+            raise ValueError(f"{name} lives on {t.device}, {named[0][1]} on {named[0][0].device}")
+    region = region.contiguous()
+    return [t.contiguous() for t, _, _, _ in named], (region.view(U8) if region.dtype == torch.bool else region), G, R
+
+
+def infill_structure(s_in: torch.Tensor, s_model: torch.Tensor, region):
+    """`pm_infill_structure` ("Infill" in include/polyphemus_hip.h): the structure of an infill.  `s_in` fp32 [G,4,32] 0/1 is
+    the input's structure (`tokens_from_notes`), `s_model` bool or uint8 [...,4,32] with G bars the model's
+    (`binary_from_logits`, `sample_structure`), `region` bool [R,4,32] or [B,n_bars,4,32] (R = G or a divisor of G: bar g reads
+    row g % R).  A cell is on iff (region ? s_model : s_in); a bar that comes out empty gets cell [0,0].  Returns (bool
+    [G,4,32], bar_forced int32 [G]: 1 where [0,0] was switched on).  One launch, nothing is read back."""
+    if isinstance(s_model, torch.Tensor) and s_model.dtype == torch.bool:
+        s_model = s_model.view(U8) if s_model.is_contiguous() else s_model.contiguous().view(U8)
+    (s_in, s_model), region, G, R = _infill_args([(s_in, "s_in", F32, (4, 32)), (s_model, "s_model", U8, (4, 32))], region)
+    out = torch.empty(G, 4, 32, dtype=U8, device=s_in.device)
+    bar_forced = torch.empty(G, dtype=I32, device=s_in.device)
+    call("pm_infill_structure", ptr(s_in), ptr(s_model), ptr(region), G, R, None, ptr(out), ptr(bar_forced), stream())
+    return out.view(torch.bool), bar_forced
+
+
+def infill_tokens(s_in: torch.Tensor, s_out: torch.Tensor, region, tokens_in: torch.Tensor, tokens: torch.Tensor,
+                  bar_forced: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`pm_infill_tokens` ("Infill" in include/polyphemus_hip.h): the kept cells' tokens put back, IN PLACE.  `s_in` fp32
+    [G,4,32] and `tokens_in` int32 [N_in,16,2] are the input (`tokens_from_notes`), `s_out` fp32 [G,4,32] the merged structure
+    after the decoder's graph build, `tokens` int32 [N,15,2] (contiguous) the drawn tokens of its nodes, `region` as for
+    `infill_structure`.  A node outside the region takes the 15 slots behind the SOS of the input's node of its cell, or the
+    chord of a cell without a note where the input has none; nodes inside the region stay as drawn.  Returns status int32 [5]
+    on the device: active cells of s_out, of s_in, kept nodes, kept nodes without a source, bars forced (the sum of
+    `bar_forced`, int32 [G] from `infill_structure`; None counts none).  Nothing is read back: a caller that has not
+    checked N against s_out's cells compares status[0] with it."""
+    named = [(s_in, "s_in", F32, (4, 32)), (s_out, "s_out", F32, (4, 32)), (tokens_in, "tokens_in", I32, (C.MAX_SIMU_TOKENS, 2)),
+             (tokens, "tokens", I32, (C.MAX_SIMU_TOKENS - 1, 2))]
+    for t, name, _, tail in named[2:]:
+        if isinstance(t, torch.Tensor) and t.dim() != 3:
+            raise ValueError(f"{name} must be int32 [N,{tail[0]},2], got {t.dtype} {tuple(t.shape)}")
+    if bar_forced is not None and not (isinstance(bar_forced, torch.Tensor) and bar_forced.dtype == I32 and bar_forced.dim() == 1):
+        raise ValueError("bar_forced must be an int32 tensor [G]")
+    if isinstance(tokens, torch.Tensor) and not tokens.is_contiguous():
+        raise ValueError("tokens must be contiguous: it is written in place")
+    (s_in, s_out, tokens_in, tokens), region, G, R = _infill_args(named, region)
+    if bar_forced is not None:
+        if bar_forced.shape[0] != G or bar_forced.device != s_in.device:
+            raise ValueError(f"bar_forced must be int32 [G = {G}] on {s_in.device}, got [{bar_forced.shape[0]}] on {bar_forced.device}")
+        bar_forced = bar_forced.contiguous()
+    N_in, N, dev = tokens_in.shape[0], tokens.shape[0], s_in.device
+    scratch, status = torch.empty(6 * G + 2 + 5, dtype=I32, device=dev).split([6 * G + 2, 5])   # PM_INFILL_SCRATCH(G)
+    call("pm_infill_tokens", ptr(s_in), ptr(s_out), ptr(region), G, R, ptr(tokens_in) if N_in else None, N_in,
+         ptr(tokens) if N else None, N, ptr(bar_forced), ptr(scratch), ptr(status), stream())
+    return status
+
+
 def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
                      c_logits=None, node_track=None):
     """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
