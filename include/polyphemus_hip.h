@@ -546,6 +546,12 @@ int pm_gcl_input_grad_bn(const PmBnBwd* norm, uint16_t* dh_planes /* 3 planes [N
  * products hi*hi + hi*lo + lo*hi with fp32 accumulation: element error <= 2^-22 relative plus the dropped lo*lo term of the
  * same size — below the rounding an fp32 dot product of the same length accumulates — at half the matrix-core work, two
  * thirds of the operand bytes (csrc/common.h pm_split2h_pair; parity of the step against the fp64 oracle: tests/).
+ * CONDITION: the 2^-22 is relative only for elements with |v s| >= 2^-2, i.e. within 15 binades of the bound the scale is
+ * taken from; below, the element error is 2^-25 / s absolute.  One scale serves the whole tensor: a tensor whose bulk lies
+ * more than 15 binades below its bound (an outlier channel, a BatchNorm column of tiny variance, a large gradient row — on
+ * top of the factor 16 of the dh bound) loses a factor of two of product accuracy per further binade (relative L2 against
+ * fp64: 1.2e-6 at 19 binades, 1.9e-5 at 23; tests/test_pair_format_gpu.py holds the products to exactly this model).
+ * pm_h2_clamp_events does NOT see it: it counts bounds that were too small, never bounds that were too large.
  * Planes keep the layout and strides of the three-plane format; plane 2 is unused.  d = 512 runs the same format through the
  * ring pipeline of wide.hip (pm_gcl_forward_fused_h2, pm_bn_bwd_fused_h2 + pm_gcl_input_grad_fused_h2, pm_gcl_weight_grad_fused_h2).
  *   absmax_in : device words [PM_ABSMAX_SLOTS] holding float bits whose maximum is max |x| of the kernel's fp32 input (pm_absmax, or a producer's
@@ -818,6 +824,11 @@ int pm_bn_bwd_fused(const float* x, const float* dy, int32_t O, int32_t C, const
 /* The column sums of pm_bn_bwd_fused alone: acc3 [PM_BN_REPL][3][C] (caller-zeroed) += sums of du', du' * xhat, xhat. */
 int pm_bn_bwd_sums(const float* x, const float* dy, int32_t O, int32_t C, const float* mean, const float* var, float eps,
                    const float* gamma, const float* beta, int relu, double* acc3, pm_stream_t stream);
+/* ... which also leaves max |dy| — of the gradient as READ, not of the ReLU-masked du', hence a bound for it — in
+ * absmax_dy[PM_ABSMAX_SLOTS] (float bits, atomic max): PmH2.absmax_in of the layer's input gradient */
+int pm_bn_bwd_sums_absmax(const float* x, const float* dy, int32_t O, int32_t C, const float* mean, const float* var, float eps,
+                          const float* gamma, const float* beta, int relu, double* acc3, uint32_t* absmax_dy,
+                          pm_stream_t stream);
 /* Eval-mode BatchNorm folded into the linear map in front of it (model.py:203 under `vae.eval()`,
  * generate.py:112): with s = gamma / sqrt(running_var + eps), t = beta - running_mean * s,
  *   W_out[k, n] = W[k, n] * s[n]      (W [rows, cols] row-major, the GCL operand [weight; root] [7d, d])
@@ -895,6 +906,9 @@ int pm_chord_tables_fwd(const float* tables /* [4][131][d/2] */, const float* ch
                         pm_stream_t stream);
 int pm_chord_sum_fwd(const float* PT, const float* cvec, const int32_t* tokens /* [N,16,2] */, const uint8_t* is_drum, int32_t N,
                      int32_t d, int32_t n_slots, float* x0 /* [N,d] */, pm_stream_t stream);
+/* ... which also leaves max x0 (x0 >= 0) in absmax_out[PM_ABSMAX_SLOTS] (float bits, atomic max): PmH2.absmax_in of the first GCL layer */
+int pm_chord_sum_fwd_absmax(const float* PT, const float* cvec, const int32_t* tokens, const uint8_t* is_drum, int32_t N,
+                            int32_t d, int32_t n_slots, float* x0, uint32_t* absmax_out, pm_stream_t stream);
 int pm_chord_sum_bwd(const float* dy /* [N,d] */, const int32_t* tokens, const int32_t* plan, int32_t N, int32_t E, int32_t G,
                      int32_t d /* multiple of 32, <= 512 */, int32_t n_slots, float* Gt, pm_stream_t stream);
 int pm_chord_tables_bwd_w(const float* Gt, const float* tables, int32_t d, int32_t n_slots, float* d_chord_w /* += */,

@@ -42,10 +42,12 @@ _SIGS = {
     "pm_chord_pad_vec": "pppiips",
     "pm_chord_tables_fwd": "ppiippps",
     "pm_chord_sum_fwd": "ppppiiips",
+    "pm_chord_sum_fwd_absmax": "ppppiiipps",
     "pm_chord_sum_bwd": "pppiiiiips",
     "pm_chord_tables_bwd_w": "ppiipps",
     "pm_chord_tables_bwd_x": "ppiips",
     "pm_bn_bwd_sums": "ppiippfppips",
+    "pm_bn_bwd_sums_absmax": "ppiippfppipps",
     "pm_gcl_weight_grad_fused": "plplpiiiiips",
     "pm_gcl_forward_from_planes": "plpiiiippipps",
     "pm_rows_times_weight": "piiipiiippis",

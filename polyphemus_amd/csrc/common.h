@@ -178,7 +178,13 @@ __device__ static inline void pm_split3_pair(float a, float b, unsigned& h1, uns
 // three MFMA products hi*hi + hi*lo + lo*hi with fp32 accumulation — Ootomo & Yokota's error-corrected half-precision
 // product).  Representation error per element <= 2^-22 |v s| while lo is a normal fp16 (|v s| >= 2^-2), 2^-25 absolute
 // below that; the dropped lo*lo term is 2^-22 relative: the accuracy of an fp32 dot product (whose sequential sum of K
-// terms rounds by ~sqrt(K) 2^-24) at half the matrix-core work of the exact three-term bf16 split above.  fp16 has five
+// terms rounds by ~sqrt(K) 2^-24) at half the matrix-core work of the exact three-term bf16 split above — WHILE the operand's
+// bulk lies within 15 binades of the bound its scale is taken from (|v s| >= 2^-2).  Below that the element error is absolute
+// and the product's relative error doubles per binade: one scale serves a whole tensor, so an outlier channel 2^t above
+// the rest (or a loose bound: the dh bound carries a factor 16 and the largest gamma * rstd) moves every other channel down
+// the window.  Measured, relative L2 against fp64 (tests/test_pair_format_gpu.py, profiles/LOG.md): the three GCL products
+// stay within twice the exact-split route up to t = 8 (dh bulk 15 binades below its bound); at 19 binades 1.2e-6, at 23
+// binades 1.9e-5 — what this representation bound predicts, not more (fp16 subnormals are kept, not flushed).  fp16 has five
 // exponent bits, so every operand carries a power-of-two scale s (exact to apply and to undo) chosen from the tensor's
 // |max| so that max |v s| lands near 2^13: pm_pow2_scale below.
 typedef _Float16 pm_f16x2 __attribute__((ext_vector_type(2)));
