@@ -684,12 +684,22 @@ enum { PM_GEMM_RELU = 1, PM_GEMM_ACCUM = 2,
                              products skips its own clear */,
        PM_GEMM_PARTITION = 4 /* grouped + row lists + device counts: the groups' lists partition at most M (K when
                                 transA) rows IN TOTAL; the launch then only enumerates live row panels */ };
-/* tile configuration pm_gemm_f32 picks for a shape (host only).  fp32 MFMA: 0 = 64x64x16, 1 = 128x128x16,
- * 2 = 64x64x32, 3 = 128x128x32.  Split mode (fp32 operands split exactly into three bf16 terms, six partial products
- * on v_mfma_f32_32x32x16_bf16, fp32 accumulation; error below an fp32 FMA chain): 4 = 128x128x16, 5 = 128x64x16,
- * 6 = 64x64x32, 7 = 128x128x32; needs 16-byte aligned operands, otherwise the fp32 rule applies. */
+/* Tile configurations (host only).  Live ids — fp32 MFMA: 0 = 64x64x16, 2 = 64x64x32 (NN, NT, TN).  Split mode "x6" (fp32
+ * operands split exactly into three bf16 terms, six partial products on v_mfma_f32_32x32x16_bf16, fp32 accumulation;
+ * error below an fp32 FMA chain; needs 16-byte aligned operands): 4 = 128x128x16, 7 = 128x128x32 (NN, NT),
+ * 5 = 128x64x16 (TN).  Pre-split operands (PmGemmDesc.operand_planes): 8 = 64x64x32, 9 = 64x128 with B direct (NN, NT).
+ * Ids 1, 3, 6 and 10 are retired: no kernel is built for them and nothing launches them; the numbering is kept because
+ * the profiler classes are PM_PROF_GEMM0 + 3 * id + layout.
+ * pm_gemm_config: the configuration a PLAIN product of this shape runs on — one group, no row map, fp32 operands that
+ *   are 16-byte aligned with contiguous leading dimensions.  It asks the same function as the launch, so for such a
+ *   call it is what pm_gemm_f32 launches, a pinned configuration included.  A misaligned operand, a grouped or
+ *   row-mapped call can land on an fp32 tile where this reports an x6 one.
+ * pm_gemm_force_config (A/B timing): -1 = automatic (default); 0, 2, 4, 5, 7 pin that configuration; any other value
+ *   returns PM_E_INVALID and leaves the current choice as it is.  A pinned fp32 id applies to every fp32-operand call.
+ *   A pinned x6 id applies to the calls whose operands allow x6 (alignment) and whose layout it has a kernel for
+ *   (4, 7: NN / NT; 5: TN); every other call follows the shape rule.  Calls with pre-split operands ignore the pin. */
 int pm_gemm_config(int32_t transA, int32_t M, int32_t N, int32_t K);
-int pm_gemm_force_config(int32_t cfg); /* -1 = automatic (default); 0..7 pins a configuration (A/B timing) */
+int pm_gemm_force_config(int32_t cfg);
 int pm_gemm_f32(int transA, int transB, int32_t M, int32_t N, int32_t K, const float* A, int32_t lda,
                 const float* B, int32_t ldb, float* C, int32_t ldc, const float* bias, int flags,
                 int split_k, const int32_t* rowmap, int32_t rows_per_entry, const int32_t* dyn_entries,

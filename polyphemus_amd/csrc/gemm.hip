@@ -4,12 +4,16 @@
 // (model.py:112,116), which become ONE grouped launch on the compact aggregate [track block | onset | next | x]
 // (K = 4d, row lists per track relation, stacked weights) — or one plain call on [h_0|...|h_5|x] (K = 7d).
 // Plain bf16 MFMA cannot hold the 1e-4 parity bar through 16 BatchNorm'd layers; three arithmetic modes keep fp32
-// accuracy (one kernel template, 4 waves (2x2) of 32x32 MFMA tiles per workgroup unless noted):
-//   MODE 0  fp32 MFMA   v_mfma_f32_32x32x2_f32 (157 TFLOP/s peak)      C0 64x64x16, C1 128x128x16, C2 64x64x32, C3 128x128x32
+// accuracy (one kernel template, 4 waves of 32x32 MFMA tiles per workgroup; configurations Cid, see GEMM_CFGS below —
+// the one table of what is built, choose_config the one place that picks from it):
+//   MODE 0  fp32 MFMA   v_mfma_f32_32x32x2_f32 (157 TFLOP/s peak)      C0 64x64x16, C2 64x64x32
 //   MODE 1  split "x6"  v_mfma_f32_32x32x16_bf16, fp32 operands split in the kernel by 4 extra producer waves
-//                                                                      C4 128x128x16, C5 128x64x16, C6 64x64x32, C7 128x128x32
+//                                                                      C4 128x128x16, C7 128x128x32 (NN, NT), C5 128x64x16 (TN)
 //   MODE 2  planes      v_mfma_f32_32x32x16_bf16, operands PRE-SPLIT by the kernels that produced them
-//                                                                      C8 64x64x32 (C9 128x64x32, C10 128x128x32 measured slower)
+//                                                                      C8 64x64x32
+//   MODE 3  planes, B direct: B (a weight matrix) read as fragment-major planes straight into registers
+//                                                                      C9 64x128x64 (NN), 64x128x32 (NT)
+// (tried and retired, ids not reused: C1 / C3 128x128 fp32 tiles, C6 x6 64x64x32, C10 planes 128x128x32)
 // Split arithmetic: every fp32 value is EXACTLY the sum of three bf16 terms (x = x1 + x2 + x3, 8 significand bits each,
 // same exponent range) and the six partial products of weight >= 2^-16
 //   x1y1 + (x1y2 + x2y1) + (x1y3 + x2y2 + x3y1)
@@ -27,18 +31,10 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef PM_BD_DUAL
-#define PM_BD_DUAL 0
-#endif
-#ifndef PM_TN_DUAL
-#define PM_TN_DUAL 1
-#endif
-#ifndef PM_PL_WAVES
-#define PM_PL_WAVES 5          // waves per SIMD the 64x64 planes kernel is register-budgeted for
-#endif
-#ifndef PM_BD_WAVES
-#define PM_BD_WAVES 5
-#endif
+// waves per SIMD the planes kernels are register-budgeted for (64x64 tile: capped at 100 VGPRs so that FIVE workgroups
+// fit a CU — the 1036 tiles of a GCL contraction then run as one resident wave of workgroups instead of 1024 + a
+// 12-tile tail); B direct with k-tiles of 64 holds twice the B fragments and is budgeted for 4
+constexpr int PM_PL_WAVES = 5, PM_BD_WAVES = 5;
 struct GemmArgs {
   const float* A; const float* B; float* C; const float* bias;
   const int32_t* rowmap; const int32_t* dyn_entries;
@@ -72,7 +68,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-#define PM_OOB ((int)0x80000000)     // byte offset >= num_records: the buffer load returns 0, no branch, no fault
+constexpr int PM_OOB = (int)0x80000000;   // byte offset >= num_records: the buffer load returns 0, no branch, no fault
 
 // Stage one operand tile (R rows x BK k) through registers into its k-major LDS image S[k][r].
 //  KC = true : stored k-contiguous, element (r,k) at P[row(r)*ld + k]   (A when !transA, B when transB)
@@ -330,12 +326,21 @@ struct PlaneStage {
 };
 
 // MODE 0: fp32 MFMA.  MODE 1 ("x6"): fp32 operands split in the kernel.  MODE 2 ("planes"): operands pre-split.
-// (planes mode, 64x64 tile: capped at 100 VGPRs so that FIVE workgroups fit a CU — the 1036 tiles of a GCL
-//  contraction then run as one resident wave of workgroups instead of 1024 + a 12-tile tail)
+// MODE 3: planes with B taken straight from fragment-major planes.
+// The kernel is ONE function in three parts — tile lookup, main loop of the mode, epilogue — and stays one on purpose:
+// with the parts as force-inlined functions every one of the 34 kernels came out different (kernel arguments reached
+// through a reference lose their global address space: flat instead of global atomics, 1-15 % more code), and the
+// generated code is this file's performance contract (profiles/LOG.md, "One configuration table").
+// The six partial products of the split arithmetic as (plane of A, plane of B), smallest terms first:
+// (3,1) (2,2) (1,3) | (2,1) (1,2) | (1,1)
+__device__ constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
+// occupancy bounds (min, max waves per SIMD) of a mode: the planes kernels are held to their register budget
+constexpr int gemm_waves_per_eu(int mode, int bk, int otherwise) {
+  return mode == 2 ? PM_PL_WAVES : (mode == 3 ? (bk > 32 ? 4 : PM_BD_WAVES) : otherwise);
+}
 template <int BM, int BN, int BK, int WVM, int WVN, bool TA, bool TB, bool VA, bool VB, int MODE>
 __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
-    __attribute__((amdgpu_waves_per_eu((MODE == 2 && BM * BN <= 64 * 64) ? PM_PL_WAVES : (MODE == 3 ? (BK > 32 ? 4 : PM_BD_WAVES) : 1),
-                                       (MODE == 2 && BM * BN <= 64 * 64) ? PM_PL_WAVES : (MODE == 3 ? (BK > 32 ? 4 : PM_BD_WAVES) : 8))))
+    __attribute__((amdgpu_waves_per_eu(gemm_waves_per_eu(MODE, BK, 1), gemm_waves_per_eu(MODE, BK, 8))))
     k_gemm(GemmArgs g) {
   constexpr bool X6 = MODE == 1, PL = MODE >= 2, BD = MODE == 3;
   static_assert(MODE == 0 || (VA && VB && BK % 16 == 0), "split modes stage with 16-byte loads");
@@ -353,8 +358,9 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
   char* const Ax0 = reinterpret_cast<char*>(smem);      // split mode: two A images (3 planes each), then two B images
   char* const Bx0 = Ax0 + 2 * StA::XBYTES;
 
-  // deterministic mode: a workgroup that leaves early hands the turns of its MFMA waves on
-#define GEMM_SKIP do { pm_turn_skip_block(g.gate, WVM * WVN); return; } while (0)
+  // ---------------- 1. tile lookup: group, K slice, tile origin, live extents, K range of this workgroup
+  // (a workgroup that leaves early returns through pm_turn_skip_block: in deterministic mode it hands the turns of its
+  //  MFMA waves on)
   int grp = blockIdx.y, t = blockIdx.x, zs = blockIdx.z, nwg;
   if (TA) {
     // weight gradients: XCD-aware order over the WHOLE grid (tiles x groups x K-slices).  Workgroup L runs on XCD
@@ -372,7 +378,7 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
     int tot = 0;
     for (int q = 0; q < g.ngroups; ++q) tot += (g.dyn_entries[q * g.dyn_boff] * g.rpe + BM - 1) / BM;
     nwg = tot * g.ntn;
-    if (t >= nwg) GEMM_SKIP;
+    if (t >= nwg) return pm_turn_skip_block(g.gate, WVM * WVN);
     {                                        // XCD-aware order over the live tiles of all groups (see below)
       const int q = nwg >> 3, r = nwg & 7, xcd = t & 7, idx = t >> 3;
       t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
@@ -410,12 +416,12 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
   // (with a device-side row count only the live row panels take part, so they still spread over all 8 XCDs)
   if (!TA && !g.packed) {
     nwg = ((M + BM - 1) / BM) * g.ntn;
-    if (t >= nwg) GEMM_SKIP;
+    if (t >= nwg) return pm_turn_skip_block(g.gate, WVM * WVN);
     const int q = nwg >> 3, r = nwg & 7, xcd = t & 7, idx = t >> 3;
     t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int m0 = (t / g.ntn) * BM, n0 = (t % g.ntn) * BN;
-  if (m0 >= M) GEMM_SKIP;
+  if (m0 >= M) return pm_turn_skip_block(g.gate, WVM * WVN);
   // Row classes (compact GCL): rows [b1,b3) of the group's list receive onset edges, rows [b2,b4) next edges; for all
   // other rows that block of the aggregate is identically zero.  Forward (cls_dim 1): skip those K blocks for a row
   // tile without such rows; input gradient (2): skip the output tiles nobody reads; weight gradient (3): contract
@@ -429,21 +435,21 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
       const int lo = mb == 1 ? on_lo : (mb == 2 ? nx_lo : 0), hi = mb == 1 ? on_hi : (mb == 2 ? nx_hi : K);
       g.rowmap += lo;
       K = hi - lo;
-      if (K <= 0) GEMM_SKIP;
+      if (K <= 0) return pm_turn_skip_block(g.gate, WVM * WVN);
       kper = (((K + (int)gridDim.z - 1) / (int)gridDim.z + BK - 1) / BK) * BK;
     } else {
       use_on = m0 < on_hi && m0 + BM > on_lo;
       use_nx = m0 < nx_hi && m0 + BM > nx_lo;
       if (g.cls_dim == 2) {
         const int nb_ = n0 / g.cls_blk;
-        if ((nb_ == 1 && !use_on) || (nb_ == 2 && !use_nx)) GEMM_SKIP;
+        if ((nb_ == 1 && !use_on) || (nb_ == 2 && !use_nx)) return pm_turn_skip_block(g.gate, WVM * WVN);
       }
     }
   }
   const int kbeg = zs * kper;
   int kend = kbeg + kper;
   if (kend > K) kend = K;
-  if (kbeg >= kend) GEMM_SKIP;
+  if (kbeg >= kend) return pm_turn_skip_block(g.gate, WVM * WVN);
 
   const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) % (WVM * WVN);
   const bool producer = X6 && threadIdx.x >= THREADS;
@@ -467,6 +473,7 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+  // ---------------- 2. main loop of the mode: planes with B direct | planes | x6 | fp32
   if constexpr (PL) {
     // Pre-split operands: single LDS image per operand (two barriers per k-tile, 4 workgroups per CU cover them),
     // the loads of tile t+1 are in flight during the MFMAs of tile t.
@@ -492,16 +499,6 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
       const int q = v / kblk;
       return (q == 0 ? 0 : q == 1 ? s1 : q == 2 ? s2 : 3) * kblk + (v - q * kblk);
     };
-    f32x16 acc2;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
-    f32x16 accb[PM_BD_DUAL ? TM : 1][PM_BD_DUAL ? TN : 1];
-#pragma unroll
-    for (int i = 0; i < (PM_BD_DUAL ? TM : 1); ++i)
-#pragma unroll
-      for (int j = 0; j < (PM_BD_DUAL ? TN : 1); ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accb[i][j][r] = 0.f;
     if constexpr (BD) {
       // B direct (MODE 3): B is a weight matrix kept as FRAGMENT-MAJOR planes (pm_split_planes_frag): the 1 KiB that a
       // wave needs for one (32-row tile, 16-wide k-step, plane) MFMA operand is contiguous, so every wave takes its B
@@ -552,228 +549,192 @@ __global__ void __launch_bounds__(64 * WVM * WVN * (MODE == 1 ? 2 : 1))
           for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int i = 0; i < TM; ++i) a[p][i] = PA_::frag(Ax0 + p * PA_::PPLANE, wr * WM + i * 32, ks, lane);
-          constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};    // smallest terms first
 #pragma unroll
           for (int t6 = 0; t6 < 6; ++t6)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-              for (int j = 0; j < TN; ++j) {
-                if (PM_BD_DUAL && (t6 & 1))      // odd products to a second accumulator set: twice the independent chains
-                  accb[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t6]][i], bq[ks][PB[t6]][j], accb[i][j], 0, 0, 0);
-                else
-                  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t6]][i], bq[ks][PB[t6]][j], acc[i][j], 0, 0, 0);
-              }
+              for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t6]][i], bq[ks][PB[t6]][j], acc[i][j], 0, 0, 0);
           bload(bq[ks], kn < kend ? kn + ks * 16 : kend);
         }
         __syncthreads();
         if (v0 + BK < kv_end) pa.store(Ax0);
         __syncthreads();
       }
-      if (PM_BD_DUAL) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] += accb[PM_BD_DUAL ? i : 0][PM_BD_DUAL ? j : 0][r];
-      }
     } else {
-    pa.prime(kbeg, kend);
-    pb.prime(kbeg, kend);
-    pa.load(kmap(0), kend);
-    pb.load(kmap(0), kend);
-    char* const Bx1 = Ax0 + PA_::PBYTES;
-    pa.store(Ax0);
-    pb.store(Bx1);
-    __syncthreads();
-    for (int v0 = 0; v0 < kv_end; v0 += BK) {
-      pa.load(kmap(v0 + BK), kend);            // (past the end: out-of-range offsets, returns 0, no traffic)
-      pb.load(kmap(v0 + BK), kend);
-      constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};    // smallest terms first
-      if constexpr (PM_TN_DUAL && TM * TN == 1 && BK == 32) {
+      f32x16 acc2;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+      pa.prime(kbeg, kend);
+      pb.prime(kbeg, kend);
+      pa.load(kmap(0), kend);
+      pb.load(kmap(0), kend);
+      char* const Bx1 = Ax0 + PA_::PBYTES;
+      pa.store(Ax0);
+      pb.store(Bx1);
+      __syncthreads();
+      for (int v0 = 0; v0 < kv_end; v0 += BK) {
+        pa.load(kmap(v0 + BK), kend);            // (past the end: out-of-range offsets, returns 0, no traffic)
+        pb.load(kmap(v0 + BK), kend);
         // one 32x32 tile per wave: its six products per k-step form ONE dependent MFMA chain; the two k-steps of the
         // tile go to two accumulators (added in the epilogue), so two independent chains interleave
-        bf16x8 a[2][3], b[2][3];
+        static_assert(TM * TN == 1 && BK == 32, "planes kernel: one 32x32 tile per wave, two k-steps per k-tile");
+        {
+          bf16x8 a[2][3], b[2][3];
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
+          for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            a[ks][p] = PA_::frag(Ax0 + p * PA_::PPLANE, wr * WM, ks, lane);
-            b[ks][p] = PB_::frag(Bx1 + p * PB_::PPLANE, wc * WN, ks, lane);
+            for (int p = 0; p < 3; ++p) {
+              a[ks][p] = PA_::frag(Ax0 + p * PA_::PPLANE, wr * WM, ks, lane);
+              b[ks][p] = PB_::frag(Bx1 + p * PB_::PPLANE, wc * WN, ks, lane);
+            }
+#pragma unroll
+          for (int t6 = 0; t6 < 6; ++t6) {
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][PA[t6]], b[0][PB[t6]], acc[0][0], 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][PA[t6]], b[1][PB[t6]], acc2, 0, 0, 0);
           }
-#pragma unroll
-        for (int t6 = 0; t6 < 6; ++t6) {
-          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][PA[t6]], b[0][PB[t6]], acc[0][0], 0, 0, 0);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][PA[t6]], b[1][PB[t6]], acc2, 0, 0, 0);
         }
-      } else {
-#pragma unroll
-      for (int ks = 0; ks < BK / 16; ++ks) {
-        bf16x8 a[3][TM], b[3][TN];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) a[p][i] = PA_::frag(Ax0 + p * PA_::PPLANE, wr * WM + i * 32, ks, lane);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) b[p][j] = PB_::frag(Bx1 + p * PB_::PPLANE, wc * WN + j * 32, ks, lane);
+        __syncthreads();
+        if (v0 + BK < kv_end) {
+          pa.store(Ax0);
+          pb.store(Bx1);
         }
-#pragma unroll
-        for (int t6 = 0; t6 < 6; ++t6)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t6]][i], b[PB[t6]][j], acc[i][j], 0, 0, 0);
+        __syncthreads();
       }
-      }
-      __syncthreads();
-      if (v0 + BK < kv_end) {
-        pa.store(Ax0);
-        pb.store(Bx1);
-      }
-      __syncthreads();
-    }
-    }
-    if constexpr (PM_TN_DUAL && TM * TN == 1 && BK == 32 && !BD) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[0][0][r] += acc2[r];
     }
   } else {
-  sa.init(g.A, g.lda, m0, M, mapA, g.rpe);
-  sb.init(g.B, g.ldb, n0, g.N, mapB, g.rpe, g.b_split, (int)(grp * g.b_boff * 4), (int)(g.b_hi * 4));
-  sa.prime(kbeg, kend);
-  sb.prime(kbeg, kend);
-  if (!X6 || producer) {
-    sa.load(kbeg, kend);
-    sb.load(kbeg, kend);
-    if constexpr (X6) { sa.store_x6(Ax0); sb.store_x6(Bx0); }
-    else { sa.store(As0); sb.store(Bs0); }
-  }
-
-  int buf = 0;
-  if constexpr (X6) {
-    // Producer waves keep the global loads TWO k-tiles ahead (two register sets): at bf16 rate a k-tile of MFMAs
-    // is ~0.3-0.6 us, about one HBM round trip.  Iteration t: producers issue the loads of tile t+2 and split +
-    // store tile t+1 (loaded during iteration t-1) into LDS buffer (t+1)&1 while the consumers multiply tile t out
-    // of buffer t&1; one barrier per k-tile.
-    constexpr int NVA = StA::NV, NVB = StB::NV;
-    u32x4 ra[2][NVA], rb[2][NVB];
-    const int a_off = StA::x6_lane_off(wr * WM, lane), b_off = StB::x6_lane_off(wc * WN, lane);
-    if (producer) { sa.load_to(ra[1], kbeg + BK, kend); sb.load_to(rb[1], kbeg + BK, kend); }
-    __syncthreads();
-    auto phase = [&](int k0, u32x4 (&la)[NVA], u32x4 (&lb)[NVB], u32x4 (&na)[NVA], u32x4 (&nb)[NVB], int cb) {
-      // la/lb: register set the loads of tile k0+2BK go to; na/nb: set holding tile k0+BK; cb: LDS buffer of tile k0
-      if (producer) {
-        // unconditional (past the end every offset is out of range and the load returns 0 without touching
-        // memory): a conditional issue would make the vmcnt bookkeeping ambiguous and drain the prefetch
-        sa.load_to(la, k0 + 2 * BK, kend); sb.load_to(lb, k0 + 2 * BK, kend);
-        if (k0 + BK < kend) {
-          sa.store_x6_from(na, Ax0 + (cb ^ 1) * StA::XBYTES);
-          sb.store_x6_from(nb, Bx0 + (cb ^ 1) * StB::XBYTES);
-        }
-      } else {
-        const char* as = Ax0 + cb * StA::XBYTES + a_off;
-        const char* bs = Bx0 + cb * StB::XBYTES + b_off;
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-          bf16x8 a[3][TM], b[3][TN];
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[p][i] = StA::x6_frag(as + p * StA::XPLANE + i * StA::XSTEP_I + ks * StA::XSTEP_K);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[p][j] = StB::x6_frag(bs + p * StB::XPLANE + j * StB::XSTEP_I + ks * StB::XSTEP_K);
-          }
-          // smallest terms first: (3,1) (2,2) (1,3) | (2,1) (1,2) | (1,1)
-          constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-          for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-              for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t]][i], b[PB[t]][j], acc[i][j], 0, 0, 0);
-        }
-      }
+    sa.init(g.A, g.lda, m0, M, mapA, g.rpe);
+    sb.init(g.B, g.ldb, n0, g.N, mapB, g.rpe, g.b_split, (int)(grp * g.b_boff * 4), (int)(g.b_hi * 4));
+    sa.prime(kbeg, kend);
+    sb.prime(kbeg, kend);
+    if (!X6 || producer) {
+      sa.load(kbeg, kend);
+      sb.load(kbeg, kend);
+      if constexpr (X6) { sa.store_x6(Ax0); sb.store_x6(Bx0); }
+      else { sa.store(As0); sb.store(Bs0); }
+    }
+    int buf = 0;
+    if constexpr (X6) {
+      // Producer waves keep the global loads TWO k-tiles ahead (two register sets): at bf16 rate a k-tile of MFMAs
+      // is ~0.3-0.6 us, about one HBM round trip.  Iteration t: producers issue the loads of tile t+2 and split +
+      // store tile t+1 (loaded during iteration t-1) into LDS buffer (t+1)&1 while the consumers multiply tile t out
+      // of buffer t&1; one barrier per k-tile.
+      constexpr int NVA = StA::NV, NVB = StB::NV;
+      u32x4 ra[2][NVA], rb[2][NVB];
+      const int a_off = StA::x6_lane_off(wr * WM, lane), b_off = StB::x6_lane_off(wc * WN, lane);
+      if (producer) { sa.load_to(ra[1], kbeg + BK, kend); sb.load_to(rb[1], kbeg + BK, kend); }
       __syncthreads();
-    };
-    for (int k0 = kbeg; k0 < kend; k0 += 2 * BK) {
-      phase(k0, ra[0], rb[0], ra[1], rb[1], 0);
-      if (k0 + BK < kend) phase(k0 + BK, ra[1], rb[1], ra[0], rb[0], 1);
-    }
-  } else {
-  __syncthreads();
-  // bias gradient riding along with a weight gradient dW = dy^T x (PmGemmDesc.a_colsum): the waves of the first column
-  // of the first column tile add up the A fragments they feed to the matrix core anyway (lane (li, lh) holds
-  // A[k + lh, m + li]); one atomic per output row and workgroup in the epilogue
-  const bool do_cs = TA && MODE == 0 && g.colsum_a != nullptr && n0 == 0 && wc == 0;
-  float csa[TM];
+      auto phase = [&](int k0, u32x4 (&la)[NVA], u32x4 (&lb)[NVB], u32x4 (&na)[NVA], u32x4 (&nb)[NVB], int cb) {
+        // la/lb: register set the loads of tile k0+2BK go to; na/nb: set holding tile k0+BK; cb: LDS buffer of tile k0
+        if (producer) {
+          // unconditional (past the end every offset is out of range and the load returns 0 without touching
+          // memory): a conditional issue would make the vmcnt bookkeeping ambiguous and drain the prefetch
+          sa.load_to(la, k0 + 2 * BK, kend); sb.load_to(lb, k0 + 2 * BK, kend);
+          if (k0 + BK < kend) {
+            sa.store_x6_from(na, Ax0 + (cb ^ 1) * StA::XBYTES);
+            sb.store_x6_from(nb, Bx0 + (cb ^ 1) * StB::XBYTES);
+          }
+        } else {
+          const char* as = Ax0 + cb * StA::XBYTES + a_off;
+          const char* bs = Bx0 + cb * StB::XBYTES + b_off;
 #pragma unroll
-  for (int i = 0; i < TM; ++i) csa[i] = 0.f;
-  for (int k0 = kbeg; k0 < kend; k0 += BK) {
-    const bool more = k0 + BK < kend;
-    if (more) {
-      sa.load(k0 + BK, kend);
-      sb.load(k0 + BK, kend);
-    }
-    const float* as = As0 + buf * (BK * LDA_S) + wr * WM + li + lh * LDA_S;
-    const float* bs = Bs0 + buf * (BK * LDB_S) + wc * WN + li + lh * LDB_S;
-    // fragments of step kk+2 are read while the MFMAs of step kk run (explicit LDS software pipeline)
-    float a[2][TM], b[2][TN];
+          for (int ks = 0; ks < BK / 16; ++ks) {
+            bf16x8 a[3][TM], b[3][TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) a[0][i] = as[i * 32];
+            for (int p = 0; p < 3; ++p) {
 #pragma unroll
-    for (int j = 0; j < TN; ++j) b[0][j] = bs[j * 32];
+              for (int i = 0; i < TM; ++i) a[p][i] = StA::x6_frag(as + p * StA::XPLANE + i * StA::XSTEP_I + ks * StA::XSTEP_K);
 #pragma unroll
-    for (int kk = 0; kk < BK; kk += 2) {
-      const int cur = (kk >> 1) & 1, nxt = cur ^ 1;
-      if (kk + 2 < BK) {
+              for (int j = 0; j < TN; ++j) b[p][j] = StB::x6_frag(bs + p * StB::XPLANE + j * StB::XSTEP_I + ks * StB::XSTEP_K);
+            }
 #pragma unroll
-        for (int i = 0; i < TM; ++i) a[nxt][i] = as[(kk + 2) * LDA_S + i * 32];
+            for (int t = 0; t < 6; ++t)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) b[nxt][j] = bs[(kk + 2) * LDB_S + j * 32];
+              for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t]][i], b[PB[t]][j], acc[i][j], 0, 0, 0);
+          }
+        }
+        __syncthreads();
+      };
+      for (int k0 = kbeg; k0 < kend; k0 += 2 * BK) {
+        phase(k0, ra[0], rb[0], ra[1], rb[1], 0);
+        if (k0 + BK < kend) phase(k0 + BK, ra[1], rb[1], ra[0], rb[0], 1);
       }
-      __builtin_amdgcn_sched_barrier(0);     // keep the next step's ds_reads ahead of this step's MFMAs
+    } else {
+      __syncthreads();
+      // bias gradient riding along with a weight gradient dW = dy^T x (PmGemmDesc.a_colsum): the waves of the first column
+      // of the first column tile add up the A fragments they feed to the matrix core anyway (lane (li, lh) holds
+      // A[k + lh, m + li]); one atomic per output row and workgroup in the epilogue
+      const bool do_cs = TA && MODE == 0 && g.colsum_a != nullptr && n0 == 0 && wc == 0;
+      float csa[TM];
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+      for (int i = 0; i < TM; ++i) csa[i] = 0.f;
+      for (int k0 = kbeg; k0 < kend; k0 += BK) {
+        const bool more = k0 + BK < kend;
+        if (more) {
+          sa.load(k0 + BK, kend);
+          sb.load(k0 + BK, kend);
+        }
+        const float* as = As0 + buf * (BK * LDA_S) + wr * WM + li + lh * LDA_S;
+        const float* bs = Bs0 + buf * (BK * LDB_S) + wc * WN + li + lh * LDB_S;
+        // fragments of step kk+2 are read while the MFMAs of step kk run (explicit LDS software pipeline)
+        float a[2][TM], b[2][TN];
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
+        for (int i = 0; i < TM; ++i) a[0][i] = as[i * 32];
+#pragma unroll
+        for (int j = 0; j < TN; ++j) b[0][j] = bs[j * 32];
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+          const int cur = (kk >> 1) & 1, nxt = cur ^ 1;
+          if (kk + 2 < BK) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[nxt][i] = as[(kk + 2) * LDA_S + i * 32];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[nxt][j] = bs[(kk + 2) * LDB_S + j * 32];
+          }
+          __builtin_amdgcn_sched_barrier(0);     // keep the next step's ds_reads ahead of this step's MFMAs
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][i], b[cur][j], acc[i][j], 0, 0, 0);
+          if constexpr (TA && MODE == 0) {
+            if (do_cs) {
+#pragma unroll
+              for (int i = 0; i < TM; ++i) csa[i] += a[cur][i];
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (more) {
+          sa.store(As0 + (buf ^ 1) * (BK * LDA_S));
+          sb.store(Bs0 + (buf ^ 1) * (BK * LDB_S));
+        }
+        __syncthreads();
+        buf ^= 1;
+      }
       if constexpr (TA && MODE == 0) {
         if (do_cs) {
+          pm_turn_enter(g.gate, my_turn);
+          in_turn = true;
 #pragma unroll
-          for (int i = 0; i < TM; ++i) csa[i] += a[cur][i];
+          for (int i = 0; i < TM; ++i) {
+            const float v = csa[i] + __shfl_xor(csa[i], 32);
+            const int row = m0 + wr * WM + i * 32 + li;
+            if (lh == 0 && row < M) atomicAdd(g.colsum_a + row, v);
+          }
         }
       }
-      __builtin_amdgcn_sched_barrier(0);
     }
-    if (more) {
-      sa.store(As0 + (buf ^ 1) * (BK * LDA_S));
-      sb.store(Bs0 + (buf ^ 1) * (BK * LDB_S));
-    }
-    __syncthreads();
-    buf ^= 1;
-  }
-  if constexpr (TA && MODE == 0) {
-    if (do_cs) {
-      pm_turn_enter(g.gate, my_turn);
-      in_turn = true;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const float v = csa[i] + __shfl_xor(csa[i], 32);
-        const int row = m0 + wr * WM + i * 32 + li;
-        if (lh == 0 && row < M) atomicAdd(g.colsum_a + row, v);
-      }
-    }
-  }
-  }
-
   }
   if (producer) return;
-#undef GEMM_SKIP
   if (!in_turn) pm_turn_enter(g.gate, my_turn);
-  // Epilogue.  C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5).
+  // ---------------- 3. epilogue.  C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5).
   const bool atomic = gridDim.z > 1;
   const bool accum = (g.flags & PM_GEMM_ACCUM) != 0;
   const bool relu = (g.flags & PM_GEMM_RELU) != 0;
@@ -853,31 +814,70 @@ static void launch_one(dim3 grid, hipStream_t st, const GemmArgs& g) {
   }
   hipLaunchKernelGGL(kern, grid, dim3(64 * WVM * WVN * (MODE == 1 ? 2 : 1)), lds, st, g);
 }
+// One tile kernel = one (configuration, layout); the fp32 tiles additionally exist per operand alignment.
+typedef void (*GemmLaunch)(bool va, bool vb, dim3 grid, hipStream_t st, const GemmArgs& g);
 template <int BM, int BN, int BK, int WVM, int WVN, bool TA, bool TB, int MODE>
-static void launch_v(bool va, bool vb, dim3 grid, hipStream_t st, const GemmArgs& g) {
+static void launch_aligned(bool va, bool vb, dim3 grid, hipStream_t st, const GemmArgs& g) {
   if constexpr (MODE != 0) launch_one<BM, BN, BK, WVM, WVN, TA, TB, true, true, MODE>(grid, st, g);
   else if (va && vb) launch_one<BM, BN, BK, WVM, WVN, TA, TB, true, true, 0>(grid, st, g);
   else if (va) launch_one<BM, BN, BK, WVM, WVN, TA, TB, true, false, 0>(grid, st, g);
   else if (vb) launch_one<BM, BN, BK, WVM, WVN, TA, TB, false, true, 0>(grid, st, g);
   else launch_one<BM, BN, BK, WVM, WVN, TA, TB, false, false, 0>(grid, st, g);
 }
+
+// The configuration table: every tile kernel this file builds is named here, and nothing else is instantiated.
+// Ids index the profiler classes (PM_PROF_GEMM0 + 3 * id + layout) and the tile names of ops.py by position, so the ids
+// of configurations that were tried and dropped (1, 3: 128x128 fp32 tiles; 6: x6 64x64x32; 10: planes 128x128x32) stay
+// retired and are not reused.
+enum { GEMM_FP32 = 0, GEMM_X6 = 1, GEMM_PLANES = 2, GEMM_PLANES_BD = 3 };        // = MODE of k_gemm
+enum { LAY_NN = 0, LAY_NT = 1, LAY_TN = 2 };
+struct GemmTile { int BM, BN, BK; GemmLaunch launch; };                          // launch == nullptr: no kernel for this layout
+struct GemmCfg { int id, mode; GemmTile lay[3]; };                               // lay[LAY_NN], lay[LAY_NT], lay[LAY_TN]
 template <int BM, int BN, int BK, int WVM, int WVN, int MODE>
-static void launch_t(int ta, int tb, bool va, bool vb, dim3 grid, hipStream_t st, const GemmArgs& g) {
-  if (!ta && !tb) launch_v<BM, BN, BK, WVM, WVN, false, false, MODE>(va, vb, grid, st, g);
-  else if (!ta && tb) launch_v<BM, BN, BK, WVM, WVN, false, true, MODE>(va, vb, grid, st, g);
-  else if constexpr (MODE != 3) launch_v<BM, BN, BK, WVM, WVN, true, false, MODE>(va, vb, grid, st, g);
+constexpr GemmTile TILE_NN = {BM, BN, BK, launch_aligned<BM, BN, BK, WVM, WVN, false, false, MODE>};
+template <int BM, int BN, int BK, int WVM, int WVN, int MODE>
+constexpr GemmTile TILE_NT = {BM, BN, BK, launch_aligned<BM, BN, BK, WVM, WVN, false, true, MODE>};
+template <int BM, int BN, int BK, int WVM, int WVN, int MODE>
+constexpr GemmTile TILE_TN = {BM, BN, BK, launch_aligned<BM, BN, BK, WVM, WVN, true, false, MODE>};
+constexpr GemmTile NO_TILE = {0, 0, 0, nullptr};
+static const GemmCfg GEMM_CFGS[] = {
+    {0, GEMM_FP32, {TILE_NN<64, 64, 16, 2, 2, 0>, TILE_NT<64, 64, 16, 2, 2, 0>, TILE_TN<64, 64, 16, 2, 2, 0>}},
+    {2, GEMM_FP32, {TILE_NN<64, 64, 32, 2, 2, 0>, TILE_NT<64, 64, 32, 2, 2, 0>, TILE_TN<64, 64, 32, 2, 2, 0>}},
+    {4, GEMM_X6, {TILE_NN<128, 128, 16, 2, 2, 1>, TILE_NT<128, 128, 16, 2, 2, 1>, NO_TILE}},
+    {5, GEMM_X6, {NO_TILE, NO_TILE, TILE_TN<128, 64, 16, 2, 2, 1>}},
+    {7, GEMM_X6, {TILE_NN<128, 128, 32, 2, 2, 1>, TILE_NT<128, 128, 32, 2, 2, 1>, NO_TILE}},
+    // pre-split operands: 64x64x32 (measured in the step: 128x64x32 85 us, 128x128x32 97-130 us against 70-80 us)
+    {8, GEMM_PLANES, {TILE_NN<64, 64, 32, 2, 2, 2>, TILE_NT<64, 64, 32, 2, 2, 2>, TILE_TN<64, 64, 32, 2, 2, 2>}},
+    // B direct: k-tiles of 64 for the forward (K = 4d: half the barriers, 62.2 -> 59.8 us), of 32 for the input gradient (K = d)
+    {9, GEMM_PLANES_BD, {TILE_NN<64, 128, 64, 1, 4, 3>, TILE_NT<64, 128, 32, 1, 4, 3>, NO_TILE}},
+};
+static const GemmCfg* find_config(int id) {
+  for (const GemmCfg& c : GEMM_CFGS)
+    if (c.id == id) return &c;
+  return nullptr;
 }
 
-enum { PM_GEMM_NCFG = 11 };                   // 0..3 fp32 MFMA, 4..7 split mode, 8 / 10 pre-split planes, 9 planes with B direct
-static const int CFG_BM[PM_GEMM_NCFG] = {64, 128, 64, 128, 128, 128, 64, 128, 64, 64, 128};
-static const int CFG_BN[PM_GEMM_NCFG] = {64, 128, 64, 128, 128, 64, 64, 128, 64, 128, 128};
-static const int CFG_BK[PM_GEMM_NCFG] = {16, 16, 32, 32, 16, 16, 32, 32, 32, 32, 32};   // (config 9: 64 for the long-K forward product)
+// What the choice needs to know about a product beyond its descriptor.
+struct GemmFacts {
+  bool x6_ok;      // both operands 16-byte aligned with extents that are multiples of 4: the x6 kernels can stage them
+  bool bdirect;    // planes: B is also given as fragment-major planes and the tiles line up with the fragment grid
+};
 
-// Tile configuration: an explicit override (pm_gemm_force_config, for A/B timing in one process) or the shape rule.
-static int g_forced_cfg = -1;
-extern "C" int pm_gemm_force_config(int32_t cfg) { g_forced_cfg = (cfg >= 0 && cfg < 8) ? cfg : -1; return PM_OK; }
-static int pick_config(int transA, int M, int N, int K, bool x6_ok = false, bool ungrouped = false) {
-  if (g_forced_cfg >= 0 && (g_forced_cfg < 4 || x6_ok)) return g_forced_cfg;
+// A configuration pinned by pm_gemm_force_config (A/B timing in one process), or nullptr: the shape rule decides.
+static const GemmCfg* g_pinned_cfg = nullptr;
+extern "C" int pm_gemm_force_config(int32_t cfg) {
+  const GemmCfg* c = cfg == -1 ? nullptr : find_config(cfg);
+  if (cfg != -1 && (!c || c->mode > GEMM_X6)) return PM_E_INVALID;             // retired, planes (the operands decide) or unknown
+  g_pinned_cfg = c;
+  return PM_OK;
+}
+
+// The one choice: pm_gemm_f32_desc launches the row this returns, and pm_gemm_config reports it.
+static const GemmCfg* choose_config(const PmGemmDesc& q, const GemmFacts& f) {
+  const int lay = q.transA ? LAY_TN : (q.transB ? LAY_NT : LAY_NN);
+  if (q.operand_planes) return find_config(f.bdirect ? 9 : 8);
+  // a pinned fp32 tile applies to everything, a pinned x6 tile where the operands allow x6 and it has the layout
+  if (g_pinned_cfg && (g_pinned_cfg->mode == GEMM_FP32 || (f.x6_ok && g_pinned_cfg->lay[lay].launch))) return g_pinned_cfg;
   // Measured on MI355X (tools/bench_gemm.py, shapes of the training step, interleaved A/B in one process):
   //  - NN / NT (the node dimension is M): 64x64 tiles win or tie everywhere: 4 workgroups per CU = 4 waves per
   //    SIMD hide the LDS / barrier latency; the panels they re-read sit in L2 / Infinity Cache.  With a long K
@@ -890,25 +890,25 @@ static int pick_config(int transA, int M, int N, int K, bool x6_ok = false, bool
   //  - Split mode (x6, needs 16-byte aligned operands) wins on every large shape of the step (same harness):
   //    NN/NT K >= 1024: 128x128x32 126-173 TFLOP/s (fp32 mode 96-118); NN/NT short K: 128x128x16 114-140 (90-108);
   //    TN: 128x64x16 123-155 (77-107).  Small problems stay on the fp32 tiles (fewer, cheaper workgroups).
-  //    Inside the training step (row-gathered, grouped launches, one 8-wave workgroup per CU) the gain did not
-  //    materialise (10.71 ms against 10.78 ms per step), so split mode is opt-in: PM_GEMM_SPLIT=1 or a forced config.
-  constexpr bool split_on = false;
-  // default: the large UNGROUPED NN / NT products (chord encoder / decoder and their input gradients) run in split
-  // mode (78-90 us against 99-112 us in the step); weight gradients stay on the fp32 tiles (split mode: 132 against 106 us)
-  constexpr bool split_ungrouped = true;
-  // (N < 128: the 128-wide split tiles would be partly empty — the duration un-embedding, N = 99: 60 us against 46 us on the fp32 tiles)
-  // ... since round 4 the large weight gradients too: they now run beside the head chain / in the step's tail, not beside the
-  // one-workgroup-per-CU GCL kernels, and there the split tiles win (step 4.892 -> 4.859 ms; PM_GEMM_SPLIT_TN=0: fp32 tiles)
-  constexpr bool split_tn = true;
-  if ((split_on || (split_ungrouped && ungrouped && !transA && N >= 128) || (split_tn && transA)) && x6_ok && (double)M * N * K >= 1.0e9) {
-    constexpr int tn_cfg = 5;   // (development A/B: 4, 5, 7)
-    if (transA) return (tn_cfg == 4 || tn_cfg == 7) ? tn_cfg : 5;
-    return K >= 1024 ? 7 : 4;
-  }
-  return K >= 1024 ? 2 : 0;
+  //    Inside the training step the row-gathered and grouped NN / NT launches (one 8-wave workgroup per CU) did not
+  //    gain (10.71 ms against 10.78 ms per step) and stay on the fp32 tiles.  x6 runs
+  //     * the large UNGROUPED NN / NT products without a row map (chord encoder / decoder and their input gradients:
+  //       78-90 us against 99-112 us in the step) with N >= 128 (below, the 128-wide tiles would be partly empty — the
+  //       duration un-embedding, N = 99: 60 us against 46 us on the fp32 tiles);
+  //     * the large weight gradients, grouped or not: they run beside the head chain / in the step's tail, not beside
+  //       the one-workgroup-per-CU GCL kernels, and there the 128x64x16 tiles win (step 4.892 -> 4.859 ms; alone
+  //       beside the GCL kernels they had lost, 132 against 106 us).
+  const bool plain = q.n_groups == 1 && !q.rowmap;
+  if (f.x6_ok && (double)q.M * q.N * q.K >= 1.0e9 && (q.transA || (plain && q.N >= 128)))
+    return find_config(q.transA ? 5 : (q.K >= 1024 ? 7 : 4));
+  return find_config(q.K >= 1024 ? 2 : 0);
 }
 
-extern "C" int pm_gemm_config(int32_t transA, int32_t M, int32_t N, int32_t K) { return pick_config(transA, M, N, K); }
+extern "C" int pm_gemm_config(int32_t transA, int32_t M, int32_t N, int32_t K) {
+  PmGemmDesc q = {};                                       // a plain product: one group, no row map, fp32 operands ...
+  q.transA = transA; q.M = M; q.N = N; q.K = K; q.n_groups = 1;
+  return choose_config(q, GemmFacts{true, false})->id;     // ... that are 16-byte aligned
+}
 
 static inline bool ldc_contig(const PmGemmDesc* q, int N) { return q->ldc == N; }
 
@@ -954,16 +954,16 @@ extern "C" int pm_gemm_f32_desc(const PmGemmDesc* q, pm_stream_t stream) {
   g.a_ps = q->a_plane_stride; g.b_ps = q->b_plane_stride;
   g.bfrag = reinterpret_cast<const char*>(q->b_frag); g.bf_n = transB ? q->ldb / 16 : q->ldb / 32;
   g.cls_ptr = q->class_ptr; g.cls_blk = q->class_block; g.cls_dim = 0;
-  // planes mode: 64x64x32 tiles (measured in the step: 128x64x32 85 us, 128x128x32 97-130 us against 70-80 us)
   // B direct (config 9): B given additionally as fragment-major planes; forward / input-gradient products whose tiles
   // are aligned with the fragment grid (and, with row classes, with the 128-wide column tile)
-  constexpr bool bdirect_on = true;
-  const bool bdirect = planes && q->b_frag && bdirect_on && !transA && N % 128 == 0 && K % 32 == 0 && q->ldb % 32 == 0 &&
+  const bool bdirect = planes && q->b_frag && !transA && N % 128 == 0 && K % 32 == 0 && q->ldb % 32 == 0 &&
                        (n_groups == 1 || q->b_split_rows > 0) && q->b_split_rows % 32 == 0 &&
                        (q->b_split_rows == 0 || (q->b_group_stride % q->ldb == 0 && q->b_shared_off % q->ldb == 0)) &&
                        ((uintptr_t)q->b_frag % 16 == 0) && (!q->class_ptr || q->class_block % 128 == 0);
-  const int cfg = planes ? (bdirect ? 9 : 8) : pick_config(transA, M, N, K, va && vb, n_groups == 1 && !q->rowmap);
-  const int BM = CFG_BM[cfg], BN = CFG_BN[cfg], BK = (cfg == 9 && !transB) ? 64 : CFG_BK[cfg];
+  const int lay = transA ? LAY_TN : (transB ? LAY_NT : LAY_NN);
+  const GemmCfg& cfg = *choose_config(*q, GemmFacts{va && vb, bdirect});
+  const GemmTile& tile = cfg.lay[lay];
+  const int BM = tile.BM, BN = tile.BN, BK = tile.BK;
   if (q->class_ptr && q->class_block > 0 && q->rowmap && q->dyn_entries && q->rows_per_entry == 1) {
     const int blk = q->class_block;           // which dimension carries the [track | onset | next | x] blocks
     if (transA) { if (M == 4 * blk && blk % BM == 0) g.cls_dim = 3; }
@@ -974,7 +974,7 @@ extern "C" int pm_gemm_f32_desc(const PmGemmDesc* q, pm_stream_t stream) {
   // column-sum kernel (same result, one more launch)
   if (q->a_colsum) {
     if (!transA || q->rowmap || q->dyn_entries || n_groups != 1 || planes) return PM_E_INVALID;
-    if (cfg <= 3) g.colsum_a = q->a_colsum;
+    if (cfg.mode == GEMM_FP32) g.colsum_a = q->a_colsum;
     else {
       const int rc = pm_colsum_acc(q->A, K, M, q->lda, q->a_colsum, stream);
       if (rc != PM_OK) return rc;
@@ -1024,23 +1024,8 @@ extern "C" int pm_gemm_f32_desc(const PmGemmDesc* q, pm_stream_t stream) {
   // deterministic mode: K slices, groups that share stacked rows, column statistics and the bias gradient add in turn
   g.gate = (split_k > 1 || g.colstats || g.colsum_a || (g.c_split > 0 && n_groups > 1)) ? pm_det_gate(st) : nullptr;
   const double work = 2.0 * M * N * K * (partitioned ? 1.0 : (double)n_groups);
-  const int pe = pm_prof_open(st, PM_PROF_GEMM0 + cfg * 3 + (transA ? 2 : (transB ? 1 : 0)), work);
-  switch (cfg) {
-    case 0: launch_t<64, 64, 16, 2, 2, 0>(transA, transB, va_rows, vb_rows, grid, st, g); break;
-    case 1: launch_t<128, 128, 16, 2, 2, 0>(transA, transB, va_rows, vb_rows, grid, st, g); break;
-    case 2: launch_t<64, 64, 32, 2, 2, 0>(transA, transB, va_rows, vb_rows, grid, st, g); break;
-    case 3: launch_t<128, 128, 32, 2, 2, 0>(transA, transB, va_rows, vb_rows, grid, st, g); break;
-    case 4: launch_t<128, 128, 16, 2, 2, 1>(transA, transB, va, vb, grid, st, g); break;
-    case 5: launch_t<128, 64, 16, 2, 2, 1>(transA, transB, va, vb, grid, st, g); break;
-    case 6: launch_t<64, 64, 32, 2, 2, 1>(transA, transB, va, vb, grid, st, g); break;
-    case 7: launch_t<128, 128, 32, 2, 2, 1>(transA, transB, va, vb, grid, st, g); break;
-    case 8: launch_t<64, 64, 32, 2, 2, 2>(transA, transB, va, vb, grid, st, g); break;
-    case 9:        // B direct: k-tiles of 64 for the forward (K = 4d: half the barriers, 62.2 -> 59.8 us), of 32 for the input gradient (K = d)
-      if (transB) launch_t<64, 128, 32, 1, 4, 3>(transA, transB, va, vb, grid, st, g);
-      else launch_t<64, 128, 64, 1, 4, 3>(transA, transB, va, vb, grid, st, g);
-      break;
-    default: launch_t<128, 128, 32, 2, 2, 2>(transA, transB, va, vb, grid, st, g); break;
-  }
+  const int pe = pm_prof_open(st, PM_PROF_GEMM0 + cfg.id * 3 + lay, work);
+  tile.launch(va_rows, vb_rows, grid, st, g);               // (the alignment matters to the fp32 tiles only, see above)
   pm_prof_close(st, pe);
   return pm_check_launch();
 }

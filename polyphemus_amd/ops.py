@@ -43,10 +43,16 @@ def _prof_end(name: str, e0, work: float):
 
 _GEMM_TILES = ("64x64x16", "128x128x16", "64x64x32", "128x128x32", "x6:128x128x16", "x6:128x64x16", "x6:64x64x32",
                "x6:128x128x32", "planes:64x64x32", "planesB:64x128x32", "planes:128x128x32")
+# Tile names by configuration id (the profiler's class numbering follows the same ids).  The library builds and launches
+# only the live ids; 1, 3, 6 and 10 are retired and keep their place in the list.  pm_gemm_force_config pins an fp32 or
+# x6 id; the planes configurations follow from the operands of a call.
+GEMM_LIVE_IDS = (0, 2, 4, 5, 7, 8, 9)
+GEMM_PIN_IDS = (0, 2, 4, 5, 7)
 
 
 def gemm_class(transA: bool, transB: bool, M: int, N: int, K: int) -> str:
-    """Kernel instance a GEMM call maps to (asks the library which tile configuration it picks)."""
+    """Kernel instance a plain GEMM call maps to: the library's own choice for one group, no row map and 16-byte
+    aligned fp32 operands (pm_gemm_config), which is what the launch runs for such a call."""
     from ._lib import lib
     return f"gemm_{'T' if transA else 'N'}{'T' if transB else 'N'}_{_GEMM_TILES[lib().pm_gemm_config(int(transA), M, N, K)]}"
 

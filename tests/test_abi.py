@@ -62,6 +62,63 @@ def test_ctypes_signatures_match_header():
         assert name in _lib.EXPORTED, f"{name} not bound"
 
 
+GEMM_LIVE, GEMM_PINS = (0, 2, 4, 5, 7, 8, 9), (0, 2, 4, 5, 7)       # configuration ids with kernels / that can be pinned
+PM_OK, PM_E_INVALID = 0, -1
+
+
+def test_gemm_force_config_accepts_live_ids_and_refuses_the_rest():
+    """`pm_gemm_force_config` (host only): -1 and the live fp32 / x6 ids are taken; retired ids (1, 3, 6, 10), the planes
+    ids (8, 9: the operands of a call decide) and unknown values are refused and leave the current pin in place —
+    seen through `pm_gemm_config`, which reports a pinned fp32 tile for every shape."""
+    from polyphemus_amd import ops
+    assert (ops.GEMM_LIVE_IDS, ops.GEMM_PIN_IDS) == (GEMM_LIVE, GEMM_PINS)
+    assert int(re.search(r"PM_E_INVALID = (-?\d+)", open(HEADER).read()).group(1)) == PM_E_INVALID
+    L = _lib.lib()
+    try:
+        for ok in (-1,) + GEMM_PINS:
+            assert L.pm_gemm_force_config(ok) == PM_OK, ok
+        for pin in (2, 0):
+            assert L.pm_gemm_force_config(pin) == PM_OK
+            for bad in (1, 3, 6, 8, 9, 10, 11, -2):
+                assert L.pm_gemm_force_config(bad) == PM_E_INVALID, bad
+                assert L.pm_gemm_config(0, 4096, 512, 128) == pin and L.pm_gemm_config(1, 512, 512, 8192) == pin, (pin, bad)
+        assert L.pm_gemm_force_config(-1) == PM_OK
+        assert L.pm_gemm_config(0, 4096, 512, 128) == 0                      # and automatic again: K < 1024, below 1e9
+    finally:
+        L.pm_gemm_force_config(-1)
+
+
+def test_gemm_config_reports_live_ids_and_follows_the_shape_rule():
+    """`pm_gemm_config` (host only; a plain product of 16-byte aligned operands): a live id for every shape, the x6
+    tiles from M*N*K = 1e9 on (NN / NT with N >= 128: K >= 1024 -> 7, else 4; TN: 5), else the fp32 tiles (K >= 1024 -> 2,
+    else 0); a pinned fp32 id is the answer for every shape."""
+    L = _lib.lib()
+
+    def rule(ta, M, N, K):
+        if M * N * K >= 10 ** 9 and (ta or N >= 128):
+            return 5 if ta else (7 if K >= 1024 else 4)
+        return 2 if K >= 1024 else 0
+
+    grid = [(ta, M, N, K) for ta in (0, 1) for M in (64, 1000, 4096, 16271) for N in (99, 127, 128, 512, 3840)
+            for K in (67, 256, 1023, 1024, 4096)]
+    # both sides of M*N*K = 1e9 (at K below and above 1024), N = 127 / 128 far above it
+    grid += [(ta, M, 1000, K) for ta in (0, 1) for M, K in ((999, 1001), (1000, 1000), (500, 2000), (499, 2000))]
+    grid += [(ta, 16384, N, K) for ta in (0, 1) for N in (127, 128) for K in (1000, 1024)]
+    try:
+        assert L.pm_gemm_force_config(-1) == PM_OK
+        seen = set()
+        for ta, M, N, K in grid:
+            cfg = L.pm_gemm_config(ta, M, N, K)
+            assert cfg in GEMM_LIVE and cfg == rule(ta, M, N, K), (ta, M, N, K, cfg)
+            seen.add(cfg)
+        assert seen == set(GEMM_PINS)
+        for pin in (0, 2):
+            assert L.pm_gemm_force_config(pin) == PM_OK
+            assert all(L.pm_gemm_config(ta, M, N, K) == pin for ta, M, N, K in grid)
+    finally:
+        L.pm_gemm_force_config(-1)
+
+
 def test_plan_layout_host_only():
     off = _lib.plan_layout(100, 400, 8)
     assert len(off) == len(_lib.PLAN_FIELDS) + 1

@@ -227,12 +227,16 @@ def test_gemm_weight_gradient_carries_the_bias_gradient(Kr, M, N, ldx):
     assert rel_err(db, db0.double() + dy.double().sum(0)) < 5e-6
 
 
-@pytest.mark.parametrize("cfg", [4, 5, 6, 7])
-@pytest.mark.parametrize("M,N,K,ta,tb", [
-    (1000, 256, 1024, False, False), (333, 1024, 256, False, True), (1024, 256, 3001 * 4, True, False),
-    (130, 132, 36, False, True), (515, 260, 72, False, False), (260, 68, 1028, True, False)])
+@pytest.mark.parametrize("M,N,K,ta,tb,cfg", [
+    (M, N, K, ta, tb, cfg)
+    for cfg in (4, 5, 7)
+    for M, N, K, ta, tb in [
+        (1000, 256, 1024, False, False), (333, 1024, 256, False, True), (1024, 256, 3001 * 4, True, False),
+        (130, 132, 36, False, True), (515, 260, 72, False, False), (260, 68, 1028, True, False)]
+    if ta == (cfg == 5)])
 def test_gemm_split_mode(cfg, M, N, K, ta, tb):
-    """split mode (three-term bf16 operand split, six products, fp32 accumulate): same bound as the fp32 tiles."""
+    """split mode (three-term bf16 operand split, six products, fp32 accumulate): same bound as the fp32 tiles.  Every
+    shape on every x6 configuration that has a kernel for its layout: 4 and 7 for NN / NT, 5 for TN."""
     torch.manual_seed(M + N + K + cfg)
     A = torch.randn((K, M) if ta else (M, K), device=DEV) * 3
     B = torch.randn((N, K) if tb else (K, N), device=DEV)
@@ -249,6 +253,57 @@ def test_gemm_split_mode(cfg, M, N, K, ta, tb):
         assert rel_err(acc, want) < 5e-6
     finally:
         lib().pm_gemm_force_config(-1)
+
+
+def _gemm_launch_classes(fn):
+    """launch counts per profiler class (PM_PROF_GEMM0 = 0: GEMM class = 3 * configuration id + layout) of the calls in fn"""
+    import ctypes
+    L = lib()
+    try:
+        L.pm_prof_configure(-1, 1)
+        L.pm_prof_begin(64)
+        fn()
+        torch.cuda.synchronize()
+        ms, work, cnt = (ctypes.c_double * PROF_NCLASS)(), (ctypes.c_double * PROF_NCLASS)(), (ctypes.c_int64 * PROF_NCLASS)()
+        assert L.pm_prof_end(ctypes.cast(ms, ctypes.c_void_p), ctypes.cast(work, ctypes.c_void_p),
+                             ctypes.cast(cnt, ctypes.c_void_p)) == 0
+    finally:
+        L.pm_prof_configure(-1, 1)
+    return list(cnt)
+
+
+@pytest.mark.parametrize("ta,tb,M,N,K,want", [
+    (False, False, 2048, 512, 1024, 7), (False, True, 8192, 512, 256, 4), (True, False, 512, 512, 4096, 5),
+    (False, True, 300, 131, 67, 0), (False, False, 256, 256, 1024, 2)])
+def test_gemm_reported_configuration_is_the_launched_one(ta, tb, M, N, K, want):
+    """`pm_gemm_config` (what `ops.gemm_class` and the profiling labels print) asks the function the launch asks: one
+    `ops.gemm` call is counted once, in the class of the configuration reported for its shape."""
+    torch.manual_seed(M + N + K)
+    A = torch.randn((K, M) if ta else (M, K), device=DEV)
+    B = torch.randn((N, K) if tb else (K, N), device=DEV)
+    out = torch.full((M, N), float("nan"), device=DEV)
+    cfg = lib().pm_gemm_config(int(ta), M, N, K)
+    assert cfg == want
+    cnt = _gemm_launch_classes(lambda: ops.gemm(A, B, out, M, N, K, A.stride(0), B.stride(0), N, transA=ta, transB=tb))
+    layout = 2 if ta else (1 if tb else 0)
+    assert sum(cnt) == 1 and cnt[3 * cfg + layout] == 1, [(c, n) for c, n in enumerate(cnt) if n]
+    ref = (A.double().t() if ta else A.double()) @ (B.double().t() if tb else B.double())
+    assert rel_err(out, ref) < 5e-6
+
+
+def test_gemm_reported_configuration_assumes_aligned_operands():
+    """`pm_gemm_config` answers for 16-byte aligned operands (its header says so): the same shape with A offset by one
+    float cannot be staged by the x6 kernels and lands on an fp32 tile, whatever is reported."""
+    M, N, K = 2048, 512, 1024
+    torch.manual_seed(9)
+    A = torch.randn(M * K + 1, device=DEV)[1:].view(M, K)
+    assert A.data_ptr() % 16 == 4
+    B = torch.randn(K, N, device=DEV)
+    out = torch.full((M, N), float("nan"), device=DEV)
+    assert lib().pm_gemm_config(0, M, N, K) == 7
+    cnt = _gemm_launch_classes(lambda: ops.gemm(A, B, out, M, N, K, K, N, N))
+    assert sum(cnt) == 1 and cnt[3 * 2 + 0] == 1, [(c, n) for c, n in enumerate(cnt) if n]     # fp32 64x64x32 (K >= 1024), NN
+    assert rel_err(out, A.double() @ B.double()) < 5e-6
 
 
 def test_split_planes_is_exact():

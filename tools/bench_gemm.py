@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""A/B timing (and error against float64) of the GEMM tile configurations, fp32-MFMA (0..3) and split mode (4..7), on the shapes of the training step
+"""A/B timing (and error against float64) of the GEMM tile configurations that can be pinned (ops.GEMM_PIN_IDS: fp32-MFMA 0, 2 and
+split mode 4, 5, 7; a configuration without a kernel for a shape's layout falls back to the shape rule) on the shapes of the training step
 (interleaved rounds in ONE process, HIP events; guide rule 24).  Usage on the GPU box:
     python tools/bench_gemm.py [--d 256] [--nodes 16271]"""
 import argparse
@@ -16,7 +17,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--d", type=int, default=256)
 ap.add_argument("--nodes", type=int, default=16271)
 ap.add_argument("--rounds", type=int, default=6)
-ap.add_argument("--cfgs", type=str, default="0,1,2,3,4,5,6,7")
+ap.add_argument("--cfgs", type=str, default=",".join(str(c) for c in ops.GEMM_PIN_IDS))
 args = ap.parse_args()
 d, Nn = args.d, args.nodes
 dev = "cuda"
@@ -30,6 +31,7 @@ shapes = [  # name, transA, transB, M, N, K
     ("dur_dW   TN", 1, 0, 99, d // 2, Nn * 15), ("head     NT", 0, 1, 256, d, 2 * d),
 ]
 cfgs = [int(c) for c in args.cfgs.split(",")]
+assert all(c in ops.GEMM_PIN_IDS for c in cfgs), f"configurations that can be pinned: {ops.GEMM_PIN_IDS}"
 print(f"{'shape':14s} {'M':>7s} {'N':>6s} {'K':>7s} auto | " + " | ".join(f"cfg{c} us  TF/s" for c in cfgs))
 for name, ta, tb, M, N, K in shapes:
     A = torch.randn((K, M) if ta else (M, K), device=dev)

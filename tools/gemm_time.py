@@ -12,7 +12,8 @@ def run(ta, tb, M, N, K, cfg, ldc=None, reps=20):
     B = torch.randn((N, K) if tb else (K, N), device="cuda")
     ldc = ldc or N
     C = torch.zeros(M, ldc, device="cuda")
-    lib().pm_gemm_force_config(cfg)
+    assert cfg == -1 or cfg in ops.GEMM_PIN_IDS, cfg
+    assert lib().pm_gemm_force_config(cfg) == 0
     for _ in range(3):
         ops.gemm(A, B, C, M, N, K, A.stride(0), B.stride(0), ldc, transA=bool(ta), transB=bool(tb), accum=bool(ta), split_k=0 if ta else 1)
     torch.cuda.synchronize()
