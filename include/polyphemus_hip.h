@@ -472,6 +472,77 @@ int pm_infill_tokens(const float* s_in /* [G,4,32] 0/1 */, const float* s_out /*
                      const int32_t* bar_forced /* [G] or NULL */, int32_t* scratch /* [PM_INFILL_SCRATCH(G)] */,
                      int32_t* status /* [5] */, pm_stream_t stream);
 
+/* ------------------------------------------------------------------ Note statistics
+ * What a batch of pieces held as note events contains, counted on the device, and a subset of its pieces: what "draw several
+ * takes of a latent and keep the best by a criterion" needs without a host loop over the notes.  The counts are the small
+ * integer reductions behind the objective measures of muspy.metrics (pitch range, pitches and pitch classes used, polyphony,
+ * empty beats, groove); the ratios are left to the caller.  Additive, same ABI version.
+ *
+ * notes [M,3] int32 (time, pitch, duration) and track_ptr [4B+1] int32 are the layout pm_tokens_from_notes reads; every
+ * track's range is clamped into [0, M] as there, so nothing outside notes[0:M] and track_ptr[0:4B+1] is read.
+ *
+ * pm_note_stats: with L = 32 n_bars, a row (t, p, d) of a track is COUNTED iff 0 <= t < L; other rows add to out_of_range and
+ * to nothing else.  A counted row is the note the encoder would see: pitch q = clamp(p, 0, 127), duration e = clamp(d, 1, 96),
+ * sounding over the steps [t, min(t + e, L)).  Rows need not be sorted and no output depends on their order.  All outputs are
+ * int32, one record per (piece, track) in track_ptr order, and every word is written on every call:
+ *   track       [4B,12], indexed by PM_NOTE_STAT_*:
+ *                 N_NOTES counted rows; N_ONSETS steps with at least one onset; PITCH_MIN lowest q (128 if no note);
+ *                 PITCH_MAX highest q (-1 if no note); N_PITCHES distinct q; N_PITCH_CLASSES distinct q mod 12;
+ *                 NOTE_STEPS the sum of the clipped lengths min(t + e, L) - t; SOUNDING_STEPS steps at which at least one
+ *                 note sounds; POLY_STEPS steps at which at least two sound; MAX_POLYPHONY the largest number of notes
+ *                 sounding at one step; MAX_CHORD the largest number of onsets at one step (above 14, pm_tokens_from_notes
+ *                 would drop some); OUT_OF_RANGE rows that were not counted.
+ *   pitch_class [4B,12]: counted rows per q mod 12.
+ *   onsets      [4B,n_bars]: bit s of word b is set iff a counted row has t = 32 b + s (bit 31 is the sign bit: the word is a
+ *               bit pattern).
+ *   sounding    [4B,n_bars]: the same layout for "at least one note sounds at this step".
+ * One launch, a wave per track and the four tracks of a piece per workgroup; the per-step counters (a difference array of the
+ * sounding count and the onset count, 2 L int32 per wave) live in LDS, so n_bars <= 64 (64 KB per workgroup).  Integer LDS
+ * adds, a wave scan over the steps and wave reductions: no global atomics, no workspace, no host read; two calls on the same
+ * input write the same bytes.  12 B are read per row, 96 + 8 n_bars B written per track.  Sums are int32 (NOTE_STEPS wraps
+ * beyond 2^31 - 1, more than 22 million notes of a track).
+ * PM_E_INVALID (before any launch): a NULL pointer (notes may be NULL when M == 0); B <= 0; n_bars outside [1, 64]; M < 0;
+ *   3 M, 4 B n_bars or 48 B >= 2^31; a pointer not 4-byte aligned; an output overlapping an input or another output.
+ *
+ * pm_notes_select: the pieces index[0..K) of the input, in that order, as notes / track_ptr / totals of their own.
+ *   index         [K] int32, K >= 1; entries are to lie in [0, B) and be distinct.  An entry out of range gives an empty piece
+ *                 (four equal out_track_ptr entries), and so does an entry that repeats an earlier one: the lowest position
+ *                 keeps the piece.  Both are counted, never followed.
+ *   out_track_ptr [4K+1]: the scan of the chosen tracks' clamped lengths; out_track_ptr[4K] = M'.
+ *   out_notes     [capacity,3]: the chosen rows, unchanged; nothing at or beyond row `capacity` is written and rows from M' on
+ *                 are left as they were.  With distinct entries and a track_ptr that does not decrease M' <= M.
+ *   out_totals    [2]: M', and the cells: rows whose time differs from the previous row of their track plus one per track that
+ *                 is not empty (for tracks sorted by time, the distinct (piece, track, time) triples).
+ *   status        [2]: entries out of range, entries that repeat an earlier one.
+ *   scratch       PM_SELECT_SCRATCH(B, K) int32: the first position of every input piece, four counts per chosen track.
+ * Five launches on the stream (first positions = INT_MAX, their integer minimum over the index, lengths and cells with a wave
+ * per chosen track, the scan by one workgroup, the rows), no host read; the minimum is the only atomic and does not depend on
+ * arrival order, so two calls on the same input write the same bytes.
+ * PM_E_INVALID (before any launch): a NULL pointer (notes may be NULL when M == 0, out_notes when capacity == 0); B <= 0,
+ *   K < 1, M < 0 or capacity < 0; 3 M, 3 capacity, 4 B + 1 or the scratch size >= 2^31; a pointer not 4-byte aligned; an output
+ *   or the scratch overlapping any other buffer (the inputs may share memory with each other). */
+#define PM_NOTE_STAT_N_NOTES 0
+#define PM_NOTE_STAT_N_ONSETS 1
+#define PM_NOTE_STAT_PITCH_MIN 2
+#define PM_NOTE_STAT_PITCH_MAX 3
+#define PM_NOTE_STAT_N_PITCHES 4
+#define PM_NOTE_STAT_N_PITCH_CLASSES 5
+#define PM_NOTE_STAT_NOTE_STEPS 6
+#define PM_NOTE_STAT_SOUNDING_STEPS 7
+#define PM_NOTE_STAT_POLY_STEPS 8
+#define PM_NOTE_STAT_MAX_POLYPHONY 9
+#define PM_NOTE_STAT_MAX_CHORD 10
+#define PM_NOTE_STAT_OUT_OF_RANGE 11
+#define PM_NOTE_STAT_FIELDS 12
+#define PM_SELECT_SCRATCH(B, K) ((int64_t)(B) + 16 * (int64_t)(K))
+int pm_note_stats(const int32_t* notes /* [M,3] time, pitch, duration */, const int32_t* track_ptr /* [4B+1] */, int32_t B,
+                  int32_t n_bars, int64_t M, int32_t* track /* [4B,12] */, int32_t* pitch_class /* [4B,12] */,
+                  int32_t* onsets /* [4B,n_bars] */, int32_t* sounding /* [4B,n_bars] */, pm_stream_t stream);
+int pm_notes_select(const int32_t* notes /* [M,3] */, const int32_t* track_ptr /* [4B+1] */, int32_t B, int64_t M,
+                    const int32_t* index /* [K] */, int32_t K, int32_t* out_notes /* [capacity,3] */, int64_t capacity,
+                    int32_t* out_track_ptr /* [4K+1] */, int32_t* out_totals /* [2] */,
+                    int32_t* scratch /* [PM_SELECT_SCRATCH(B, K)] */, int32_t* status /* [2] */, pm_stream_t stream);
+
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):
  *   A[n, r*d:(r+1)*d] = mean_{e: dst=n, type=r} keep_e * relu(x[src_e] * T[dist_e]) / (1-p)

@@ -5,7 +5,8 @@ Converting the pianoroll to MIDI (muspy) is outside the hot path and stays with 
 pieces as ordered note events instead (`NoteBatch`, csrc/notes.hip), which is what that conversion reads out of the pianoroll.
 The other direction has no entry point in the reference: `NoteBatch.from_lists` / `to_graph` (csrc/notes_in.hip) turn notes into the
 batch the encoder consumes, `encode_notes` and `vary_notes` encode a piece and decode around it, `infill_notes` regenerates the
-cells of a region (`region_mask`) and keeps the other notes (csrc/infill.hip)."""
+cells of a region (`region_mask`) and keeps the other notes (csrc/infill.hip).  `NoteBatch.stats` counts what the pieces hold on the
+device (`NoteStats`, csrc/stats.hip), `NoteBatch.select` takes a subset of them, `pick_takes` keeps the best of several takes."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -262,6 +263,143 @@ class NoteBatch:
         """The pieces as the `BarGraphBatch` the encoder consumes (`graphs.device_batch_from_notes`): two host reads."""
         from .graphs import device_batch_from_notes
         return device_batch_from_notes(self.notes, self.track_ptr, self.n_bars)
+
+    def stats(self, check: bool = False) -> "NoteStats":
+        """What the pieces hold, counted per (piece, track) on the device (`ops.note_stats`, csrc/stats.hip): one launch and
+        no host read, unless `check` asks for rows outside the piece to raise."""
+        track, pitch_class, onsets, sounding = ops.note_stats(self.notes, self.track_ptr, self.n_bars, check)
+        B = track.shape[0] // 4
+        return NoteStats(track.view(B, 4, -1), pitch_class.view(B, 4, 12), onsets.view(B, 4, -1), sounding.view(B, 4, -1),
+                         self.n_bars, self.resolution)
+
+    def select(self, index, check: bool = True) -> "NoteBatch":
+        """The pieces `index[0..K)` (an int32 or int64 tensor or a list; entries in [0, B), distinct) as a NoteBatch of their
+        own, in that order, copied on the device (`ops.notes_select`).  `check` costs one host read and raises ValueError on
+        an entry out of range or repeated; without it such an entry gives an empty piece.  `totals[1]` counts the cells as
+        `from_lists` does (the distinct (piece, track, time) of sorted tracks), not the model's active cells."""
+        notes, track_ptr, totals, _ = ops.notes_select(self.notes, self.track_ptr, index, check)
+        return NoteBatch(notes, track_ptr, totals, self.n_bars, self.resolution)
+
+
+MAJOR_SCALE = (0, 2, 4, 5, 7, 9, 11)
+
+
+@dataclass
+class NoteStats:
+    """The counts of `NoteBatch.stats()` (`ops.note_stats`, "Note statistics" in include/polyphemus_hip.h), int32 on the
+    device: `track` [B,4,12] (fields `ops.NOTE_STAT_FIELDS`: n_notes, n_onsets, pitch_min, pitch_max, n_pitches,
+    n_pitch_classes, note_steps, sounding_steps, poly_steps, max_polyphony, max_chord, out_of_range), `pitch_class` [B,4,12]
+    (notes per pitch mod 12), `onsets` and `sounding` [B,4,n_bars] (bit s of word b: step 32 b + s has an onset / a sounding
+    note).  A note is a row whose time lies inside the piece, with the pitch clamped to 0..127 and the duration to 1..96 and
+    cut at the end of the piece: what the encoder sees, which is where the measures below differ from `muspy.metrics` on
+    `to_muspy()` (muspy takes pitches and durations as they are and lets the last notes sound beyond the piece).  The methods
+    are torch ops on the device, float32 [B,4] unless noted, without a host read."""
+    track: torch.Tensor
+    pitch_class: torch.Tensor
+    onsets: torch.Tensor
+    sounding: torch.Tensor
+    n_bars: int
+    resolution: int = 8
+
+    def field(self, name: str) -> torch.Tensor:
+        """int32 [B,4]: one field of `track` by its name in `ops.NOTE_STAT_FIELDS`"""
+        return self.track[..., ops.NOTE_STAT_FIELDS.index(name)]
+
+    def polyphony(self) -> torch.Tensor:
+        """`muspy.metrics.polyphony`: the mean number of notes sounding over the steps at which any sounds, note_steps /
+        sounding_steps; 0 for a silent track (muspy: nan).  Durations are clamped and cut at the end of the piece."""
+        num, den = self.field("note_steps").float(), self.field("sounding_steps").float()
+        return torch.where(den > 0, num / den.clamp(min=1), torch.zeros_like(num))
+
+    def polyphony_rate(self) -> torch.Tensor:
+        """`muspy.metrics.polyphony_rate` with threshold 2: the share of the piece's 32 n_bars steps at which at least two
+        notes sound.  muspy divides by the length up to the end of the last note; here the piece's length is fixed."""
+        return self.field("poly_steps").float() / float(32 * self.n_bars)
+
+    def pitch_class_entropy(self) -> torch.Tensor:
+        """`muspy.metrics.pitch_class_entropy`: the Shannon entropy in bits of the notes' pitch-class histogram; 0 for a
+        track without notes (muspy: nan).  Pitches are clamped to 0..127 first."""
+        c = self.pitch_class.float()
+        p = c / c.sum(-1, keepdim=True).clamp(min=1)
+        return -(p * torch.log2(torch.where(p > 0, p, torch.ones_like(p)))).sum(-1)
+
+    def scale_consistency(self) -> torch.Tensor:
+        """`muspy.metrics.scale_consistency`: the largest share of notes inside one of the 12 transpositions of the major
+        scale (classes 0, 2, 4, 5, 7, 9, 11; the natural minor scales are the same 12 sets, which muspy walks a second time);
+        0 for a track without notes (muspy: nan)."""
+        c = self.pitch_class.float()
+        scales = torch.zeros(12, 12, dtype=c.dtype, device=c.device)
+        for root in range(12):
+            scales[root, [(root + k) % 12 for k in MAJOR_SCALE]] = 1.0
+        inside = (c.unsqueeze(-2) * scales).sum(-1).amax(-1)     # (sums of small integers: exact in fp32)
+        return inside / c.sum(-1).clamp(min=1)
+
+    def groove_consistency(self) -> torch.Tensor:
+        """`muspy.metrics.groove_consistency` with a measure of 32 steps: 1 minus the mean over neighbouring bars of the
+        Hamming distance of their onset patterns / 32; 1 when n_bars == 1 (muspy: nan).  muspy's last measure ends with the
+        last note; here every bar of the piece counts."""
+        if self.n_bars == 1:
+            return torch.ones(self.onsets.shape[:2], dtype=torch.float32, device=self.onsets.device)
+        diff = _popcount32(self.onsets[..., :-1] ^ self.onsets[..., 1:]).float()
+        return 1.0 - diff.sum(-1) / float(32 * (self.n_bars - 1))
+
+    def empty_beat_rate(self) -> torch.Tensor:
+        """`muspy.metrics.empty_beat_rate`, float32 [B]: the share of the piece's 4 n_bars beats (`resolution` steps each) in
+        which no track sounds.  muspy counts a beat as used when a note starts in it and stops at the last note's end; here a
+        beat is used while a note sounds in it, and all beats of the piece count."""
+        r = self.resolution
+        if not (ops._integer(r) and r >= 1 and 32 % r == 0):
+            raise ValueError(f"resolution must divide 32 (a bar's steps), got {r!r}")
+        any_track = self.sounding[:, 0] | self.sounding[:, 1] | self.sounding[:, 2] | self.sounding[:, 3]       # [B,n_bars]
+        shifts = torch.arange(0, 32, r, dtype=torch.int32, device=any_track.device)
+        mask = -1 if r == 32 else (1 << r) - 1
+        used = ((any_track.unsqueeze(-1) >> shifts) & mask) != 0                                                # [B,n_bars,32/r]
+        return 1.0 - used.float().mean(dim=(1, 2))
+
+
+def _popcount32(x: torch.Tensor) -> torch.Tensor:
+    """int32 -> the number of set bits of every word (the sign bit counts), by the parallel-sum identity"""
+    x = x.to(torch.int64) & 0xFFFFFFFF
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    x = (x + (x >> 4)) & 0x0F0F0F0F
+    return ((x * 0x01010101) & 0xFFFFFFFF) >> 24
+
+
+def pick_takes(vae, z, takes: int, key, **generate_notes_kwargs):
+    """Several takes of every latent, the best of each kept by a criterion, chosen on the device.  `z` is [B,d];
+    `z.repeat_interleave(takes, 0)` goes through ONE `generate_notes` call (rows that repeat a latent differ in their draws, so
+    sampling or `structure_rules` is what makes takes differ), `key(stats)` gets the `NoteStats` of the B * takes pieces and
+    returns a float tensor [B * takes] on their device, higher is better; NaN counts as -inf.  Of each group of `takes`
+    consecutive rows the best is kept, ties go to the lowest row.  `s_cond` (bar graphs) and `s_tensor_cond` [B,n_bars,4,32],
+    if given, are repeated as `z` is.  Returns (NoteBatch of B pieces, s_tensor [B,n_bars,4,32] of the winners, chosen int64 [B]:
+    the row of each winner among the B * takes).  No host read beyond `generate_notes`' own."""
+    if not (ops._integer(takes) and takes >= 1):
+        raise ValueError(f"takes must be an int >= 1, got {takes!r}")
+    if "return_tokens" in generate_notes_kwargs:
+        raise ValueError("return_tokens is not an argument of pick_takes: the tokens of the takes are not kept")
+    if not callable(key):
+        raise ValueError(f"key must be a callable NoteStats -> float tensor [B * takes], got {key!r}")
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[0] < 1:
+        raise ValueError(f"z must be a tensor [B,d] with B >= 1, got {type(z).__name__}"
+                         + (f" {tuple(z.shape)}" if isinstance(z, torch.Tensor) else ""))
+    takes, B = int(takes), z.shape[0]
+    kw = dict(generate_notes_kwargs)
+    s_cond, s_tensor_cond = kw.pop("s_cond", None), kw.pop("s_tensor_cond", None)
+    if s_tensor_cond is not None:
+        s_tensor_cond = s_tensor_cond.repeat_interleave(takes, 0)
+    if s_cond is not None:                                       # the bar graphs of the repeated structure
+        s_rep = s_cond.s_tensor.view(B, -1, 4, 32).bool().repeat_interleave(takes, 0)
+        s_cond = vae.decoder._structure_from_binary(s_rep)
+    batch, s_tensor = generate_notes(vae, z.repeat_interleave(takes, 0), s_cond, s_tensor_cond, **kw)
+    score = key(batch.stats())
+    if (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (B * takes,)
+            or score.device != batch.notes.device):
+        got = f"{score.dtype} {tuple(score.shape)} on {score.device}" if isinstance(score, torch.Tensor) else type(score).__name__
+        raise ValueError(f"key must return a float tensor [{B * takes}] on {batch.notes.device}, got {got}")
+    score = torch.nan_to_num(score.float(), nan=float("-inf"), posinf=float("inf"), neginf=float("-inf")).view(B, takes)
+    chosen = score.argmax(1) + takes * torch.arange(B, device=score.device)     # (argmax: the first of equal maxima)
+    return batch.select(chosen, check=False), s_tensor[chosen], chosen
 
 
 def generate_notes(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,

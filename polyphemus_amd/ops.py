@@ -500,6 +500,96 @@ def infill_tokens(s_in: torch.Tensor, s_out: torch.Tensor, region, tokens_in: to
     return status
 
 
+NOTE_STAT_FIELDS = ("n_notes", "n_onsets", "pitch_min", "pitch_max", "n_pitches", "n_pitch_classes", "note_steps",
+                    "sounding_steps", "poly_steps", "max_polyphony", "max_chord", "out_of_range")    # PM_NOTE_STAT_*
+MAX_STAT_BARS = 64
+
+
+def _note_batch_args(notes, track_ptr):
+    """The checks the readers of the `NoteBatch` layout share (`tokens_from_notes`' rules): `notes` int32 [M,3] and `track_ptr`
+    int32 [4B+1] tensors (ValueError), on one device (ValueError) that is a GPU (HipExtensionError).  `check_device` runs
+    last, so a caller puts its own argument checks between the two."""
+    for t, name in ((notes, "notes"), (track_ptr, "track_ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if notes.dtype != I32 or notes.dim() != 2 or notes.shape[1] != 3:
+        raise ValueError(f"notes must be int32 [M,3], got {notes.dtype} {tuple(notes.shape)}")
+    if track_ptr.dtype != I32 or track_ptr.dim() != 1 or track_ptr.shape[0] < 5 or track_ptr.shape[0] % 4 != 1:
+        raise ValueError(f"track_ptr must be int32 [4B+1] with B >= 1, got {track_ptr.dtype} {tuple(track_ptr.shape)}")
+
+    def check_device():
+        for t, name in ((notes, "notes"), (track_ptr, "track_ptr")):
+            if not t.is_cuda:
+                raise HipExtensionError(f"{name} lives on {t.device}: the HIP path needs device tensors (no CPU fallback)")
+        if track_ptr.device != notes.device:
+            raise ValueError(f"track_ptr lives on {track_ptr.device}, notes on {notes.device}")
+    return check_device
+
+
+def note_stats(notes: torch.Tensor, track_ptr: torch.Tensor, n_bars: int, check: bool = False):
+    """`pm_note_stats` ("Note statistics" in include/polyphemus_hip.h): what the pieces of the `NoteBatch` layout (`notes` int32
+    [M,3], `track_ptr` int32 [4B+1], `n_bars` bars of 32 steps, at most 64) hold, counted per (piece, track) on the device in
+    one launch.  A row is counted iff its time lies inside the piece, as the note the encoder would see (pitch clamped to
+    0..127, duration to 1..96, cut at the end of the piece).  Returns four int32 tensors: track [4B,12] (NOTE_STAT_FIELDS),
+    pitch_class [4B,12], onsets [4B,n_bars] and sounding [4B,n_bars] (bit s of word b: step 32 b + s).  Nothing is read back
+    unless `check` is set: then rows outside the piece (`out_of_range`) raise ValueError with their count."""
+    check_device = _note_batch_args(notes, track_ptr)
+    if not (_integer(n_bars) and 1 <= n_bars <= MAX_STAT_BARS):
+        raise ValueError(f"n_bars must be an int in [1, {MAX_STAT_BARS}], got {n_bars!r}")
+    check_device()
+    notes, track_ptr, n_bars = notes.contiguous(), track_ptr.contiguous(), int(n_bars)
+    B, M, dev = track_ptr.shape[0] // 4, notes.shape[0], notes.device
+    nf = len(NOTE_STAT_FIELDS)
+    track, pitch_class = torch.empty(4 * B, nf, dtype=I32, device=dev), torch.empty(4 * B, 12, dtype=I32, device=dev)
+    onsets, sounding = torch.empty(4 * B, n_bars, dtype=I32, device=dev), torch.empty(4 * B, n_bars, dtype=I32, device=dev)
+    call("pm_note_stats", ptr(notes) if M else None, ptr(track_ptr), B, n_bars, M, ptr(track), ptr(pitch_class), ptr(onsets),
+         ptr(sounding), stream())
+    if check:
+        bad = int(track[:, nf - 1].sum().item())                 # the one host read
+        if bad:
+            raise ValueError(f"notes: {bad} rows out of range (a time outside [0, {32 * n_bars}))")
+    return track, pitch_class, onsets, sounding
+
+
+def notes_select(notes: torch.Tensor, track_ptr: torch.Tensor, index, check: bool = True):
+    """`pm_notes_select` ("Note statistics" in include/polyphemus_hip.h): the pieces `index[0..K)` of the `NoteBatch` layout
+    (`notes` int32 [M,3], `track_ptr` int32 [4B+1]), in that order, without leaving the device.  `index` is an int32 or int64
+    tensor [K] or a list of ints, K >= 1, its entries in [0, B) and distinct.  Returns (notes int32 [M,3], track_ptr int32
+    [4K+1], totals int32 [2] = rows M', cells; status int32 [2] = entries out of range, entries that repeat an earlier one):
+    the new notes buffer has the input's size, which distinct entries cannot exceed, and rows from M' on are not written.  An
+    entry that is counted in `status` gives an empty piece.  `check` reads `status` back (one host sync) and raises ValueError
+    with the counts; without it nothing is read back."""
+    check_device = _note_batch_args(notes, track_ptr)
+    if isinstance(index, torch.Tensor):
+        if index.dtype not in (I32, I64) or index.dim() != 1 or index.shape[0] < 1:
+            raise ValueError(f"index must be an int32 or int64 tensor [K] with K >= 1, got {index.dtype} {tuple(index.shape)}")
+    elif isinstance(index, (list, tuple)) and len(index) >= 1 and all(_integer(v) and -(1 << 31) <= v < (1 << 31) for v in index):
+        index = torch.tensor([int(v) for v in index], dtype=I32)
+        if notes.is_cuda:
+            index = index.to(notes.device)
+    else:
+        raise ValueError(f"index must be an int32 or int64 tensor [K] or a non-empty list of ints, got {index!r}")
+    check_device()
+    if index.device != notes.device:
+        raise ValueError(f"index lives on {index.device}, notes on {notes.device}")
+    B, M, K, dev = track_ptr.shape[0] // 4, notes.shape[0], index.shape[0], notes.device
+    if index.dtype == I64:                                       # (an entry beyond int32 is out of range either way)
+        index = index.clamp(-1, B).to(I32)
+    notes, track_ptr, index = notes.contiguous(), track_ptr.contiguous(), index.contiguous()
+    out = torch.empty(M, 3, dtype=I32, device=dev)
+    out_ptr = torch.empty(4 * K + 1, dtype=I32, device=dev)
+    n_scratch = B + 16 * K                                       # PM_SELECT_SCRATCH(B, K)
+    scratch, totals, status = torch.empty(n_scratch + 4, dtype=I32, device=dev).split([n_scratch, 2, 2])
+    call("pm_notes_select", ptr(notes) if M else None, ptr(track_ptr), B, M, ptr(index), K, ptr(out) if M else None, M,
+         ptr(out_ptr), ptr(totals), ptr(scratch), ptr(status), stream())
+    totals, status = totals.clone(), status.clone()              # (lets the scratch go)
+    if check:
+        out_of_range, repeated = status.tolist()                 # the one host read
+        if out_of_range or repeated:
+            raise ValueError(f"index: {out_of_range} entries outside [0, {B}), {repeated} entries that repeat an earlier one")
+    return out, out_ptr, totals, status
+
+
 def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
                      c_logits=None, node_track=None):
     """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
