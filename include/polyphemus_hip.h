@@ -543,6 +543,61 @@ int pm_notes_select(const int32_t* notes /* [M,3] */, const int32_t* track_ptr /
                     int32_t* out_track_ptr /* [4K+1] */, int32_t* out_totals /* [2] */,
                     int32_t* scratch /* [PM_SELECT_SCRATCH(B, K)] */, int32_t* status /* [2] */, pm_stream_t stream);
 
+/* ------------------------------------------------------------------ Note splicing
+ * Bar ranges of the pieces of a batch copied into bar ranges of new pieces, on the device: what cuts songs into the model's
+ * windows (the reference's sliding window, preprocess.py:165-205: the window by onset time, the two silence filters, the
+ * transposition) and what puts windows behind each other in time again.  Additive, same ABI version.
+ *
+ * notes [M,3] int32 (time, pitch, duration) and track_ptr [4B+1] int32 are the layout pm_tokens_from_notes reads, pieces of
+ * src_bars bars; every track's range is clamped into [0, M] as there, so nothing outside notes[0:M] and track_ptr[0:4B+1] is
+ * read.  Source tracks need not be sorted by time.
+ *
+ * pm_notes_splice: K output pieces of out_bars bars.
+ *   segments      [S,4] int32, a row (src_piece, src_bar, out_bar, bars); seg_ptr [K+1] int32: output piece j is made of
+ *                 segments[seg_ptr[j] : seg_ptr[j+1]], in that order; none gives a silent piece.
+ *   rows          track k of output piece j holds, segment by segment, the rows of track k of src_piece whose time t lies in
+ *                 [32 src_bar, 32 (src_bar + bars)), in the source's row order, as (t - 32 src_bar + 32 out_bar, pitch,
+ *                 duration): a note goes by its onset alone and is never cut (the slice of subsong_content, preprocess.py:171).
+ *                 The order is part of the result: it decides the slots pm_tokens_from_notes assigns and which notes past the
+ *                 14th of a timestep are dropped.
+ *   followed      a segment is followed iff 0 <= src_piece < B, bars >= 1, src_bar >= 0, src_bar + bars <= src_bars,
+ *                 out_bar >= the end (out_bar + bars) of the last followed segment of the same output piece, 0 in front of
+ *                 the first, and out_bar + bars <= out_bars.  Any other copies nothing and is counted.  seg_ptr is clamped as
+ *                 track_ptr is (0 <= lo <= hi <= S); an entry outside [0, S] or below the entry before it is counted.
+ *   shift         NULL or [K] int32: the pitches of tracks 1..3 (never the drums) of output piece j become
+ *                 clamp(clamp(pitch, 0, 127) + shift[j], 0, 127), preprocess.py:196-205 on the pitch tokens.  NULL leaves every
+ *                 pitch as it is.
+ *   silence_rule  0 / 1; 1 needs out_bars <= 64.  With act[k][b] = "track k of the output piece has a row in bar b":
+ *                 out_bars > 1: keep = 0 if a bar is silent in all four tracks, or if `1 in np.diff(np.where(act == 0)[1])`
+ *                 (preprocess.py:182): walking the silent (track, bar) pairs in row-major order, two neighbours whose bars are
+ *                 c and c + 1.  That is two consecutive silent bars of one track, and also the last silent bar c of one track
+ *                 followed by the first silent bar c + 1 of the next track that has any; out_bars == 1: keep = 0 iff all four
+ *                 tracks are silent; else keep = 1.  Pieces with keep = 0 are written like the others; the caller drops them
+ *                 (pm_notes_select).  With silence_rule = 0 keep is all ones.
+ *   out_notes     [capacity,3]; nothing at or beyond row `capacity` is written, rows from M' on are left as they were.
+ *   out_track_ptr [4K+1], the scan of the tracks' rows; out_track_ptr[4K] = M'.
+ *   out_totals    [2]: M' (the rows needed, whatever the capacity), and the cells as pm_notes_select counts them: rows whose
+ *                 time differs from the previous row of their track plus one per track that is not empty.
+ *   keep          [K] 0 / 1.
+ *   status        [4]: segments not followed; seg_ptr entries counted; max(M' - capacity, 0); 0.
+ *   scratch       PM_SPLICE_SCRATCH(K, S) int32: four counts and the 64-bit mask of bars per output track (nothing is kept
+ *                 per segment: the launch that copies walks the segments again with a running base).
+ * Three launches on the stream: the counts with a wave per (output piece, track), which scans the source track once per
+ * segment; the scan by one workgroup with totals, status and keep; the rows with the same shape, order kept by a ballot and
+ * the popcount of the lanes below.  No host read, no atomics: two calls on the same input write the same bytes.  Per segment
+ * and track 4 B per source row are read by the count and 4 to 12 B by the copy; 12 B are written per row that goes along.
+ * PM_E_INVALID (before any launch): a NULL pointer (notes may be NULL when M == 0, segments when S == 0, out_notes when
+ *   capacity == 0, shift always); B <= 0, K < 1, S < 0, M < 0, capacity < 0, src_bars < 1 or out_bars < 1; silence_rule not
+ *   0 / 1, or 1 with out_bars > 64; 3 M, 3 capacity, 4 B + 1, 4 S, 32 src_bars, 32 out_bars or the scratch size >= 2^31; a
+ *   pointer not 4-byte aligned; an output or the scratch overlapping any other buffer (the inputs may share memory). */
+#define PM_SPLICE_SCRATCH(K, S) (24 * (int64_t)(K) + 0 * (int64_t)(S))
+int pm_notes_splice(const int32_t* notes /* [M,3] */, const int32_t* track_ptr /* [4B+1] */, int32_t B, int32_t src_bars,
+                    int64_t M, const int32_t* segments /* [S,4] */, int32_t S, const int32_t* seg_ptr /* [K+1] */, int32_t K,
+                    int32_t out_bars, const int32_t* shift /* [K] or NULL */, int32_t silence_rule,
+                    int32_t* out_notes /* [capacity,3] */, int64_t capacity, int32_t* out_track_ptr /* [4K+1] */,
+                    int32_t* out_totals /* [2] */, int32_t* keep /* [K] */,
+                    int32_t* scratch /* [PM_SPLICE_SCRATCH(K, S)] */, int32_t* status /* [4] */, pm_stream_t stream);
+
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):
  *   A[n, r*d:(r+1)*d] = mean_{e: dst=n, type=r} keep_e * relu(x[src_e] * T[dist_e]) / (1-p)

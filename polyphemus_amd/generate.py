@@ -6,7 +6,10 @@ pieces as ordered note events instead (`NoteBatch`, csrc/notes.hip), which is wh
 The other direction has no entry point in the reference: `NoteBatch.from_lists` / `to_graph` (csrc/notes_in.hip) turn notes into the
 batch the encoder consumes, `encode_notes` and `vary_notes` encode a piece and decode around it, `infill_notes` regenerates the
 cells of a region (`region_mask`) and keeps the other notes (csrc/infill.hip).  `NoteBatch.stats` counts what the pieces hold on the
-device (`NoteStats`, csrc/stats.hip), `NoteBatch.select` takes a subset of them, `pick_takes` keeps the best of several takes."""
+device (`NoteStats`, csrc/stats.hip), `NoteBatch.select` takes a subset of them, `pick_takes` keeps the best of several takes.
+`NoteBatch.windows` cuts songs into the model's windows as the reference's preprocessing does (preprocess.py:165-205) and
+`NoteBatch.join` puts windows behind each other again (csrc/splice.hip); `encode_song` and `vary_song` take a whole song through
+the VAE on them."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -280,6 +283,162 @@ class NoteBatch:
         notes, track_ptr, totals, _ = ops.notes_select(self.notes, self.track_ptr, index, check)
         return NoteBatch(notes, track_ptr, totals, self.n_bars, self.resolution)
 
+    def windows(self, n_bars: int, stride: int = 1, song_bars=None, filter=None, transpose=None, seed=None,
+                check: bool = True):
+        """Songs cut into windows of `n_bars` bars, on the device (`ops.notes_splice`, csrc/splice.hip): the reference's
+        sliding window (preprocess.py:165-205).  The windows of song b start at the bars 0, `stride`, ... while
+        start + n_bars <= song_bars[b], songs in order; a note goes into a window by its onset and is never cut, the order of
+        a track's rows is kept.  Returns (NoteBatch of the windows, WindowIndex: which song and bar each came from, the shift
+        it got).  The notes buffer holds M ceil(n_bars / stride) rows, a bound that needs no host read.
+        `song_bars`: the bars of every song, at most `self.n_bars`, which is the default.  A list is read on the host, and the
+        result holds exactly the windows that fit.  A tensor [B] is not read: the result then holds
+        (self.n_bars - n_bars) // stride + 1 pieces per song, and those that do not fit into their song are silent and have
+        `song` = -1 in the index.
+        `filter="reference"` drops the windows the reference's silence rules reject (preprocess.py:176-194; n_bars <= 64):
+        the rule is applied on the device, but how many windows stay sizes the result, so this is the one place where a host
+        read is inherent.  ValueError when none stays.
+        `transpose`: None, an int, an int tensor [K] (a shift per window, in the order of the result before the filter), or
+        "random": `torch.randint(-5, 7)` on the device from a generator seeded with `seed` (None: the device's global one),
+        preprocess.py:198.  Tracks 1..3 get clamp(clamp(pitch, 0, 127) + shift, 0, 127), the drums stay.
+        `check` costs one host read and raises ValueError if the kernel counted anything it did not follow."""
+        if not (ops._integer(n_bars) and n_bars >= 1):
+            raise ValueError(f"n_bars must be an int >= 1, got {n_bars!r}")
+        if not (ops._integer(stride) and stride >= 1):
+            raise ValueError(f"stride must be an int >= 1, got {stride!r}")
+        if filter not in (None, "reference"):
+            raise ValueError(f"filter must be None or 'reference', got {filter!r}")
+        if filter is not None and n_bars > ops.MAX_RULE_BARS:
+            raise ValueError(f"filter='reference' needs n_bars <= {ops.MAX_RULE_BARS}, got {n_bars}")
+        ops.check_sampling_args(seed=seed)
+        check_device = ops._note_batch_args(self.notes, self.track_ptr)
+        if not (ops._integer(self.n_bars) and self.n_bars >= 1):
+            raise ValueError(f"the batch's n_bars must be an int >= 1, got {self.n_bars!r}")
+        n_bars, stride, B, M = int(n_bars), int(stride), self.track_ptr.shape[0] // 4, self.notes.shape[0]
+        per = (self.n_bars - n_bars) // stride + 1 if n_bars <= self.n_bars else 0       # windows of a whole song
+        counts = None                                                                 # windows per song, where the host knows
+        if song_bars is None:
+            counts = [per] * B
+        elif isinstance(song_bars, (list, tuple)):
+            if len(song_bars) != B or not all(ops._integer(v) and 0 <= v <= self.n_bars for v in song_bars):
+                raise ValueError(f"song_bars must hold {B} ints in [0, {self.n_bars}], got {song_bars!r}")
+            counts = [(int(v) - n_bars) // stride + 1 if v >= n_bars else 0 for v in song_bars]
+        elif not (isinstance(song_bars, torch.Tensor) and song_bars.dtype in (torch.int32, torch.int64) and tuple(song_bars.shape) == (B,)):
+            raise ValueError(f"song_bars must be None, a list of {B} ints or an int32 / int64 tensor [{B}], got {song_bars!r}")
+        K = sum(counts) if counts is not None else B * per
+        if K < 1:
+            raise ValueError(f"no window of {n_bars} bars fits into songs of {self.n_bars} bars" + (f" (song_bars = {song_bars!r})" if counts else ""))
+        if isinstance(transpose, torch.Tensor):
+            if transpose.dtype not in (torch.int32, torch.int64) or tuple(transpose.shape) != (K,):
+                raise ValueError(f"transpose must be an int tensor [K = {K}], got {transpose.dtype} {tuple(transpose.shape)}")
+        elif not (transpose is None or transpose == "random" or (ops._integer(transpose) and -127 <= transpose <= 127)):
+            raise ValueError(f"transpose must be None, an int in [-127, 127], an int tensor [K = {K}] or 'random', got {transpose!r}")
+        check_device()
+        dev = self.notes.device
+        for t, name in ((song_bars, "song_bars"), (transpose, "transpose")):
+            if isinstance(t, torch.Tensor) and t.device != dev:
+                raise ValueError(f"{name} lives on {t.device}, notes on {dev}")
+        arange = lambda n: torch.arange(n, dtype=torch.int64, device=dev)
+        if counts is not None:                                   # every window fits: one segment each, in place
+            if song_bars is None:
+                song, start = arange(B).repeat_interleave(per), arange(per).repeat(B) * stride
+            else:
+                c = torch.tensor(counts, dtype=torch.int64).to(dev)
+                song = torch.repeat_interleave(arange(B), c, output_size=K)
+                start = (arange(K) - (c.cumsum(0) - c)[song]) * stride
+            seg_ptr = arange(K + 1)
+            rows = torch.stack([song, start, torch.zeros_like(song), torch.full_like(song, n_bars)], 1)
+        else:                                                    # the segments of the windows that fit first, in order
+            song, start = arange(B).repeat_interleave(per), arange(per).repeat(B) * stride
+            fits = start + n_bars <= song_bars.to(torch.int64).clamp(0, self.n_bars)[song]
+            order = torch.argsort((~fits).to(torch.int8), stable=True)
+            rows = torch.stack([song, start, torch.zeros_like(song), torch.full_like(song, n_bars)], 1)[order]
+            seg_ptr = torch.cat([fits.new_zeros(1, dtype=torch.int64), fits.cumsum(0)])
+            song = torch.where(fits, song, torch.full_like(song, -1))
+        if transpose is None:
+            shift, used = None, torch.zeros(K, dtype=torch.int32, device=dev)
+        elif isinstance(transpose, torch.Tensor):
+            shift = used = transpose.clamp(-128, 128).to(torch.int32)
+        elif transpose == "random":
+            gen = None if seed is None else torch.Generator(device=dev).manual_seed(int(seed))
+            shift = used = torch.randint(-5, 7, (K,), generator=gen, device=dev, dtype=torch.int32)
+        else:
+            shift = used = torch.full((K,), int(transpose), dtype=torch.int32, device=dev)
+        cap = M * (-(-n_bars // stride))
+        notes, track_ptr, totals, keep, _ = ops.notes_splice(self.notes, self.track_ptr, self.n_bars, rows.to(torch.int32),
+                                                             seg_ptr.to(torch.int32), n_bars, shift, filter is not None, cap, check)
+        out = NoteBatch(notes, track_ptr, totals, n_bars, self.resolution)
+        index = WindowIndex(song.to(torch.int32), start.to(torch.int32), used)
+        if filter is not None:
+            kept = keep.nonzero().flatten()                      # the host read that sizes the result
+            if kept.numel() == 0:
+                raise ValueError(f"filter='reference' rejects all {K} windows")
+            out = out.select(kept, check=False)
+            index = WindowIndex(index.song[kept], index.start[kept], index.shift[kept])
+        return out, index
+
+    def join(self, index, hop_bars=None, check: bool = True) -> "NoteBatch":
+        """Pieces put behind each other in time, on the device (`ops.notes_splice`): the inverse of `windows`.  `index` is
+        int [K,G], a tensor or nested lists: output piece j is made of the pieces index[j, 0..G) of this batch, -1 standing
+        for a silent window.  With W = `self.n_bars` and `hop_bars` in [1, W] (W by default) an output piece has
+        hop (G - 1) + W bars: window g gives its first `hop` bars from bar g hop on, the last window all W of them.  The
+        entries that are not -1 must lie in [0, B) and be distinct, which is what bounds the result by the input's rows;
+        `check` costs one host read and raises ValueError otherwise.  Without it an entry out of range gives silence and
+        the rows that repeated entries push beyond the buffer are not written."""
+        W = self.n_bars
+        hop = W if hop_bars is None else hop_bars
+        if not (ops._integer(W) and W >= 1):
+            raise ValueError(f"the batch's n_bars must be an int >= 1, got {W!r}")
+        if not (ops._integer(hop) and 1 <= hop <= W):
+            raise ValueError(f"hop_bars must be an int in [1, {W}], got {hop_bars!r}")
+        check_device = ops._note_batch_args(self.notes, self.track_ptr)
+        if isinstance(index, torch.Tensor):
+            if index.dtype not in (torch.int32, torch.int64) or index.dim() != 2 or index.numel() == 0:
+                raise ValueError(f"index must be an int32 or int64 tensor [K,G] with K, G >= 1, got {index.dtype} {tuple(index.shape)}")
+        elif (isinstance(index, (list, tuple)) and len(index) >= 1 and all(isinstance(r, (list, tuple)) and len(r) >= 1 for r in index)
+              and len({len(r) for r in index}) == 1 and all(ops._integer(v) and -(1 << 31) <= v < (1 << 31) for r in index for v in r)):
+            index = torch.tensor([[int(v) for v in r] for r in index], dtype=torch.int64)
+            if self.notes.is_cuda:
+                index = index.to(self.notes.device)
+        else:
+            raise ValueError(f"index must be an int tensor [K,G] or K lists of G ints, K, G >= 1, got {index!r}")
+        K, G = index.shape
+        out_bars = int(hop) * (G - 1) + W
+        if out_bars > 0x7fffffff // 32 or K * G > 0x7fffffff // 4:
+            raise ValueError(f"index [{K},{G}] gives pieces of {out_bars} bars: too many")
+        check_device()
+        dev = self.notes.device
+        if index.device != dev:
+            raise ValueError(f"index lives on {index.device}, notes on {dev}")
+        B = self.track_ptr.shape[0] // 4
+        flat = index.reshape(-1).to(torch.int64).clamp(-2, B)    # (an entry beyond int32 is out of range either way)
+        used = flat != -1
+        g = torch.arange(G, dtype=torch.int64, device=dev).repeat(K)
+        bars = torch.where(g == G - 1, torch.full_like(g, W), torch.full_like(g, int(hop)))
+        order = torch.argsort((~used).to(torch.int8), stable=True)                   # the silent windows have no segment
+        rows = torch.stack([flat, torch.zeros_like(g), g * int(hop), bars], 1)[order].to(torch.int32)
+        seg_ptr = torch.cat([used.new_zeros(1, dtype=torch.int64), used.view(K, G).sum(1).cumsum(0)]).to(torch.int32)
+        notes, track_ptr, totals, _, status = ops.notes_splice(self.notes, self.track_ptr, W, rows, seg_ptr, out_bars, check=False)
+        if check:
+            inside = (flat >= 0) & (flat < B)
+            seen = torch.zeros(B + 1, dtype=torch.int64, device=dev).scatter_add_(0, torch.where(inside, flat, torch.full_like(flat, B)),
+                                                                                   torch.ones_like(flat))
+            repeated = (seen[:B] - 1).clamp(min=0).sum().view(1)
+            outside, _, excess, _, repeated = torch.cat([status.to(torch.int64), repeated]).tolist()     # the one host read
+            if outside or repeated or excess:
+                raise ValueError(f"index: {outside} entries outside [0, {B}) that are not -1, {repeated} entries that repeat an "
+                                 f"earlier one ({excess} rows beyond the buffer)")
+        return NoteBatch(notes, track_ptr, totals, out_bars, self.resolution)
+
+
+@dataclass
+class WindowIndex:
+    """Where the pieces `NoteBatch.windows` returned come from, int32 [K] tensors on the device, aligned with the pieces:
+    `song` (the piece of the input; -1 for a window that did not fit into a song whose length was given as a tensor), `start`
+    (its first bar there) and `shift` (the semitones tracks 1..3 were transposed by, 0 without `transpose`)."""
+    song: torch.Tensor
+    start: torch.Tensor
+    shift: torch.Tensor
+
 
 MAJOR_SCALE = (0, 2, 4, 5, 7, 9, 11)
 
@@ -471,6 +630,49 @@ def vary_notes(vae, batch, strength=1.0, keep_structure=False, seed=None, return
         s_cond, s_tensor_cond = graph, graph.s_tensor.view(-1, batch.n_bars, 4, 32).bool()
     out = generate_notes(vae, z, s_cond, s_tensor_cond, seed=seed, **generate_notes_kwargs)
     return out + (z,) if return_z else out
+
+
+def _song_windows(vae, song):
+    """(the windows of `song` as a NoteBatch of the model's n_bars = W, B, windows per song S): W bars each, one behind the
+    other.  A song whose length is no multiple of W counts as padded with silence up to the next one: `n_bars` is a label on
+    the layout, so the padding moves nothing.  No host read."""
+    if not isinstance(song, NoteBatch):
+        raise ValueError(f"song must be a NoteBatch, got {type(song).__name__}")
+    W = vae.cfg["n_bars"]
+    if not (ops._integer(song.n_bars) and song.n_bars >= 1):
+        raise ValueError(f"song.n_bars must be an int >= 1, got {song.n_bars!r}")
+    S = -(-song.n_bars // W)
+    padded = NoteBatch(song.notes, song.track_ptr, song.totals, S * W, song.resolution)
+    wins, _ = padded.windows(W, stride=W, check=False)
+    return wins, song.track_ptr.shape[0] // 4, S
+
+
+def encode_song(vae, song):
+    """The latents of whole songs: `song` (a `NoteBatch` of B songs of any length) is cut into the S = ceil(n_bars / W)
+    windows of the model's W bars on the device (`NoteBatch.windows(W, stride=W)`) and every window is encoded
+    (`encode_notes`).  Returns (mu, log_var) [B,S,d].  A last window that the song fills only partly is silent behind the
+    song's end."""
+    wins, B, S = _song_windows(vae, song)
+    mu, log_var = encode_notes(vae, wins)
+    return mu.reshape(B, S, -1), log_var.reshape(B, S, -1)
+
+
+def vary_song(vae, song, strength=1.0, keep_structure=False, seed=None, **generate_notes_kwargs):
+    """Variations of whole songs: `song` is cut into windows of the model's W bars, the windows go through `vary_notes`
+    as one batch (its arguments, `strength=0` is the reconstruction) and come back behind each other (`NoteBatch.join`) as a
+    NoteBatch of B songs of W ceil(n_bars / W) bars.  Cutting and joining happen on the device and read nothing back, so
+    the host reads are those of `vary_notes`."""
+    for k in ("return_tokens", "return_z"):
+        if k in generate_notes_kwargs:
+            raise ValueError(f"{k} is not an argument of vary_song: the windows' tokens and latents are not kept")
+    if not isinstance(song, NoteBatch):
+        raise ValueError(f"song must be a NoteBatch, got {type(song).__name__}")
+    if not (ops._real(strength) and np.isfinite(strength) and strength >= 0):
+        raise ValueError(f"strength must be a finite number >= 0, got {strength!r}")
+    wins, B, S = _song_windows(vae, song)
+    varied = vary_notes(vae, wins, strength, keep_structure, seed, **generate_notes_kwargs)[0]
+    index = torch.arange(B * S, dtype=torch.int32, device=varied.notes.device).view(B, S)
+    return varied.join(index, check=False)
 
 
 def region_mask(n_bars: int, tracks=None, bars=None, steps=None) -> np.ndarray:

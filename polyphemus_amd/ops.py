@@ -590,6 +590,70 @@ def notes_select(notes: torch.Tensor, track_ptr: torch.Tensor, index, check: boo
     return out, out_ptr, totals, status
 
 
+MAX_RULE_BARS = 64
+
+
+def notes_splice(notes: torch.Tensor, track_ptr: torch.Tensor, src_bars: int, segments: torch.Tensor, seg_ptr: torch.Tensor,
+                 out_bars: int, shift: Optional[torch.Tensor] = None, silence_rule: bool = False, capacity: Optional[int] = None,
+                 check: bool = True):
+    """`pm_notes_splice` ("Note splicing" in include/polyphemus_hip.h): bar ranges of the pieces of the `NoteBatch` layout
+    (`notes` int32 [M,3], `track_ptr` int32 [4B+1], pieces of `src_bars` bars) copied into bar ranges of K new pieces of
+    `out_bars` bars, without leaving the device.  `segments` int32 [S,4] holds rows (src_piece, src_bar, out_bar, bars) and
+    `seg_ptr` int32 [K+1] the segments of every output piece; a row goes along by its onset, rebased, in the source's order.
+    `shift` int32 [K] transposes the tracks 1..3 of every output piece (pitches clamped to 0..127 before and after), None
+    leaves the pitches alone; `silence_rule` asks for the reference's silence filters (out_bars <= 64) in `keep`; `capacity`
+    is the rows of the new notes buffer, M by default.  Returns (notes int32 [capacity,3], track_ptr int32 [4K+1], totals
+    int32 [2] = rows needed, cells; keep int32 [K]; status int32 [4] = segments not followed, bad seg_ptr entries, rows beyond
+    the capacity, 0).  `check` reads `status` back (one host sync) and raises ValueError with the counts; without it
+    nothing is read back and what is counted was not followed."""
+    check_device = _note_batch_args(notes, track_ptr)
+    if not (_integer(src_bars) and 1 <= src_bars <= 0x7fffffff // 32):
+        raise ValueError(f"src_bars must be an int >= 1, got {src_bars!r}")
+    if not (_integer(out_bars) and 1 <= out_bars <= 0x7fffffff // 32):
+        raise ValueError(f"out_bars must be an int >= 1, got {out_bars!r}")
+    if not isinstance(segments, torch.Tensor) or segments.dtype != I32 or segments.dim() != 2 or segments.shape[1] != 4:
+        raise ValueError("segments must be an int32 tensor [S,4], got "
+                         + (f"{segments.dtype} {tuple(segments.shape)}" if isinstance(segments, torch.Tensor) else type(segments).__name__))
+    if not isinstance(seg_ptr, torch.Tensor) or seg_ptr.dtype != I32 or seg_ptr.dim() != 1 or seg_ptr.shape[0] < 2:
+        raise ValueError("seg_ptr must be an int32 tensor [K+1] with K >= 1, got "
+                         + (f"{seg_ptr.dtype} {tuple(seg_ptr.shape)}" if isinstance(seg_ptr, torch.Tensor) else type(seg_ptr).__name__))
+    K, S, M = seg_ptr.shape[0] - 1, segments.shape[0], notes.shape[0]
+    if shift is not None and not (isinstance(shift, torch.Tensor) and shift.dtype == I32 and tuple(shift.shape) == (K,)):
+        raise ValueError(f"shift must be None or an int32 tensor [K = {K}], got "
+                         + (f"{shift.dtype} {tuple(shift.shape)}" if isinstance(shift, torch.Tensor) else type(shift).__name__))
+    if not isinstance(silence_rule, (bool, np.bool_)):
+        raise ValueError(f"silence_rule must be a bool, got {silence_rule!r}")
+    if silence_rule and out_bars > MAX_RULE_BARS:
+        raise ValueError(f"silence_rule needs out_bars <= {MAX_RULE_BARS}, got {out_bars}")
+    if capacity is None:
+        capacity = M
+    if not (_integer(capacity) and 0 <= capacity <= 0x7fffffff // 3):
+        raise ValueError(f"capacity must be an int in [0, {0x7fffffff // 3}], got {capacity!r}")
+    check_device()
+    for t, name in ((segments, "segments"), (seg_ptr, "seg_ptr"), (shift, "shift")):
+        if t is not None and t.device != notes.device:
+            raise ValueError(f"{name} lives on {t.device}, notes on {notes.device}")
+    B, cap, dev = track_ptr.shape[0] // 4, int(capacity), notes.device
+    notes, track_ptr, segments, seg_ptr = notes.contiguous(), track_ptr.contiguous(), segments.contiguous(), seg_ptr.contiguous()
+    shift = None if shift is None else shift.contiguous()
+    out = torch.empty(cap, 3, dtype=I32, device=dev)
+    out_ptr, keep = torch.empty(4 * K + 1, dtype=I32, device=dev), torch.empty(K, dtype=I32, device=dev)
+    n_scratch = 24 * K                                           # PM_SPLICE_SCRATCH(K, S)
+    scratch, totals, status = torch.empty(n_scratch + 6, dtype=I32, device=dev).split([n_scratch, 2, 4])
+    call("pm_notes_splice", ptr(notes) if M else None, ptr(track_ptr), B, int(src_bars), M, ptr(segments) if S else None, S,
+         ptr(seg_ptr), K, int(out_bars), ptr(shift), int(bool(silence_rule)), ptr(out) if cap else None, cap, ptr(out_ptr),
+         ptr(totals), ptr(keep), ptr(scratch), ptr(status), stream())
+    totals, status = totals.clone(), status.clone()              # (lets the scratch go)
+    if check:
+        bad_seg, bad_ptr, excess, _ = status.tolist()            # the one host read
+        if bad_seg or bad_ptr or excess:
+            raise ValueError(f"segments: {bad_seg} not followed (a piece outside [0, {B}), a bar range outside the source's "
+                             f"{src_bars} or the output's {out_bars} bars, or an output range in front of the end of the one "
+                             f"before); seg_ptr: {bad_ptr} bad entries (outside [0, {S}] or below the entry before them); "
+                             f"notes: {excess} rows beyond the capacity of {cap}")
+    return out, out_ptr, totals, keep, status
+
+
 def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
                      c_logits=None, node_track=None):
     """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
