@@ -67,7 +67,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   exponential moving average of the parameters (pm_adam_step_ema, pm_buffer_swap); sampled generation
  *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash); chord-aware sampling (pm_sample_chords, pm_node_tracks; the
  *   PmChordRules struct); structure sampling (pm_sample_structure; the PmStructureRules struct); note events
- *   (pm_notes_from_tokens). */
+ *   (pm_notes_from_tokens); the GCL self block without its round trip (pm_gcl_forward_fused_sel / _sel_h2,
+ *   pm_gcl_weight_grad_fused_x / _x_h2: new entry points, no existing argument list changed). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -725,6 +726,30 @@ int pm_gcl_weight_grad_fused(const uint16_t* a_planes /* 3 planes [N,4d] */, int
                              const uint16_t* dh_planes /* 3 planes [N,d] */, int64_t dh_plane_stride, const int32_t* plan,
                              int32_t N, int32_t E, int32_t G, int32_t d, int32_t use_classes, float* dW /* [7d,d] += */,
                              pm_stream_t stream);
+/* The self block of A' without its round trip through HBM.  Columns [3d, 4d) of the compact aggregate are the root term's
+ * operand (model.py:119: the layer's own input row), in the planes: split(x[n]) (pair format: split(x[n] * *scale_out)) —
+ * a second copy of a tensor the caller holds until the backward has run.
+ *   pm_gcl_forward_fused_sel / _sel_h2: pm_gcl_forward_fused / _h2 with `self_planes`: 0 = those columns of every plane are
+ *   NOT written (layout and stride of `planes` unchanged; whatever they held stays); != 0 = the call above.  h, col_stats,
+ *   the relation blocks and *scale_out do not depend on it.
+ *   pm_gcl_weight_grad_fused_x / _x_h2: pm_gcl_weight_grad_fused / _h2 whose self-block tiles read the rows of `x` [N, d] —
+ *   the `x` the forward was given — and split them as the forward did, instead of reading those columns of `a_planes`
+ *   (never touched).  The same operand bits, so the same dW: bit-identical in deterministic mode.  N * d * 4 < 2^31. */
+int pm_gcl_forward_fused_sel(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d,
+                             float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag, const float* bias,
+                             int32_t use_classes, float* h, double* col_stats, uint16_t* planes, int64_t plane_stride,
+                             int32_t self_planes, pm_stream_t stream);
+int pm_gcl_forward_fused_sel_h2(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d,
+                                float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag, const float* bias,
+                                int32_t use_classes, float* h, double* col_stats, uint16_t* planes, int64_t plane_stride,
+                                const PmH2* h2, int32_t self_planes, pm_stream_t stream);
+int pm_gcl_weight_grad_fused_x(const uint16_t* a_planes, int64_t a_plane_stride, const float* x /* [N,d] */,
+                               const uint16_t* dh_planes, int64_t dh_plane_stride, const int32_t* plan, int32_t N, int32_t E,
+                               int32_t G, int32_t d, int32_t use_classes, float* dW /* [7d,d] += */, pm_stream_t stream);
+int pm_gcl_weight_grad_fused_x_h2(const uint16_t* a_planes, int64_t a_plane_stride, const float* x, const uint16_t* dh_planes,
+                                  int64_t dh_plane_stride, const int32_t* plan, int32_t N, int32_t E, int32_t G, int32_t d,
+                                  int32_t use_classes, float* dW, const float* a_scale, const float* dh_scale,
+                                  pm_stream_t stream);
 /* The weight products of GCL.forward (model.py:112-119) with the aggregate READ from A' planes (written by
  * pm_segreduce_fwd_planes) instead of built in the kernel: h[n] = A'[n] @ [W_t; W_4; W_5; root] + bias, `col_stats` as
  * above.  The path of dense graphs (BASELINE configs[4]: hundreds of edges per node — the fused kernel's producers keep
@@ -1484,7 +1509,7 @@ typedef struct PmBatch {                                    /* device pointers o
 } PmBatch;
 /* The step's A/B switches (environment variables PM_GCL_FUSED, PM_GCL_NO_DW, PM_NO_ROWS_W, PM_GCL_NO_CLASSES, PM_FUSED_CE,
  * PM_SIDE_STREAM, PM_SIDE_DELAY_US, PM_DAGG_BN, PM_DAGG_RES, PM_PLAN_SIDE, PM_CHORD_TABLES, PM_H2, PM_BAR_ROUTE, PM_PAD_SKIP, PM_UNEMBED_DW, PM_SENC_FIRST, PM_GCL_OFFSET_LIMIT,
- * PM_DEBUG: the complete list, csrc/vae_step.hip read_cfg) are read once, when the library is loaded; this re-reads them (host
+ * PM_GCL_SELF_PLANES, PM_DEBUG: the complete list, csrc/vae_step.hip read_cfg) are read once, when the library is loaded; this re-reads them (host
  * only) so that one process can run one batch through two kernel sets.  Switches of earlier rounds that are no longer read:
  * PM_NO_ROWS_TN, PM_NO_UNEMBED_DH, PM_GCL_NO_BFRAG, PM_DENSE_DEG, PM_LATE_WGRADS, PM_DW_SIDE, PM_FUSED_HEADS. */
 int pm_vae_step_reload_switches(void);

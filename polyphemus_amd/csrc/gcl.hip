@@ -63,6 +63,7 @@ struct GclArgs {
   const int* trk_list; const int* trk_cnt;
   const char* wfrag;             // fragment-major planes of the layer's [7d, d] weight (kind 1: [k-step][column tile][plane])
   uint16_t* planes; int64_t plane_stride;   // A' planes (optional)
+  int self_planes;               // 0: the self block's planes (columns [3d, 4d): the layer's own input rows) are not written
   float* h; double* colstats;
   unsigned* gate;                // deterministic mode (common.h): the workgroups add their column sums in turn
   int N, use_classes;
@@ -160,7 +161,7 @@ __global__ void __launch_bounds__(gcl_fwd_threads<D>()) __attribute__((amdgpu_wa
   // write latency into the gather's wait.  Rows past the end of the list: out-of-range offset, the store is dropped.
   const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(g.planes, 0, g.planes ? GCL_OOB : 0, 0x00020000);
   auto store_planes = [&](int c) {
-    if (!g.planes) return;
+    if (!g.planes || (!g.self_planes && c < NCH)) return;       // (the first NCH chunks of a tile are its self block)
     const int blk = chunk_blk(c), half = c % NCH;
     const char* img = img0 + (c & 1) * IMG;
     const int pt = tid - NCW * 64, ch = pt & 15, r0 = pt >> 4;        // 16 lanes per row (one 256-byte plane row), 4 rows per wave
@@ -841,7 +842,8 @@ template <int D, bool H2>
 __global__ void __launch_bounds__(DW_NTHR) __attribute__((amdgpu_waves_per_eu((DW_NMW + 4) / 4, (DW_NMW + 4) / 4)))
 k_gcl_dw(const uint16_t* __restrict__ Ap, int64_t aps, const uint16_t* __restrict__ dhp, int64_t dps,
          const int* __restrict__ trk_list, const int* __restrict__ trk_cnt, float* __restrict__ dW, int N, int nsplit,
-         int use_classes, unsigned* gate, const float* __restrict__ sa, const float* __restrict__ sdh) {
+         int use_classes, unsigned* gate, const float* __restrict__ sa, const float* __restrict__ sdh,
+         const float* __restrict__ X) {
   constexpr int NPL = H2 ? 2 : 3, T60 = H2 ? 3 : 0;     // operand planes; first product of the chain
   constexpr int NFT = 4 * D / DW_T, NCT = D / DW_T, PER = NFT * NCT;       // tiles per (group, slice)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -871,10 +873,22 @@ k_gcl_dw(const uint16_t* __restrict__ Ap, int64_t aps, const uint16_t* __restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // loaders: thread -> 16-byte chunk ch of rows r0 and r0 + 16 of each tile, three planes, both operands
   const int lt = tid - DW_NMW * 64, ch = lt & 15, r0 = lt >> 4;
-  const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(Ap), 0, GCL_OOB, 0x00020000);
+  // Self-block tiles with X given: the A' operand is the layer's input itself — the forward wrote split(x[n] * sa) there and
+  // need not have (pm_gcl_forward_fused_sel).  The loaders take 8 features per thread and row as two 16-byte loads of the fp32 row
+  // (the same two or three 16-byte slots per row a planes tile takes, the triple format's third one idle): slot s = features
+  // 64 s + 4 ch .. + 3 of the tile, so that the 16 lanes of a row read 256 contiguous bytes per load as they do from a plane.
+  // `put` splits them on the way into LDS with the forward's functions (8 bytes per plane and slot): the same image, bit for
+  // bit.  A tile lies inside one block, so the choice is uniform over the workgroup.
+  const bool selfx = X != nullptr && blk == 3;
+  const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(
+      selfx ? (void*)const_cast<float*>(X) : (void*)const_cast<uint16_t*>(Ap), 0, GCL_OOB, 0x00020000);
   const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(dhp), 0, GCL_OOB, 0x00020000);
-  const int acol = (ft * DW_T + ch * 8) * 2, dcol = (ct * DW_T + ch * 8) * 2;
-  const int aps_b = (int)(aps * 2), dps_b = (int)(dps * 2);
+  const int acol = selfx ? (ft * DW_T - 3 * D + ch * 4) * 4 : (ft * DW_T + ch * 8) * 2, dcol = (ct * DW_T + ch * 8) * 2;
+  const int arow = selfx ? D * 4 : 4 * D * 2;                      // bytes from one node's row to the next
+  const int aps_b = selfx ? 64 * 4 : (int)(aps * 2), dps_b = (int)(dps * 2);
+  const int anp = selfx ? 2 : NPL;                                 // 16-byte slots of the A' operand that are loaded
+  float asc = 1.f;                                                 // H2: the scale the forward's planes carry
+  if constexpr (H2) { if (selfx) asc = sa[0]; }
   // MFMA waves: part (wr, wc) of the tile: 64 rows x DW_WN 32-column tiles
   constexpr int DW_WN = 8 / DW_NMW, DW_WCOLS = DW_WN * 32, DW_WPR = DW_T / DW_WCOLS;   // column tiles, columns per wave, waves per row of parts
   const int li = lane & 31, lh = lane >> 5, wr = wave / DW_WPR, wc = wave % DW_WPR;
@@ -900,7 +914,7 @@ k_gcl_dw(const uint16_t* __restrict__ Ap, int64_t aps, const uint16_t* __restric
           const int n = t < nt ? sMap[t * DW_KT + r0 + j * 16] : -1;
 #pragma unroll
           for (int p = 0; p < NPL; ++p) {
-            v[j][0][p] = __builtin_amdgcn_raw_buffer_load_b128(ars, n >= 0 ? n * (4 * D * 2) + acol + p * aps_b : GCL_OOB, 0, 0);
+            v[j][0][p] = __builtin_amdgcn_raw_buffer_load_b128(ars, (n >= 0 && p < anp) ? n * arow + acol + p * aps_b : GCL_OOB, 0, 0);
             v[j][1][p] = __builtin_amdgcn_raw_buffer_load_b128(drs, n >= 0 ? n * (D * 2) + dcol + p * dps_b : GCL_OOB, 0, 0);
           }
         }
@@ -908,12 +922,38 @@ k_gcl_dw(const uint16_t* __restrict__ Ap, int64_t aps, const uint16_t* __restric
       auto put = [&](const u32x4 (&v)[2][2][3], int t) {
         char* st = smem + (t & 1) * DW_STAGE;
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 2; ++j) {
+          char* const row = st + (r0 + j * 16) * DW_PITCH + ch * 16;
+          if (selfx) {                                             // fp32 row pieces -> their planes (as `put` of k_gcl_fwd)
 #pragma unroll
-          for (int o = 0; o < 2; ++o)
+            for (int s = 0; s < 2; ++s) {
+              float4 f = __builtin_bit_cast(float4, v[j][0][s]);
+              char* const dst = row - ch * 8 + s * 128;              // features 64 s + 4 ch .. + 3: 8 bytes of each plane's row
+              if constexpr (H2) {
+                f.x *= asc; f.y *= asc; f.z *= asc; f.w *= asc;
+                unsigned l1, l2, u1, u2;
+                pm_split2h_pair(f.x, f.y, l1, l2);
+                pm_split2h_pair(f.z, f.w, u1, u2);
+                const pm_u32x2 p1 = {l1, u1}, p2 = {l2, u2};
+                *reinterpret_cast<pm_u32x2*>(dst) = p1;
+                *reinterpret_cast<pm_u32x2*>(dst + DW_PLANE) = p2;
+              } else {
+                unsigned l1, l2, l3, u1, u2, u3;
+                pm_split3_pair(f.x, f.y, l1, l2, l3);
+                pm_split3_pair(f.z, f.w, u1, u2, u3);
+                const pm_u32x2 p1 = {l1, u1}, p2 = {l2, u2}, p3 = {l3, u3};
+                *reinterpret_cast<pm_u32x2*>(dst) = p1;
+                *reinterpret_cast<pm_u32x2*>(dst + DW_PLANE) = p2;
+                *reinterpret_cast<pm_u32x2*>(dst + 2 * DW_PLANE) = p3;
+              }
+            }
+          } else {
 #pragma unroll
-            for (int p = 0; p < NPL; ++p)
-              *reinterpret_cast<u32x4*>(st + (o * 3 + p) * DW_PLANE + (r0 + j * 16) * DW_PITCH + ch * 16) = v[j][o][p];
+            for (int p = 0; p < NPL; ++p) *reinterpret_cast<u32x4*>(row + p * DW_PLANE) = v[j][0][p];
+          }
+#pragma unroll
+          for (int p = 0; p < NPL; ++p) *reinterpret_cast<u32x4*>(row + (3 + p) * DW_PLANE) = v[j][1][p];
+        }
       };
       u32x4 va[2][2][3], vb[2][2][3];
       issue(va, 0);
@@ -981,11 +1021,14 @@ k_gcl_dw(const uint16_t* __restrict__ Ap, int64_t aps, const uint16_t* __restric
 
 static int gcl_weight_grad_impl(const uint16_t* a_planes, int64_t a_plane_stride, const uint16_t* dh_planes,
                                 int64_t dh_plane_stride, const int32_t* plan, int32_t N, int32_t E, int32_t G,
-                                int32_t d, int32_t use_classes, float* dW, const float* sa, const float* sdh, pm_stream_t stream) {
+                                int32_t d, int32_t use_classes, float* dW, const float* sa, const float* sdh, pm_stream_t stream,
+                                const float* x = nullptr) {
   if (!a_planes || !dh_planes || !plan || !dW || N <= 0 || (d != 128 && d != 256 && d != 512) || a_plane_stride < (int64_t)N * 4 * d ||
       dh_plane_stride < (int64_t)N * d || (a_plane_stride & 7) || (dh_plane_stride & 7) || ((uintptr_t)a_planes % 16) ||
       ((uintptr_t)dh_planes % 16) || a_plane_stride * 6 >= 0x7fffffffLL)
     return PM_E_INVALID;
+  // (x: the self-block tiles read the fp32 rows with 32-bit byte offsets n * d * 4)
+  if (x && (((uintptr_t)x % 16) || (int64_t)N * d * 4 >= 0x7fffffffLL)) return PM_E_INVALID;
   PmPlanView pv = pm_plan_view(plan, N, E, G);
   hipStream_t st = (hipStream_t)stream;
   // K slices (one workgroup per output tile, track group and slice; slices add with float atomics): d = 512 two (64 output
@@ -1008,7 +1051,7 @@ static int gcl_weight_grad_impl(const uint16_t* a_planes, int64_t a_plane_stride
       once = true;                                                                                                     \
     }                                                                                                                  \
     hipLaunchKernelGGL((k_gcl_dw<DD, HH>), grid, block, lds, st, a_planes, a_plane_stride, dh_planes, dh_plane_stride, \
-                       pv.trk_list, pv.trk_cnt, dW, N, nsplit, use_classes, gate, sa, sdh);                            \
+                       pv.trk_list, pv.trk_cnt, dW, N, nsplit, use_classes, gate, sa, sdh, x);                         \
   } while (0)
   if (sa) { if (d == 512) LAUNCH(512, true); else if (d == 256) LAUNCH(256, true); else LAUNCH(128, true); }
   else if (d == 512) LAUNCH(512, false); else if (d == 256) LAUNCH(256, false); else LAUNCH(128, false);
@@ -1031,6 +1074,24 @@ extern "C" int pm_gcl_weight_grad_fused_h2(const uint16_t* a_planes, int64_t a_p
   return gcl_weight_grad_impl(a_planes, a_plane_stride, dh_planes, dh_plane_stride, plan, N, E, G, d, use_classes, dW, a_scale,
                               dh_scale, stream);
 }
+// ... with the self block of A' (columns [3d, 4d) of every plane) NOT read: the tiles of that block take the rows of `x` [N, d],
+// the input the forward was given, and split them as the forward did (pair format: times *a_scale first).  The same dW, bit for
+// bit in deterministic mode, as the calls above on planes whose self block the forward wrote.  N * d * 4 < 2^31.
+extern "C" int pm_gcl_weight_grad_fused_x(const uint16_t* a_planes, int64_t a_plane_stride, const float* x,
+                                          const uint16_t* dh_planes, int64_t dh_plane_stride, const int32_t* plan, int32_t N,
+                                          int32_t E, int32_t G, int32_t d, int32_t use_classes, float* dW, pm_stream_t stream) {
+  if (!x) return PM_E_INVALID;
+  return gcl_weight_grad_impl(a_planes, a_plane_stride, dh_planes, dh_plane_stride, plan, N, E, G, d, use_classes, dW, nullptr,
+                              nullptr, stream, x);
+}
+extern "C" int pm_gcl_weight_grad_fused_x_h2(const uint16_t* a_planes, int64_t a_plane_stride, const float* x,
+                                             const uint16_t* dh_planes, int64_t dh_plane_stride, const int32_t* plan, int32_t N,
+                                             int32_t E, int32_t G, int32_t d, int32_t use_classes, float* dW,
+                                             const float* a_scale, const float* dh_scale, pm_stream_t stream) {
+  if (!x || !a_scale || !dh_scale) return PM_E_INVALID;
+  return gcl_weight_grad_impl(a_planes, a_plane_stride, dh_planes, dh_plane_stride, plan, N, E, G, d, use_classes, dW, a_scale,
+                              dh_scale, stream, x);
+}
 
 static size_t gcl_lds_bytes(int d, bool drop) {
   return 2 * IMG + (size_t)PM_N_DIST * d * 4 + (BM + BM * 3 * 8) * 4;
@@ -1039,7 +1100,7 @@ static size_t gcl_lds_bytes(int d, bool drop) {
 static int gcl_forward_impl(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G,
                             int32_t d, float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag,
                             const float* bias, int32_t use_classes, float* h, double* col_stats, uint16_t* planes,
-                            int64_t plane_stride, const PmH2* h2, pm_stream_t stream) {
+                            int64_t plane_stride, const PmH2* h2, pm_stream_t stream, int self_planes = 1) {
   if (!x || !T || !plan || !w_frag || !h || N <= 0 || (d != 128 && d != 256 && d != 512) || dropout_p < 0.f || dropout_p >= 1.f ||
       ((uintptr_t)w_frag % 16) || ((uintptr_t)x % 16) || ((uintptr_t)T % 16) || (int64_t)N * d * 4 >= 0x7fffffffLL || N >= (1 << 27))
     return PM_E_INVALID;
@@ -1049,14 +1110,14 @@ static int gcl_forward_impl(const float* x, const float* T, const int32_t* plan,
   if (h2 && (!h2->absmax_in || !h2->absmax_aux || !h2->scale_out || !(h2->w_scale > 0.f))) return PM_E_INVALID;
   if (d == 512)                 // 512-wide layers: the ring pipeline of wide.hip
     return pm_wide_gcl_forward(x, T, plan, N, E, G, dropout_p, seed, layer_uid, w_frag, bias, use_classes, h, col_stats,
-                               planes, plane_stride, nullptr, (hipStream_t)stream, h2);
+                               planes, plane_stride, nullptr, (hipStream_t)stream, h2, self_planes);
   PmPlanView pv = pm_plan_view(plan, N, E, G);
   GclArgs a;
   a.mx = h2 ? h2->absmax_in : nullptr; a.mt = h2 ? h2->absmax_aux : nullptr; a.w_scale = h2 ? h2->w_scale : 1.f;
   a.sa_out = h2 ? h2->scale_out : nullptr;
   a.x = x; a.T = T; a.bias = bias; a.rowptr = pv.rowptr; a.csr_src = pv.csr_src; a.csr_dist = pv.csr_dist;
   a.csr_eid = pv.csr_eid; a.trk_list = pv.trk_list; a.trk_cnt = pv.trk_cnt;
-  a.wfrag = reinterpret_cast<const char*>(w_frag); a.planes = planes; a.plane_stride = plane_stride; a.h = h;
+  a.wfrag = reinterpret_cast<const char*>(w_frag); a.planes = planes; a.plane_stride = plane_stride; a.self_planes = self_planes; a.h = h;
   a.colstats = col_stats; a.N = N; a.use_classes = use_classes;
   a.gate = col_stats ? pm_det_gate((hipStream_t)stream) : nullptr;
   const bool drop = dropout_p > 0.f;
@@ -1101,6 +1162,24 @@ extern "C" int pm_gcl_forward_fused_h2(const float* x, const float* T, const int
   if (!h2) return PM_E_INVALID;
   return gcl_forward_impl(x, T, plan, N, E, G, d, dropout_p, seed, layer_uid, w_frag, bias, use_classes, h, col_stats, planes,
                           plane_stride, h2, stream);
+}
+// ... with a say in whether the self block of A' goes to `planes`: `self_planes` = 0 leaves columns [3d, 4d) of every plane
+// unwritten (the layout and the stride stay) — they would hold the split of x[n] (* scale_out), which the weight gradient can
+// take from x itself (pm_gcl_weight_grad_fused_x).  h, the column sums, the other blocks and scale_out are those of the calls above.
+extern "C" int pm_gcl_forward_fused_sel(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G,
+                                        int32_t d, float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag,
+                                        const float* bias, int32_t use_classes, float* h, double* col_stats, uint16_t* planes,
+                                        int64_t plane_stride, int32_t self_planes, pm_stream_t stream) {
+  return gcl_forward_impl(x, T, plan, N, E, G, d, dropout_p, seed, layer_uid, w_frag, bias, use_classes, h, col_stats, planes,
+                          plane_stride, nullptr, stream, self_planes != 0);
+}
+extern "C" int pm_gcl_forward_fused_sel_h2(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G,
+                                           int32_t d, float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag,
+                                           const float* bias, int32_t use_classes, float* h, double* col_stats, uint16_t* planes,
+                                           int64_t plane_stride, const PmH2* h2, int32_t self_planes, pm_stream_t stream) {
+  if (!h2) return PM_E_INVALID;
+  return gcl_forward_impl(x, T, plan, N, E, G, d, dropout_p, seed, layer_uid, w_frag, bias, use_classes, h, col_stats, planes,
+                          plane_stride, h2, stream, self_planes != 0);
 }
 
 // The same product with the aggregate READ from A' planes instead of built in the kernel: dense graphs (hundreds of edges

@@ -43,6 +43,8 @@ namespace {
 //                       the bar-resident kernels of cnn.hip (3 + 2 + 4) — the parity test's reference
 //   PM_DAGG_BN=0, PM_DAGG_RES=0, PM_PLAN_SIDE=0, PM_CHORD_TABLES=0, PM_H2=0, PM_BAR_ROUTE=0, PM_PAD_SKIP=0, PM_UNEMBED_DW=0, PM_SENC_FIRST=0: see
 //                       the fields of StepCfg
+//   PM_GCL_SELF_PLANES=1  the fused GCL forward also stores the self block of the A' planes and the tile weight gradient reads it
+//                       back, instead of taking those rows from the layer's fp32 input (GcnRoute.self_stored)
 //   PM_GCL_OFFSET_LIMIT=n, PM_DEBUG
 // Former switches (PM_NO_ROWS_TN, PM_NO_UNEMBED_DH, PM_GCL_NO_BFRAG, PM_DENSE_DEG, PM_LATE_WGRADS, PM_DW_SIDE, PM_FUSED_HEADS): their
 // losing side was measured and removed with the code it needed (profiles/LOG.md) — setting them has no effect.
@@ -66,6 +68,8 @@ struct StepCfg {
   bool unembed_dw;             // PM_UNEMBED_DW=0: the un-embedding weight gradients as three split-K products of the fp32 tile GEMM (rounds 2-5)
   bool pad_skip;               // PM_PAD_SKIP=0: the decoder head over every (node, active slot) row, PAD targets included (rounds 2-5)
   bool cnn_fused;              // PM_CNN_FUSED=0: see above
+  bool self_planes;            // PM_GCL_SELF_PLANES=1: see above (the same-binary A/B of the self block's round trip: 4dN bytes written
+                               // per layer and read back, for rows the workspace already holds)
   bool bar_route;              // PM_BAR_ROUTE=0: dense graphs on the row-gather kernels of segreduce.hip (rounds 1-5) instead of bar.hip
   int64_t offset_limit;        // PM_GCL_OFFSET_LIMIT: operand bytes up to which the 32-bit-offset kernels are used (tests lower it)
 };
@@ -90,6 +94,7 @@ static StepCfg read_cfg() {
   k.unembed_dw = flag("PM_UNEMBED_DW", true);
   k.senc_first = flag("PM_SENC_FIRST", true);
   k.cnn_fused = flag("PM_CNN_FUSED", true);
+  k.self_planes = flag("PM_GCL_SELF_PLANES", false);
   k.offset_limit = getenv("PM_GCL_OFFSET_LIMIT") ? atoll(getenv("PM_GCL_OFFSET_LIMIT")) : 0x7fffffffLL;
   return k;
 }
@@ -138,6 +143,9 @@ struct GcnRoute {
   enum Mul { MUL_FUSED, MUL_FROM_PLANES, MUL_GROUPED, MUL_SEVEN } mul;
   bool h2;                               // the stack's three GCL products in the fp16 pair format (PmH2; the _h2 form of each kernel)
   bool x_tracked;                        // ... and the norm apply of layer i leaves |x|max for layer i+1's operand scale
+  bool self_stored;                      // the A' planes hold their self block (columns [3d, 4d): the split of xin[i]).  Off exactly where the
+                                         // aggregate is built inside the product AND the tile kernel takes the weight gradient: that kernel
+                                         // reads xin[i] instead.  Every other producer / consumer of the planes writes / reads all four blocks
   bool plain_w_planes;                   // gcn_prepare splits the weights into row-major planes (operand of the grouped products)
   // backward, L x { norm backward; input gradient; weight gradient; aggregation }: the norm backward inside the input gradient's
   // prologue (k_gcl_dagg<.., true>; its sums by a pass of their own at the top layer) | pm_bn_bwd_fused (pair format: it writes the
@@ -494,6 +502,7 @@ GcnRoute gcn_route(const Ctx& c, const GcnSaved& sv) {
   r.res_in_dagg = in_dagg && !dropping && k.dagg_res;
   r.dagg = !c.compact ? GcnRoute::DAGG_SEVEN : in_dagg ? GcnRoute::DAGG_BN : gcl_kernels ? GcnRoute::DAGG_TILES : GcnRoute::DAGG_GROUPED;
   r.dw = !c.compact ? GcnRoute::DW_SEVEN : (tiles && gcl_width(d) && !k.no_dw) ? GcnRoute::DW_TILES : GcnRoute::DW_GROUPED;
+  r.self_stored = k.self_planes || !(r.agg == GcnRoute::AGG_IN_PRODUCT && r.dw == GcnRoute::DW_TILES);
   r.bagg = dropping ? GcnRoute::BAGG_SEG_DROPPED : bar ? GcnRoute::BAGG_BAR : GcnRoute::BAGG_SEG;
   // the segment-reduce backward of layer i also accumulates the column sums of the norm backward of layer i-1; beyond
   // d = 512 that variant spills (16-wave workgroups: 128 VGPRs), so wider models take the separate column-sum pass
@@ -626,11 +635,11 @@ float* gcn_forward(Ctx& c, float* x0, const PmGcn& g, GcnSaved& sv, uint32_t see
     switch (r.agg) {
       case GcnRoute::AGG_IN_PRODUCT:
         if (r.h2)
-          RUN(pm_gcl_forward_fused_h2(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, Wf, bias, r.classes,
-                                        sv.h[i], sums, sv.Ap[i], aps, &h2, c.st));
+          RUN(pm_gcl_forward_fused_sel_h2(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, Wf, bias, r.classes,
+                                            sv.h[i], sums, sv.Ap[i], aps, &h2, r.self_stored, c.st));
         else
-          RUN(pm_gcl_forward_fused(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, Wf, bias, r.classes,
-                                     sv.h[i], sums, sv.Ap[i], aps, c.st));
+          RUN(pm_gcl_forward_fused_sel(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, Wf, bias, r.classes,
+                                         sv.h[i], sums, sv.Ap[i], aps, r.self_stored, c.st));
         break;
       case GcnRoute::AGG_BAR:
         RUN(pm_bar_aggregate_fwd(sv.xin[i], sv.T, c.s->plan, N, c.E, c.Gn, d, p, seed, uid0 + i, sv.Ap[i], aps, r.h2 ? &h2 : nullptr, c.st)); break;
@@ -768,8 +777,13 @@ float* gcn_backward(Ctx& c, float* dx, const PmGcn& g, GcnSaved& sv) {
       case GcnRoute::DW_SEVEN:
         RUN(pm_gemm_f32(1, 0, 7 * d, d, N, sv.A[i], 7 * d, dh, d, dW, d, nullptr, PM_GEMM_ACCUM, 0, nullptr, 0, nullptr, c.st)); break;
       case GcnRoute::DW_TILES:
-        if (r.h2)
+        // (self block not stored: its tiles read the forward's input — with cfg.dropout the dropped copy — which stays in the arena)
+        if (r.h2 && !r.self_stored)
+          RUN(pm_gcl_weight_grad_fused_x_h2(sv.Ap[i], aps, sv.xin[i], dhp, dps, c.s->plan, N, c.E, c.Gn, d, r.classes, dW, sv.sA + i, sv.sdh + i, c.st));
+        else if (r.h2)
           RUN(pm_gcl_weight_grad_fused_h2(sv.Ap[i], aps, dhp, dps, c.s->plan, N, c.E, c.Gn, d, r.classes, dW, sv.sA + i, sv.sdh + i, c.st));
+        else if (!r.self_stored)
+          RUN(pm_gcl_weight_grad_fused_x(sv.Ap[i], aps, sv.xin[i], dhp, dps, c.s->plan, N, c.E, c.Gn, d, r.classes, dW, c.st));
         else
           RUN(pm_gcl_weight_grad_fused(sv.Ap[i], aps, dhp, dps, c.s->plan, N, c.E, c.Gn, d, r.classes, dW, c.st));
         break;
@@ -1691,7 +1705,9 @@ extern "C" int pm_vae_step_output_views(const void* state, int64_t* byte_offset,
 }
 
 // Where the last forward keeps an activation inside the caller's workspace (host only): parity tools read the tensors the
-// backward takes its ReLU decisions from (tests/test_fullsize_gpu.py imposes them on the fp64 oracle).  `what`: PM_SAVED_*;
+// backward takes its ReLU decisions from (tests/test_fullsize_gpu.py imposes them on the fp64 oracle).  The A' planes are not
+// among them: where GcnRoute.self_stored is off their columns [3d, 4d) are UNDEFINED (never written; PM_SAVED_GCN_XIN is what the
+// weight gradient contracts there) — a tool that wants the whole aggregate sets PM_GCL_SELF_PLANES=1.  `what`: PM_SAVED_*;
 // stack 0 = encoder / 1 = decoder GCN; *byte_offset is relative to the workspace pointer given to pm_vae_step_forward.
 extern "C" int pm_vae_step_saved(const void* state, int32_t what, int32_t stack, int32_t layer, int64_t* byte_offset, int64_t* numel) {
   const StepState* s = (const StepState*)state;

@@ -5,10 +5,11 @@
 
 // h = A'(x) @ [W_t; W_4; W_5; root] + bias in one kernel (pm_gcl_forward_fused at d = 512).  `a_planes_in` non-null:
 // the aggregate is not built by the kernel but read from these A' planes (dense graphs: pm_segreduce_fwd_planes first).
+// `self_planes` = 0: the self block of `planes` (columns [3d, 4d)) is not written (pm_gcl_forward_fused_noself).
 int pm_wide_gcl_forward(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G,
                         float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag, const float* bias,
                         int32_t use_classes, float* h, double* col_stats, uint16_t* planes, int64_t plane_stride,
-                        const uint16_t* a_planes_in, hipStream_t st, const PmH2* h2 = nullptr);
+                        const uint16_t* a_planes_in, hipStream_t st, const PmH2* h2 = nullptr, int self_planes = 1);
 // dA' = dh @ [W_t; W_4; W_5; root]^T (pm_gcl_input_grad_fused at d = 512)
 int pm_wide_gcl_input_grad(const uint16_t* dh_planes, int64_t plane_stride, const int32_t* plan, int32_t N, int32_t E,
                            int32_t G, const uint16_t* w_frag_t, int32_t use_classes, float* dA, hipStream_t st,

@@ -48,6 +48,7 @@ struct WideArgs {
   const float* T; const int* rowptr; const int* csr_src; const int* csr_dist; const int* csr_eid;
   uint32_t seed, layer_uid, thresh; float scale;
   uint16_t* planes; int64_t plane_stride;                   // A' planes out (V_FWD, optional)
+  int self_planes;                                          // ... 0: without the self block (columns [3d, 4d): the input rows)
   // MFMA waves
   const char* wfrag; int wp;                                // fragment-major weight planes; tiles per k-step (kind 1) / k-steps per tile (kind 0)
   int K, npass;                                             // V_ROWSWK: inner dimension; V_ROWSW: 512-column output blocks
@@ -132,7 +133,7 @@ __global__ void __launch_bounds__((NCW + NPW) * 64) k_wide(WideArgs g) {
       constexpr int TPT = PM_N_DIST * CH / 4 / NPT;            // float4 of a table slice per thread
       // A' planes of chunk c, copied from its image after the gathers of the next chunk have been issued (vmcnt retires in order)
       auto store_planes = [&](int c) {
-        if (!g.planes) return;
+        if (!g.planes || (!g.self_planes && c < NCHW)) return;     // (the first NCHW chunks of a tile are its self block)
         const int blk = chunk_blk(c), half = c % NCHW;
         const char* img = img0 + (c & 1) * IMG;
         const int ch = pt & 15, r0 = pt >> 4;                    // 16 lanes per 256-byte plane row
@@ -592,7 +593,7 @@ size_t wide_lds(int var) {
 int pm_wide_gcl_forward(const float* x, const float* T, const int32_t* plan, int32_t N, int32_t E, int32_t G,
                         float dropout_p, uint32_t seed, uint32_t layer_uid, const uint16_t* w_frag, const float* bias,
                         int32_t use_classes, float* h, double* col_stats, uint16_t* planes, int64_t plane_stride,
-                        const uint16_t* a_planes_in, hipStream_t st, const PmH2* h2) {
+                        const uint16_t* a_planes_in, hipStream_t st, const PmH2* h2, int self_planes) {
   const int d = WD;
   if ((int64_t)N * d * 4 * 4 >= 0x7fffffffLL) return PM_E_INVALID;
   if (a_planes_in && (plane_stride < (int64_t)N * 4 * d || (plane_stride & 7) || plane_stride * 6 >= 0x7fffffffLL))
@@ -618,7 +619,7 @@ int pm_wide_gcl_forward(const float* x, const float* T, const int32_t* plan, int
     if (wide_npw(4) == 8) launch_wide<V_FWDP, false, 8, 1>(a, grid, wide_lds(V_FWDP), st);
     else launch_wide<V_FWDP, false, 4, 1>(a, grid, wide_lds(V_FWDP), st);
   } else {
-    a.planes = planes; a.plane_stride = plane_stride;
+    a.planes = planes; a.plane_stride = plane_stride; a.self_planes = self_planes;
     const size_t lds = wide_lds(V_FWD);
     if (h2) {                                              // fp16 pair format: eight producer waves
       a.mx = h2->absmax_in; a.mt = h2->absmax_aux; a.sa_out = h2->scale_out; a.w_scale = h2->w_scale;

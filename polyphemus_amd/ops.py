@@ -787,6 +787,22 @@ def gcl_forward_fused(x, T, plan: Plan, dropout_p: float, seed: int, layer_uid: 
     return h
 
 
+def gcl_forward_fused_sel(x, T, plan: Plan, dropout_p: float, seed: int, layer_uid: int, w_frag, bias, col_stats=None,
+                          planes=None, use_classes: bool = True, self_planes: bool = False, h2=None):
+    """`pm_gcl_forward_fused_sel` / `_sel_h2` (with `h2`, the address of a PmH2): `gcl_forward_fused` that leaves columns
+    [3d, 4d) of `planes` (the self block: the split of x itself) unwritten unless `self_planes`."""
+    _chk(x, F32, "x"); _chk(T, F32, "T")
+    N, d = x.shape
+    h = torch.empty(N, d, dtype=F32, device=x.device)
+    head = (ptr(x), ptr(T), ptr(plan.buf), N, plan.E, plan.G, d, float(dropout_p), seed & 0xFFFFFFFF, layer_uid, ptr(w_frag),
+            ptr(bias), 1 if use_classes else 0, ptr(h), ptr(col_stats), ptr(planes), 0 if planes is None else planes.shape[1])
+    if h2 is None:
+        call("pm_gcl_forward_fused_sel", *head, 1 if self_planes else 0, stream())
+    else:
+        call("pm_gcl_forward_fused_sel_h2", *head, h2, 1 if self_planes else 0, stream())
+    return h
+
+
 def gcl_forward_from_planes(a_planes, plan: Plan, d: int, w_frag, bias, col_stats=None, use_classes: bool = True):
     """`pm_gcl_forward_from_planes`: h = A' @ [W_t; W_4; W_5; root] + bias with the aggregate read from the planes
     `pm_segreduce_fwd_planes` wrote (int16 [3, N*4d]); the dense-graph path at d = 512."""
@@ -840,6 +856,19 @@ def gcl_weight_grad_fused(a_planes, dh_planes, plan: Plan, d: int, dW, use_class
     _chk(dW, F32, "dW")
     call("pm_gcl_weight_grad_fused", ptr(a_planes), a_planes.shape[1], ptr(dh_planes), dh_planes.shape[1], ptr(plan.buf),
          plan.N, plan.E, plan.G, d, 1 if use_classes else 0, ptr(dW), stream())
+    return dW
+
+
+def gcl_weight_grad_fused_x(a_planes, x, dh_planes, plan: Plan, d: int, dW, use_classes: bool = True, a_scale=None, dh_scale=None):
+    """`pm_gcl_weight_grad_fused_x` / `_x_h2` (with the two device scales of the pair format): `gcl_weight_grad_fused` whose
+    self-block tiles read the rows of `x` [N, d] (the forward's input) instead of columns [3d, 4d) of `a_planes`."""
+    _chk(dW, F32, "dW"); _chk(x, F32, "x")
+    head = (ptr(a_planes), a_planes.shape[1], ptr(x), ptr(dh_planes), dh_planes.shape[1], ptr(plan.buf), plan.N, plan.E, plan.G, d,
+            1 if use_classes else 0, ptr(dW))
+    if a_scale is None:
+        call("pm_gcl_weight_grad_fused_x", *head, stream())
+    else:
+        call("pm_gcl_weight_grad_fused_x_h2", *head, ptr(a_scale), ptr(dh_scale), stream())
     return dW
 
 
