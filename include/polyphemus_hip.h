@@ -599,6 +599,55 @@ int pm_notes_splice(const int32_t* notes /* [M,3] */, const int32_t* track_ptr /
                     int32_t* out_totals /* [2] */, int32_t* keep /* [K] */,
                     int32_t* scratch /* [PM_SPLICE_SCRATCH(K, S)] */, int32_t* status /* [4] */, pm_stream_t stream);
 
+/* ------------------------------------------------------------------ Scores
+ * What the decoder thinks of a piece: the log-likelihood of the piece's own tokens and structure under the decoder's logits,
+ * per bar and track, with the counts behind the reference's accuracies.  The reference has these terms only as batch means:
+ * the cross-entropies with ignore_index = PAD and the BCE with logits of `_losses` (training.py:298-347), the ratios of
+ * `_note_accuracy` and its neighbours (training.py:438-468).  Here they stay apart per (bar g = i * n_bars + b of piece i,
+ * track k); sums over bars and tracks, ratios, ELBO and importance-weighted bounds are left to the caller.  Additive, same
+ * ABI version.
+ *
+ * pm_score_tokens: nodes are the active cells of s_tensor in cell order, as in pm_node_tracks; a node at or beyond N is
+ * ignored.  Row (n, j), j = 0..14, has the logits c_logits[n, j] (131 pitch columns, then 99 duration columns) and the targets
+ *   tokens[n, j]      with tok_slots = 15 (the layout pm_sample_tokens writes),
+ *   tokens[n, j + 1]  with tok_slots = 16 (pm_tokens_from_notes, BarGraphBatch.tokens: slot 0 is the SOS and is no target).
+ * A pitch target is present iff it lies in [0, 130), a duration target iff it lies in [0, 98): PAD (130 / 98, the reference's
+ * ignore_index, training.py:101-102) and anything outside the head is absent.  For a head h of a row with a present target t:
+ *   logp = (x_t - m) - log sum_c exp(x_c - m), m = max_c x_c over the head's columns, in fp32;
+ *   hit  = (t is the head's arg-max, the first index among equal maxima: the rule of pm_content_accuracy).
+ *   row_logp    fp32 [N,15,2] (pitch, duration): logp, 0 where the target is absent.
+ *   row_verdict uint8 [N,15]: bit 0 pitch hit, bit 1 duration hit, bit 2 pitch target present, bit 3 duration target present.
+ *   logp        fp64 [G,4,2]: the sums of row_logp over the rows of the track's nodes.  A node's 15 rows are added in slot
+ *               order, the nodes of a track by a fixed tree, all in fp64.
+ *   counts      int32 [G,4,6]: nodes, pitch targets, duration targets, pitch hits, duration hits, note hits (pitch AND duration
+ *               hit on a row whose pitch target is present: `_note_accuracy`).
+ *   scratch     bar_nodes [G] and node_ptr [G+1] as for pm_node_tracks; node_ptr[G] is the number of active cells, which the
+ *               caller compares with N.
+ * Every word of the four outputs is written on every call, those of bars and tracks without nodes included (zeros); all N
+ * rows of row_logp and row_verdict are written whether or not a cell owns the node.  A row whose targets are both absent is
+ * not read: 8 B of targets per row, 920 B of logits per row with a target, 9 B written per row; the bar pass reads 135 B per
+ * node and writes 160 B per bar.  Four launches on the stream (cells per bar, their scan, the rows, the bars), no host read, no
+ * atomics: two calls on the same inputs write the same bytes, and the words of a bar depend on that bar's nodes alone.
+ * PM_E_INVALID (before any launch): a NULL pointer (c_logits, tokens, row_logp and row_verdict may be NULL when N == 0);
+ *   G <= 0; N < 0; tok_slots other than 15 / 16; 15 N or 128 G >= 2^31; bar_nodes == node_ptr; tokens, row_logp or logp not
+ *   8-byte aligned, another fp32 / int32 buffer not 4-byte aligned.
+ *
+ * pm_score_structure: the Bernoulli log-likelihood of the cells of s_tensor [G,4,32] (a cell is on iff it is non-zero) under
+ * s_logits [G,4,32], per (bar, track):
+ *   logp   fp64 [G,4] = - sum_t [max(x, 0) - x y + log1p(exp(-|x|))]: the terms in fp32, their 32-term sum in fp64 by a fixed
+ *          tree.
+ *   counts int32 [G,4,4]: targets on, predictions on, true positives, cells that agree.  The prediction is the one of
+ *          pm_structure_metrics, sigmoid(x) >= 0.5.
+ * One launch, a bar per half-wave: 1 KB read and 96 B written per bar, no atomics, no workspace.
+ * PM_E_INVALID (before the launch): a NULL pointer; G <= 0 or 128 G >= 2^31; logp not 8-byte aligned, another buffer not
+ *   4-byte aligned. */
+int pm_score_tokens(const float* c_logits /* [N,15,230] */, const int32_t* tokens /* [N,tok_slots,2] */, int32_t tok_slots,
+                    const float* s_tensor /* [G,4,32] */, int32_t G, int64_t N, int32_t* bar_nodes /* [G] ws */,
+                    int32_t* node_ptr /* [G+1] ws */, float* row_logp /* [N,15,2] */, uint8_t* row_verdict /* [N,15] */,
+                    double* logp /* [G,4,2] */, int32_t* counts /* [G,4,6] */, pm_stream_t stream);
+int pm_score_structure(const float* s_logits /* [G,4,32] */, const float* s_tensor /* [G,4,32] */, int32_t G,
+                       double* logp /* [G,4] */, int32_t* counts /* [G,4,4] */, pm_stream_t stream);
+
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):
  *   A[n, r*d:(r+1)*d] = mean_{e: dst=n, type=r} keep_e * relu(x[src_e] * T[dist_e]) / (1-p)

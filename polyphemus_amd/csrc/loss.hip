@@ -4,7 +4,7 @@
 // the pitch (131) and duration (99) logits of every (node, slot) row — there as log_softmax + nll_loss
 // + argmax over the one-hot targets — BCEWithLogits on the structure grid and the KL divergence.
 // Memory-bound: one pass over the [N,15,230] logits produces the two losses AND d(loss)/d(logits).
-#include "common.h"
+#include "heads.h"
 
 // one wave per (node, slot) row.  out[0] += pitch CE / n_valid_pitch, out[1] += dur CE / n_valid_dur.
 // Optionally also the gradients of the three un-embedding biases (column sums of d_logits over the drum rows,
@@ -280,21 +280,10 @@ __global__ void __launch_bounds__(256) k_content_accuracy(const float* __restric
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
     const int64_t n = row / PM_N_SLOTS;
     const int s = (int)(row % PM_N_SLOTS) + 1;                          // slot 0 is SOS (training.py:352)
-    const float* x = logits + row * PM_N_TOK;
-    float bp = -INFINITY, bd = -INFINITY;
-    int ip = 0x7fffffff, id = 0x7fffffff;
-    for (int i = lane; i < PM_N_TOK; i += 64) {
-      const float v = x[i];
-      if (i < PM_N_PITCH) { if (v > bp) { bp = v; ip = i; } }
-      else if (v > bd) { bd = v; id = i - PM_N_PITCH; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float op = __shfl_xor(bp, o, 64), od = __shfl_xor(bd, o, 64);
-      const int jp = __shfl_xor(ip, o, 64), jd = __shfl_xor(id, o, 64);
-      if (op > bp || (op == bp && jp < ip)) { bp = op; ip = jp; }
-      if (od > bd || (od == bd && jd < id)) { bd = od; id = jd; }
-    }
+    float v[4];
+    int ip, id;
+    load_row(logits + row * PM_N_TOK, lane, v);
+    head_argmax(v, lane, ip, id);
     if (lane == 0) {
       const int tp = tok[(n * 16 + s) * 2], td = tok[(n * 16 + s) * 2 + 1];
       const bool np_ = tp != PM_N_PITCH - 1, nd_ = td != PM_N_DUR - 1;     // PAD is the last token of both vocabularies
@@ -326,8 +315,7 @@ __global__ void __launch_bounds__(256) k_structure_metrics(const float* __restri
                                                            int64_t n, unsigned long long* __restrict__ counts) {
   unsigned int c[4] = {0, 0, 0, 0};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float p = 1.0f / (1.0f + expf(-logits[i]));
-    const bool pred = p >= 0.5f, t = target[i] != 0.f;
+    const bool pred = structure_pred(logits[i]), t = target[i] != 0.f;
     c[0] += pred == t; c[1] += pred && t; c[2] += pred; c[3] += t;
   }
   for (int k = 0; k < 4; ++k) {
@@ -366,21 +354,10 @@ __global__ void __launch_bounds__(256) k_content_verdict(const float* __restrict
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
     const int64_t n = row / S;
     const int s = (int)(row - n * S) + 1;
-    const float* x = logits + row * PM_N_TOK;
-    float bp = -INFINITY, bd = -INFINITY;
-    int ip = 0x7fffffff, id = 0x7fffffff;
-    for (int i = lane; i < PM_N_TOK; i += 64) {
-      const float v = x[i];
-      if (i < PM_N_PITCH) { if (v > bp) { bp = v; ip = i; } }
-      else if (v > bd) { bd = v; id = i - PM_N_PITCH; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float op = __shfl_xor(bp, o, 64), od = __shfl_xor(bd, o, 64);
-      const int jp = __shfl_xor(ip, o, 64), jd = __shfl_xor(id, o, 64);
-      if (op > bp || (op == bp && jp < ip)) { bp = op; ip = jp; }
-      if (od > bd || (od == bd && jd < id)) { bd = od; id = jd; }
-    }
+    float v[4];
+    int ip, id;
+    load_row(logits + row * PM_N_TOK, lane, v);
+    head_argmax(v, lane, ip, id);
     if (lane == 0) {
       const int tp = tok[(n * 16 + s) * 2], td = tok[(n * 16 + s) * 2 + 1];
       if (tp != PM_N_PITCH - 1) verdict[row] = ip == tp;
@@ -409,8 +386,7 @@ __global__ void __launch_bounds__(256) k_metric_counts(const int* __restrict__ t
   }
   if (s_logits)
     for (int64_t i = g0; i < n_cells; i += gs) {                        // k_structure_metrics
-      const float p = 1.0f / (1.0f + expf(-s_logits[i]));
-      const bool pred = p >= 0.5f, t = s_target[i] != 0.f;
+      const bool pred = structure_pred(s_logits[i]), t = s_target[i] != 0.f;
       c[7] += pred == t; c[8] += pred && t; c[9] += pred; c[10] += t;
     }
 #pragma unroll

@@ -2,9 +2,9 @@
 // nucleus (top-p) sampling of the pitch and the duration token of every (node, slot) row of the content logits, and sampling
 // of the bar structure from the structure logits.
 //
-//   the core        : the row layout (load_row), the noise of the stream (seed, head, row, token) (unit_noise, gumbel), the
-//                     arg-max (cand_better, cand_wave) and head_filter, the top-k / top-p pass of one head of one row over a
-//                     set of candidate columns.
+//   the core        : the row layout and the arg-max (load_row, cand_better, cand_wave: heads.h, shared with loss.hip and
+//                     score.hip), the noise of the stream (seed, head, row, token) (unit_noise, gumbel) and head_filter, the
+//                     top-k / top-p pass of one head of one row over a set of candidate columns.
 //   k_sample_tokens : one wave per row of 230 logits (920 B, read once), 8 B of tokens written: both heads at once, every live
 //                     column a candidate of its head's head_filter.
 //   k_sample_chords : chord-aware sampling (PmChordRules): one wave per node, its 15 slots decided in order as notes, one EOS,
@@ -23,26 +23,12 @@
 //                     half without a bar (odd G, the last wave) take part in every cross-lane step and store nothing.
 #include <type_traits>
 #include "bars.h"
+#include "heads.h"
 
 namespace {
 
 enum { SAMPLE_GREEDY = 0, SAMPLE_PLAIN = 1, SAMPLE_TOPK = 2, SAMPLE_TOPP = 3 };
 
-// a candidate of the arg-max: score, then the lower token index
-struct Cand { float s; int c; };
-__device__ static inline Cand cand_better(Cand a, Cand b) {
-  return (b.s > a.s || (b.s == a.s && b.c < a.c)) ? b : a;
-}
-__device__ static inline Cand cand_wave(Cand a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    Cand b;
-    b.s = __shfl_xor(a.s, o, 64);
-    b.c = __shfl_xor(a.c, o, 64);
-    a = cand_better(a, b);
-  }
-  return a;
-}
 __device__ static inline float bcast(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -61,16 +47,7 @@ __device__ static inline unsigned ukey(float x) {
   return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
 
-// A row of 230 logits (920 B, read once) across the wave: lane l holds the columns l, l + 64, l + 128, l + 192 (four coalesced
-// 256-byte wave loads; the last one 38 lanes wide, -inf behind it).  Registers 0, 1 and the lanes 0..2 of register 2 are the
-// pitch head (token = column), the lanes 3..63 of register 2 and register 3 the duration head (token = column - 131).
-__device__ static inline void load_row(const float* __restrict__ x, int lane, float (&v)[4]) {
-#pragma unroll
-  for (int j = 0; j < 3; ++j) v[j] = x[lane + 64 * j];
-  v[3] = lane < PM_N_TOK - 192 ? x[lane + 192] : -INFINITY;
-}
-
-// ---- the sampling core.  The draw is a Gumbel arg-max (gumbel, cand_better, cand_wave above), so no cumulative sum and no
+// ---- the sampling core.  The draw is a Gumbel arg-max (gumbel above, cand_better and cand_wave of heads.h), so no cumulative sum and no
 // second random number per row, and head_filter is its one top-k / top-p pass.
 
 // One head of one row.  NV registers per lane: v[j] = the logit of this lane's j-th column of the head, cand[j] whether it is a

@@ -9,9 +9,11 @@ cells of a region (`region_mask`) and keeps the other notes (csrc/infill.hip).  
 device (`NoteStats`, csrc/stats.hip), `NoteBatch.select` takes a subset of them, `pick_takes` keeps the best of several takes.
 `NoteBatch.windows` cuts songs into the model's windows as the reference's preprocessing does (preprocess.py:165-205) and
 `NoteBatch.join` puts windows behind each other again (csrc/splice.hip); `encode_song` and `vary_song` take a whole song through
-the VAE on them."""
+the VAE on them.  `score_graph` and `score_notes` give the log-likelihood of pieces under the decoder per bar and track
+(`NoteScores`, csrc/score.hip)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Any
 
@@ -779,3 +781,154 @@ def infill_notes(vae, batch, region, strength=0.0, keep_structure=False, seed=No
         if wanted:
             out += (value,)
     return out
+
+
+@dataclass
+class NoteScores:
+    """What the decoder thinks of pieces (`score_graph`, `score_notes`; csrc/score.hip), device tensors for K latents of B
+    pieces of n_bars bars: `content_logp` float64 [K,B,n_bars,4,2], the summed log-probabilities of the pieces' own pitch and
+    duration tokens per (bar, track); `content_counts` int32 [K,B,n_bars,4,6] = nodes, pitch targets, duration targets, pitch
+    hits, duration hits, note hits; `structure_logp` float64 [K,B,n_bars,4], the Bernoulli log-likelihood of the pieces' own
+    cells; `structure_counts` int32 [K,B,n_bars,4,4] = cells on, predicted on, true positives, cells that agree; `row_logp`, a
+    list of K float32 [N,15,2] (per node and slot); the encoder's `mu`, `log_var` [B,d] and the latents `z` [K,B,d].  The
+    methods are plain torch in float64 and read nothing back."""
+    content_logp: torch.Tensor
+    content_counts: torch.Tensor
+    structure_logp: torch.Tensor
+    structure_counts: torch.Tensor
+    row_logp: list
+    mu: torch.Tensor
+    log_var: torch.Tensor
+    z: torch.Tensor
+
+    def log_likelihood(self, structure: bool = True) -> torch.Tensor:
+        """log p(x | z_k) per piece [K,B]: both heads of every token, with `structure` also the cells."""
+        ll = self.content_logp.sum(dim=(2, 3, 4))
+        return ll + self.structure_logp.sum(dim=(2, 3)) if structure else ll
+
+    def per_bar(self) -> torch.Tensor:
+        """The log-likelihood (tokens and cells) of every bar [K,B,n_bars]: the lowest is the bar the model finds least likely."""
+        return self.content_logp.sum(dim=(3, 4)) + self.structure_logp.sum(dim=3)
+
+    def per_track(self) -> torch.Tensor:
+        """The log-likelihood (tokens and cells) of every track [K,B,4] (Drums, Bass, Guitar, Strings)."""
+        return self.content_logp.sum(dim=(2, 4)) + self.structure_logp.sum(dim=2)
+
+    def nll_per_token(self) -> torch.Tensor:
+        """-log p of the tokens over their number (pitch and duration targets) [K,B]; NaN for a piece without a target."""
+        n = self.content_counts[..., 1:3].sum(dim=(2, 3, 4)).double()
+        return -self.content_logp.sum(dim=(2, 3, 4)) / n
+
+    def perplexity(self) -> torch.Tensor:
+        return torch.exp(self.nll_per_token())
+
+    def accuracies(self) -> dict:
+        """The reference's accuracies (training.py:438-497) per piece, each [K,B] and NaN where its denominator is 0: pitch,
+        dur, note, pitch_drums (track 0), pitch_non_drums, s_precision, s_recall, s_f1."""
+        c = self.content_counts.double().sum(dim=2)                # [K,B,4,6]
+        s = self.structure_counts.double().sum(dim=(2, 3))         # [K,B,4]
+        t = c.sum(dim=2)
+        prec, rec = s[..., 2] / s[..., 1], s[..., 2] / s[..., 0]
+        return {"pitch": t[..., 3] / t[..., 1], "dur": t[..., 4] / t[..., 2], "note": t[..., 5] / t[..., 1],
+                "pitch_drums": c[..., 0, 3] / c[..., 0, 1],
+                "pitch_non_drums": c[..., 1:, 3].sum(dim=2) / c[..., 1:, 1].sum(dim=2),
+                "s_precision": prec, "s_recall": rec, "s_f1": 2 * rec * prec / (rec + prec)}
+
+    def kl(self) -> torch.Tensor:
+        """KL(q(z|x) || N(0, I)) per piece [B]: the formula of training.py:329 without its batch mean."""
+        mu, lv = self.mu.double(), self.log_var.double()
+        return -0.5 * (1 + lv - mu * mu - lv.exp()).sum(dim=1)
+
+    def elbo(self, beta: float = 1.0) -> torch.Tensor:
+        """log p(x | z_k) - beta KL per piece [K,B]."""
+        return self.log_likelihood() - float(beta) * self.kl()
+
+    def iwae(self) -> torch.Tensor:
+        """The importance-weighted bound per piece [B]: logsumexp_k[log p(x|z_k) + log N(z_k; 0, I) - log q(z_k|x)] - log K."""
+        z, mu, lv = self.z.double(), self.mu.double(), self.log_var.double()
+        log_prior = -0.5 * (z * z + math.log(2 * math.pi)).sum(dim=2)
+        log_q = -0.5 * ((z - mu) ** 2 / lv.exp() + lv + math.log(2 * math.pi)).sum(dim=2)
+        return torch.logsumexp(self.log_likelihood() + log_prior - log_q, dim=0) - math.log(z.shape[0])
+
+
+def _check_score_args(vae, graph, z, samples, seed):
+    """The argument rules of `score_graph`, before anything runs."""
+    tokens, s_tensor = getattr(graph, "tokens", None), getattr(graph, "s_tensor", None)
+    if not isinstance(tokens, torch.Tensor) or not isinstance(s_tensor, torch.Tensor):
+        raise ValueError("graph must be a BarGraphBatch with tokens and s_tensor (a DeviceLoader batch, NoteBatch.to_graph())")
+    n_bars, d = vae.cfg["n_bars"], vae.cfg["d"]
+    if getattr(graph, "n_bars", n_bars) != n_bars:
+        raise ValueError(f"graph holds pieces of n_bars = {graph.n_bars}, the model takes n_bars = {n_bars}")
+    if s_tensor.dim() != 3 or s_tensor.shape[1:] != (4, 32) or s_tensor.shape[0] == 0 or s_tensor.shape[0] % n_bars:
+        raise ValueError(f"graph.s_tensor must be [B * {n_bars},4,32], got {tuple(s_tensor.shape)}")
+    _check_latent_args(s_tensor.shape[0] // n_bars, d, z, samples, seed)
+
+
+def _check_latent_args(B, d, z, samples, seed):
+    if not (ops._integer(samples) and samples >= 1):
+        raise ValueError(f"samples must be an int >= 1, got {samples!r}")
+    ops.check_sampling_args(seed=seed)
+    if z is not None:
+        if not isinstance(z, torch.Tensor) or not z.dtype.is_floating_point or z.dim() not in (2, 3) or z.shape[-2:] != (B, d) \
+                or z.shape[0] == 0:
+            raise ValueError(f"z must be a float tensor [{B},{d}] or [K,{B},{d}], got "
+                             f"{tuple(z.shape) if isinstance(z, torch.Tensor) else type(z).__name__}")
+
+
+def _score(vae, graph, mu, log_var, z, samples, seed) -> NoteScores:
+    """The core of `score_graph` and `score_notes`: one decoder pass per latent on the input's own bar graphs, each scored
+    against the input's tokens and structure.  Runs inside the caller's eval / no_grad block."""
+    n_bars = vae.cfg["n_bars"]
+    if z is not None:
+        zs = (z if z.dim() == 3 else z[None]).to(mu.device, torch.float32)
+    elif samples == 1 and seed is None:
+        zs = mu[None]
+    else:
+        gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+        eps = torch.randn((samples,) + tuple(mu.shape), generator=gen, dtype=torch.float32).to(mu.device)
+        zs = mu[None] + torch.exp(0.5 * log_var)[None] * eps
+    s_tensor = graph.s_tensor.view(-1, n_bars, 4, 32)
+    out = [[], [], [], [], []]
+    for zk in zs:
+        s_logits, c_logits = vae.decoder(zk.contiguous(), graph)
+        c_logp, c_counts, row_logp = ops.score_tokens(c_logits.detach().contiguous().float(), graph.tokens, s_tensor, check=False)
+        s_logp, s_counts = ops.score_structure(s_logits.detach().reshape(s_tensor.shape).contiguous().float(), s_tensor)
+        for acc, v in zip(out, (c_logp, c_counts, s_logp, s_counts, row_logp)):
+            acc.append(v)
+    return NoteScores(torch.stack(out[0]), torch.stack(out[1]), torch.stack(out[2]), torch.stack(out[3]), out[4], mu, log_var,
+                      zs.contiguous())
+
+
+def score_graph(vae, graph, z=None, samples=1, seed=None) -> NoteScores:
+    """The log-likelihood of pieces under the model, per bar and track: `graph` is a `BarGraphBatch` with tokens (a
+    `DeviceLoader` batch, `NoteBatch.to_graph()`).  The encoder gives (mu, log_var); every latent z_k is one
+    `vae.decoder(z_k, graph)` pass on the pieces' own bar graphs, whose logits are scored against the pieces' own tokens
+    (`ops.score_tokens`) and cells (`ops.score_structure`).  With `z=None, samples=1` the latent is mu; with `samples=K > 1`, or a
+    `seed`, z_k = mu + exp(log_var / 2) eps_k, eps drawn on the CPU from a generator seeded with `seed` as in `vary_notes`
+    (None with K > 1: torch's global generator); a `z` [B,d] or [K,B,d] overrides both.  Eval mode, no gradients,
+    `vae.training` left as found; no host read.  Returns `NoteScores`."""
+    _check_score_args(vae, graph, z, samples, seed)
+    was_training = vae.training
+    vae.eval()
+    try:
+        with torch.no_grad():
+            mu, log_var = vae.encoder(graph)
+            return _score(vae, graph, mu, log_var, z, samples, seed)
+    finally:
+        vae.train(was_training)
+
+
+def score_notes(vae, batch, z=None, samples=1, seed=None) -> NoteScores:
+    """`score_graph` for pieces held as notes (a `NoteBatch`, checked as by `encode_notes`): the bar to hand to `infill_notes`
+    is `scores.per_bar().argmin(-1)`.  What is scored is what the encoder sees (`NoteBatch.to_graph`: pitches clamped to
+    0..127, durations to 1..96, the first 14 notes of a cell).  No host read beyond those of `to_graph`."""
+    _check_batch(vae, batch)
+    _check_latent_args((batch.track_ptr.shape[0] - 1) // 4, vae.cfg["d"], z, samples, seed)
+    mu, log_var, graph = _encode(vae, batch)
+    was_training = vae.training
+    vae.eval()
+    try:
+        with torch.no_grad():
+            return _score(vae, graph, mu, log_var, z, samples, seed)
+    finally:
+        vae.train(was_training)

@@ -654,6 +654,74 @@ def notes_splice(notes: torch.Tensor, track_ptr: torch.Tensor, src_bars: int, se
     return out, out_ptr, totals, keep, status
 
 
+def _on_device(named) -> None:
+    """HipExtensionError for the first of (tensor, name) that is no device tensor, ValueError when they do not share a device."""
+    for t, name in named:
+        if not t.is_cuda:
+            raise HipExtensionError(f"{name} lives on {t.device}: the HIP path needs device tensors (no CPU fallback)")
+    for t, name in named[1:]:
+        if t.device != named[0][0].device:
+            raise ValueError(f"{name} lives on {t.device}, {named[0][1]} on {named[0][0].device}")
+
+
+def score_tokens(c_logits: torch.Tensor, tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool = True,
+                 return_verdict: bool = False):
+    """`pm_score_tokens` ("Scores" in include/polyphemus_hip.h): the log-likelihood of `tokens` under `c_logits` [N,15,230],
+    per bar and track of `s_tensor` [B,n_bars,4,32] (any dtype), whose active cells are the nodes in cell order.  `tokens` is
+    int32 [N,15,2] (the layout of `sample_tokens`) or [N,16,2] (`tokens_from_notes`, `BarGraphBatch.tokens`: slot 0, the SOS,
+    is no target); a PAD target adds nothing.  Returns (logp float64 [B,n_bars,4,2] = the summed pitch and duration
+    log-probabilities; counts int32 [B,n_bars,4,6] = nodes, pitch targets, duration targets, pitch hits, duration hits, note
+    hits; row_logp float32 [N,15,2]), with `return_verdict` also the rows' verdict bytes uint8 [N,15] (bit 0 pitch hit, 1
+    duration hit, 2 pitch target, 3 duration target).  Bit-identical from call to call, and a bar's numbers do not depend on
+    the rest of the batch.  `check` reads the active-cell count back (one host sync) and raises like `mtp_from_tokens` when it
+    differs from N."""
+    for t, name in ((c_logits, "c_logits"), (tokens, "tokens"), (s_tensor, "s_tensor")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    S = C.MAX_SIMU_TOKENS - 1
+    if c_logits.dtype != F32 or c_logits.dim() != 3 or c_logits.shape[1:] != (S, C.D_TOKEN_PAIR):
+        raise ValueError(f"c_logits must be float32 [N,15,230], got {c_logits.dtype} {tuple(c_logits.shape)}")
+    if tokens.dtype != I32 or tokens.dim() != 3 or tokens.shape[1] not in (S, S + 1) or tokens.shape[2] != 2:
+        raise ValueError(f"tokens must be int32 [N,15,2] or [N,16,2], got {tokens.dtype} {tuple(tokens.shape)}")
+    if tokens.shape[0] != c_logits.shape[0]:
+        raise ValueError(f"tokens has {tokens.shape[0]} nodes, c_logits {c_logits.shape[0]}")
+    s, G, bn, npt = _structure_prologue(
+        s_tensor, c_logits.device, s_tensor.dim() == 4 and 0 not in s_tensor.shape[:2],
+        f"s_tensor must be [B,n_bars,4,32] with B, n_bars >= 1, got {tuple(s_tensor.shape)}")
+    _on_device([(c_logits, "c_logits"), (tokens, "tokens"), (s_tensor, "s_tensor")])
+    c_logits, tokens = c_logits.contiguous(), tokens.contiguous()
+    B, n_bars = s_tensor.shape[:2]
+    N, dev = c_logits.shape[0], c_logits.device
+    row_logp, verdict = torch.empty(N, S, 2, dtype=F32, device=dev), torch.empty(N, S, dtype=U8, device=dev)
+    logp, counts = torch.empty(B, n_bars, 4, 2, dtype=F64, device=dev), torch.empty(B, n_bars, 4, 6, dtype=I32, device=dev)
+    call("pm_score_tokens", ptr(c_logits) if N else None, ptr(tokens) if N else None, tokens.shape[1], ptr(s), G, N, ptr(bn),
+         ptr(npt), ptr(row_logp) if N else None, ptr(verdict) if N else None, ptr(logp), ptr(counts), stream())
+    if check:
+        _check_active(npt[G], N, f"c_logits has {N} nodes")
+    return (logp, counts, row_logp, verdict) if return_verdict else (logp, counts, row_logp)
+
+
+def score_structure(s_logits: torch.Tensor, s_tensor: torch.Tensor):
+    """`pm_score_structure` ("Scores" in include/polyphemus_hip.h): the Bernoulli log-likelihood of the cells of `s_tensor`
+    [B,n_bars,4,32] (any dtype; on = non-zero) under `s_logits` (float32, the same shape), per bar and track.  Returns (logp
+    float64 [B,n_bars,4]; counts int32 [B,n_bars,4,4] = targets on, predictions on, true positives, cells that agree, the
+    prediction being `structure_metrics`').  One launch, no host read; bit-identical from call to call."""
+    for t, name in ((s_logits, "s_logits"), (s_tensor, "s_tensor")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if s_tensor.dim() != 4 or 0 in s_tensor.shape[:2] or s_tensor.shape[2:] != (4, 32):
+        raise ValueError(f"s_tensor must be [B,n_bars,4,32] with B, n_bars >= 1, got {tuple(s_tensor.shape)}")
+    if s_logits.dtype != F32 or s_logits.shape != s_tensor.shape:
+        raise ValueError(f"s_logits must be float32 {tuple(s_tensor.shape)}, got {s_logits.dtype} {tuple(s_logits.shape)}")
+    _on_device([(s_logits, "s_logits"), (s_tensor, "s_tensor")])
+    s_logits, s = s_logits.contiguous(), s_tensor.to(F32).contiguous()
+    B, n_bars = s_tensor.shape[:2]
+    logp = torch.empty(B, n_bars, 4, dtype=F64, device=s_logits.device)
+    counts = torch.empty(B, n_bars, 4, 4, dtype=I32, device=s_logits.device)
+    call("pm_score_structure", ptr(s_logits), ptr(s), B * n_bars, ptr(logp), ptr(counts), stream())
+    return logp, counts
+
+
 def check_chord_args(temperature=None, top_k=None, top_p=None, seed=None, min_notes=1, max_notes=14, allowed_pitches=None,
                      c_logits=None, node_track=None):
     """The argument rules of chord-aware sampling (`sample_chords`, `generate.generate_music(chord_rules=...)`): raises
