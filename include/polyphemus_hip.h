@@ -68,7 +68,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   (pm_sample_tokens, pm_mtp_from_tokens, pm_sample_hash); chord-aware sampling (pm_sample_chords, pm_node_tracks; the
  *   PmChordRules struct); structure sampling (pm_sample_structure; the PmStructureRules struct); note events
  *   (pm_notes_from_tokens); the GCL self block without its round trip (pm_gcl_forward_fused_sel / _sel_h2,
- *   pm_gcl_weight_grad_fused_x / _x_h2: new entry points, no existing argument list changed). */
+ *   pm_gcl_weight_grad_fused_x / _x_h2: new entry points, no existing argument list changed); harmony (pm_node_cells,
+ *   pm_sample_chords_at, pm_note_chroma). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -647,6 +648,58 @@ int pm_score_tokens(const float* c_logits /* [N,15,230] */, const int32_t* token
                     double* logp /* [G,4,2] */, int32_t* counts /* [G,4,6] */, pm_stream_t stream);
 int pm_score_structure(const float* s_logits /* [G,4,32] */, const float* s_tensor /* [G,4,32] */, int32_t G,
                        double* logp /* [G,4] */, int32_t* counts /* [G,4,4] */, pm_stream_t stream);
+
+/* ------------------------------------------------------------------ Harmony
+ * Pitch rules that follow a chord progression, and the harmony of existing pieces read back as such a rule.  The reference
+ * has neither: `generate_music` (generate.py:21-37) decodes every cell on its own and `muspy_from_mtp` (utils.py:126-141)
+ * takes what comes out; the rules of pm_sample_chords are per track and fixed for the batch.  Here a chart of pitch-class
+ * sets per (bar, step) narrows the draw, and pm_note_chroma counts which pitch classes sound where in a batch of pieces
+ * held as notes, so that the harmony of the kept tracks can bind the regenerated ones (an infill) without leaving the
+ * device.  Additive, same ABI version.
+ *
+ * pm_node_cells: node_cell[n] = 128 g + 32 track + step of node n's cell, nodes numbered in cell order as in
+ *   pm_node_tracks, whose scratch, tail rule (entries [active, N) are written 0 by the same launch, nothing at or beyond N)
+ *   and argument checks it shares; in addition node_cell must be 4-byte aligned and 128 G < 2^31.
+ *
+ * pm_sample_chords_at: pm_sample_chords with a chart.  The track of node n is (node_cell[n] >> 5) & 3, its bar
+ *   g = node_cell[n] >> 7 and its step t = node_cell[n] & 31.
+ *   chart      int32 [G,32]: bits 0..11 of chart[g][t] are the pitch classes allowed at step t of bar g; higher bits are
+ *              ignored.
+ *   track_bits bit k set = the chart binds track k (0 Drums .. 3 Strings).
+ *   the pitch rule: for a node of a bound track a pitch p < 128 is a candidate iff pitch_mask[track] allows it AND bit
+ *              p % 12 of chart[g][t] is set (and, as ever, it is not used yet and count < max_notes).  For a track that is
+ *              not bound the chart is not read.  A set that leaves a node no pitch gives the empty chord, (EOS 129, EOS 97)
+ *              in slot 0 and note_count 0, also under min_notes >= 1: the rule pm_sample_chords has for a track whose
+ *              candidates run out.
+ *   Everything else is pm_sample_chords unchanged: the noise stream and its keys, no pitch twice, the note counts, EOS / PAD.
+ *   With track_bits = 0, or with every set 0xfff, the tokens and counts are those of pm_sample_chords bit for bit.
+ *   The chart index 32 g + t is clamped into [0, 32 G), so whatever node_cell holds nothing is read outside `chart`.
+ *   The chart binds onsets: a note drawn at step t is held for its duration whatever the later sets say.
+ *   One wave per node as pm_sample_chords (the same kernel, another instantiation): 4 B of node_cell and, for a bound
+ *   track, 4 B of chart are read per node beside the up to 13.8 KB of logits.
+ *   PM_E_INVALID (before any launch): what pm_sample_chords refuses; NULL node_cell or chart; G <= 0 or 128 G >= 2^31;
+ *   track_bits outside 0..15; c_logits, node_cell, chart, tokens or note_count not 4-byte aligned.
+ *
+ * pm_note_chroma: the chromagram of the NoteBatch layout (notes [M,3], track_ptr [4B+1], pieces of n_bars bars; see "Note
+ *   statistics").  A row counts exactly as in pm_note_stats: 0 <= t < L = 32 n_bars, pitch q = clamp(p, 0, 127), length
+ *   e = clamp(d, 1, 96), sounding over the steps [t, min(t + e, L)); track ranges are clamped into [0, M].
+ *   seg_steps  1, 2, 4, 8, 16 or 32: the steps of a segment; S = 32 n_bars / seg_steps segments per piece.
+ *   chroma     int32 [4B,S,12]: chroma[tr][s][c] = the number of (note, step) pairs of track tr with q % 12 = c whose step
+ *              lies in segment s.  Every word is written on every call; the sum over s and c is NOTE_STEPS of pm_note_stats.
+ *   One launch, a workgroup per (track, chunk of 16 bars): twelve difference arrays of the chunk's 512 steps in LDS (24 KB),
+ *   integer LDS adds, a wave scan and shuffle sums: no global atomics, no workspace, no host read; the result does not
+ *   depend on the order of the rows and two calls on the same input write the same bytes.  12 B are read per row and chunk,
+ *   48 B written per segment and track.  Sums are int32.
+ *   PM_E_INVALID (before any launch): a NULL pointer (notes may be NULL when M == 0); B <= 0; n_bars outside [1, 64];
+ *   seg_steps not one of the six; M < 0; 3 M or 48 B S >= 2^31; a pointer not 4-byte aligned; chroma overlapping an input. */
+int pm_node_cells(const float* s_tensor /* [G,4,32] 0/1 */, int32_t G, int64_t N, int32_t* bar_nodes /* [G] ws */,
+                  int32_t* node_ptr /* [G+1] ws; node_ptr[G] = active cells */, int32_t* node_cell /* [N] */, pm_stream_t stream);
+int pm_sample_chords_at(const float* c_logits /* [N,15,230] */, const int32_t* node_cell /* [N] */, int64_t N,
+                        const int32_t* chart /* [G,32] */, int32_t G, int32_t track_bits, const PmChordRules* rules,
+                        uint32_t seed, int32_t* tokens /* [N,15,2] */, int32_t* note_count /* [N] or NULL */,
+                        pm_stream_t stream);
+int pm_note_chroma(const int32_t* notes /* [M,3] time, pitch, duration */, const int32_t* track_ptr /* [4B+1] */, int32_t B,
+                   int64_t M, int32_t n_bars, int32_t seg_steps, int32_t* chroma /* [4B,S,12] */, pm_stream_t stream);
 
 /* ------------------------------------------------------------------ message aggregation
  * `GCL.message` + PyG `propagate` + torch_scatter mean (model.py:110,123-135):

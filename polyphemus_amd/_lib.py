@@ -194,6 +194,9 @@ _SIGS = {
     "pm_notes_splice": "ppiilpipiipiplppppps",
     "pm_score_tokens": "ppipilpppppps",
     "pm_score_structure": "ppipps",
+    "pm_node_cells": "pilppps",
+    "pm_sample_chords_at": "pplpiipupps",
+    "pm_note_chroma": "ppiliips",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",

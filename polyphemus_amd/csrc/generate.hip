@@ -12,6 +12,7 @@
 //   pm_mtp_from_tokens    : the same pianoroll with an active cell holding the one-hot rows of its node's sampled tokens
 //                           (csrc/sample.hip) instead of its logits: the reference's arg-max decoding then returns the tokens.
 //   pm_node_tracks        : the track index of every node, in the same cell order (the per-track rules of chord-aware sampling).
+//   pm_node_cells         : the cell index of every node, in the same order (the per-(bar, step) rules of pm_sample_chords_at).
 // Byte / index work, bit-exact against the oracle (tests/test_generate_gpu.py, tests/test_sampling_gpu.py).
 #include "bars.h"
 
@@ -118,6 +119,21 @@ __global__ void __launch_bounds__(256) k_node_tracks(const float* __restrict__ s
   if (bl.on1) node_track[bl.n1] = (uint8_t)(2 + (lane >> 5));
 }
 
+// the cell of every node (pm_node_cells): k_node_tracks with the whole cell index 128 g + 32 track + step instead of the
+// track alone, which is what a rule per (bar, step) needs (pm_sample_chords_at).  Same tail rule.
+__global__ void __launch_bounds__(256) k_node_cells(const float* __restrict__ s, const int* __restrict__ node_ptr, int G,
+                                                    int64_t N, int32_t* __restrict__ node_cell) {
+  const int lane = threadIdx.x & 63;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t active = node_ptr[G];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+    if (i >= active) node_cell[i] = 0;
+  if (g >= G) return;                                                           // wave-uniform
+  const BarLanes bl(s, node_ptr, g, lane, N);
+  if (bl.on0) node_cell[bl.n0] = g * 128 + lane;                                // 128 G <= 2^31 - 1 (host check)
+  if (bl.on1) node_cell[bl.n1] = g * 128 + 64 + lane;
+}
+
 }  // namespace
 
 int pm_bar_node_ptr(hipStream_t st, const float* s_tensor, int32_t G, int32_t* bar_nodes, int32_t* node_ptr) {
@@ -157,5 +173,15 @@ extern "C" int pm_node_tracks(const float* s_tensor, int32_t G, int64_t N, int32
   hipStream_t st = (hipStream_t)stream;
   if ((!node_track && N > 0) || N < 0 || pm_bar_node_ptr(st, s_tensor, G, bar_nodes, node_ptr) != PM_OK) return PM_E_INVALID;
   hipLaunchKernelGGL(k_node_tracks, dim3(pm_cdiv(G, 4)), dim3(256), 0, st, s_tensor, node_ptr, G, N, node_track);
+  return pm_check_launch();
+}
+
+extern "C" int pm_node_cells(const float* s_tensor, int32_t G, int64_t N, int32_t* bar_nodes, int32_t* node_ptr,
+                             int32_t* node_cell, pm_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if ((!node_cell && N > 0) || N < 0 || ((uintptr_t)node_cell & 3) != 0 || (int64_t)G * 128 > 0x7fffffffLL ||
+      pm_bar_node_ptr(st, s_tensor, G, bar_nodes, node_ptr) != PM_OK)
+    return PM_E_INVALID;
+  hipLaunchKernelGGL(k_node_cells, dim3(pm_cdiv(G, 4)), dim3(256), 0, st, s_tensor, node_ptr, G, N, node_cell);
   return pm_check_launch();
 }

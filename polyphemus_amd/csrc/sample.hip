@@ -10,6 +10,9 @@
 //   k_sample_chords : chord-aware sampling (PmChordRules): one wave per node, its 15 slots decided in order as notes, one EOS,
 //                     then PAD, under per-track rules (note counts, a pitch mask, no pitch twice): draw_head draws each head
 //                     among the candidates of the slot.
+//                     CHART (pm_sample_chords_at): the node's cell replaces its track, and a chart of pitch-class sets
+//                     per (bar, step) narrows the pitch mask of the tracks it binds: one 4-byte load and two % 12 per
+//                     lane in front of the slot loop, nothing inside it.  pm_sample_chords launches CHART = false.
 //   k_sample_structure : structure sampling (PmStructureRules): which of the 4 x 32 (track, timestep) cells of every bar are active,
 //                     drawn from the structure logits under per-track rules (a bias, the least and the most active cells, the
 //                     allowed timesteps).  A bar per half-wave (HalfBar of bars.h, as k_binary_from_logits): lane t of the half
@@ -199,14 +202,22 @@ __device__ static inline int draw_head(const float (&v)[NV], const int (&tok)[NV
 // predicates on the two registers that hold the pitches below 128 (pitch p = lane p & 63, register p >> 6).  The rows'
 // addresses depend on no decision: the row of slot s + 1 is in flight while slot s is decided, and nothing is read behind
 // the slot that draws the EOS.  Lane l < 30 keeps token l of the node (slot l / 2, head l & 1) and stores it at the end.
-template <int MODE>
-__global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__ c_logits, const uint8_t* __restrict__ node_track,
+// CHART: node_tag[n] is the node's cell 128 g + 32 track + step (int32, pm_node_cells) instead of its track (uint8), and for
+// a track with its bit in track_bits a pitch is a candidate only if bit (pitch % 12) of chart[32 g + step] is set as well.
+// The chart index is clamped into [0, chart_words), so nothing outside `chart` is read whatever node_tag holds; a set that
+// leaves no pitch gives the empty chord by the rule for candidates that run out.  Without CHART the last three arguments are
+// not read.
+template <int MODE, bool CHART>
+__global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__ c_logits,
+                                                       const typename std::conditional<CHART, int32_t, uint8_t>::type* __restrict__ node_tag,
                                                        int64_t N, const PmChordRules R, float inv_tp, float inv_td, int greedy_heads,
-                                                       int top_k, uint32_t seed, int* __restrict__ tokens, int* __restrict__ note_count) {
+                                                       int top_k, uint32_t seed, int* __restrict__ tokens, int* __restrict__ note_count,
+                                                       const int32_t* __restrict__ chart, int chart_words, int track_bits) {
   const int lane = threadIdx.x & 63;
   const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;                                                           // wave-uniform
-  const int t = __builtin_amdgcn_readfirstlane((int)node_track[n]) & 3;
+  const int tag = __builtin_amdgcn_readfirstlane((int)node_tag[n]);
+  const int t = (CHART ? tag >> 5 : tag) & 3;
   int min_n = 0, max_n = 1;
   uint32_t w0 = 0, w1 = 0;                                                      // this lane's words of the track's mask
 #pragma unroll
@@ -215,7 +226,13 @@ __global__ void __launch_bounds__(256) k_sample_chords(const float* __restrict__
       min_n = R.min_notes[k]; max_n = R.max_notes[k];
       w0 = R.pitch_mask[k][lane >> 5]; w1 = R.pitch_mask[k][2 + (lane >> 5)];
     }
-  const bool allow0 = (w0 >> (lane & 31)) & 1u, allow1 = (w1 >> (lane & 31)) & 1u;
+  bool allow0 = (w0 >> (lane & 31)) & 1u, allow1 = (w1 >> (lane & 31)) & 1u;
+  if (CHART && ((track_bits >> t) & 1)) {                                       // (wave-uniform) the chart binds this track
+    const int at = min(max((tag >> 7) * 32 + (tag & 31), 0), chart_words - 1);  // bar tag >> 7, step tag & 31
+    const uint32_t set = (uint32_t)chart[at];
+    allow0 = allow0 && ((set >> (lane % 12)) & 1u);
+    allow1 = allow1 && ((set >> ((lane + 64) % 12)) & 1u);
+  }
   const float* x = c_logits + n * (PM_N_SLOTS * PM_N_TOK);
   const int tokp[3] = {lane, lane + 64, lane + 128};
   const int tokd[2] = {lane - 3, lane + 192 - PM_N_PITCH};
@@ -357,25 +374,52 @@ extern "C" int pm_sample_tokens(const float* c_logits, int64_t rows, float tempe
   return pm_check_launch();
 }
 
-extern "C" int pm_sample_chords(const float* c_logits, const uint8_t* node_track, int64_t N, const PmChordRules* rules,
-                                uint32_t seed, int32_t* tokens, int32_t* note_count, pm_stream_t stream) {
-  if (!c_logits || !node_track || !rules || !tokens || N <= 0 || N * PM_N_SLOTS >= ((int64_t)1 << 32)) return PM_E_INVALID;
-  const PmChordRules R = *rules;
+// the rules every chord entry refuses (PM_E_INVALID before any launch)
+static bool chord_rules_ok(const PmChordRules& R) {
   for (int h = 0; h < 2; ++h)
-    if (!(R.temperature[h] >= 0.f) || !(R.temperature[h] <= 3.4028234663852886e38f)) return PM_E_INVALID;   // NaN, inf, negative
-  if (R.top_k < 0 || !(R.top_p > 0.f) || !(R.top_p <= 1.f)) return PM_E_INVALID;
+    if (!(R.temperature[h] >= 0.f) || !(R.temperature[h] <= 3.4028234663852886e38f)) return false;   // NaN, inf, negative
+  if (R.top_k < 0 || !(R.top_p > 0.f) || !(R.top_p <= 1.f)) return false;
   for (int k = 0; k < 4; ++k)
     if (R.min_notes[k] < 0 || R.max_notes[k] < 1 || R.max_notes[k] > PM_N_SLOTS - 1 || R.min_notes[k] > R.max_notes[k])
-      return PM_E_INVALID;
+      return false;
+  return true;
+}
+
+// the launch of k_sample_chords<MODE, CHART> for checked arguments
+template <bool CHART, class Tag>
+static int launch_chords(const float* c_logits, const Tag* node_tag, int64_t N, const PmChordRules& R, uint32_t seed,
+                         int32_t* tokens, int32_t* note_count, const int32_t* chart, int chart_words, int track_bits,
+                         pm_stream_t stream) {
   const int zero_t = (R.temperature[0] == 0.f ? 1 : 0) | (R.temperature[1] == 0.f ? 2 : 0);
   sample_dispatch(zero_t == 3, R.top_k, R.top_p, [&](auto mode, int kk) {
     const int greedy = decltype(mode)::value == SAMPLE_GREEDY ? 3 : zero_t;
     const float inv_tp = (greedy & 1) ? 1.f : (float)(1.0 / (double)R.temperature[0]);
     const float inv_td = (greedy & 2) ? 1.f : (float)(1.0 / (double)R.temperature[1]);
-    hipLaunchKernelGGL(k_sample_chords<decltype(mode)::value>, dim3((unsigned)pm_cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream,
-                       c_logits, node_track, N, R, inv_tp, inv_td, greedy, kk, seed, tokens, note_count);
+    hipLaunchKernelGGL((k_sample_chords<decltype(mode)::value, CHART>), dim3((unsigned)pm_cdiv(N, 4)), dim3(256), 0,
+                       (hipStream_t)stream, c_logits, node_tag, N, R, inv_tp, inv_td, greedy, kk, seed, tokens, note_count, chart,
+                       chart_words, track_bits);
   });
   return pm_check_launch();
+}
+
+extern "C" int pm_sample_chords(const float* c_logits, const uint8_t* node_track, int64_t N, const PmChordRules* rules,
+                                uint32_t seed, int32_t* tokens, int32_t* note_count, pm_stream_t stream) {
+  if (!c_logits || !node_track || !rules || !tokens || N <= 0 || N * PM_N_SLOTS >= ((int64_t)1 << 32)) return PM_E_INVALID;
+  const PmChordRules R = *rules;
+  if (!chord_rules_ok(R)) return PM_E_INVALID;
+  return launch_chords<false>(c_logits, node_track, N, R, seed, tokens, note_count, nullptr, 0, 0, stream);
+}
+
+extern "C" int pm_sample_chords_at(const float* c_logits, const int32_t* node_cell, int64_t N, const int32_t* chart, int32_t G,
+                                   int32_t track_bits, const PmChordRules* rules, uint32_t seed, int32_t* tokens,
+                                   int32_t* note_count, pm_stream_t stream) {
+  if (!c_logits || !node_cell || !chart || !rules || !tokens || N <= 0 || N * PM_N_SLOTS >= ((int64_t)1 << 32)) return PM_E_INVALID;
+  if (G <= 0 || (int64_t)G * 128 > 0x7fffffffLL || track_bits < 0 || track_bits > 15) return PM_E_INVALID;
+  if ((((uintptr_t)c_logits | (uintptr_t)node_cell | (uintptr_t)chart | (uintptr_t)tokens | (uintptr_t)note_count) & 3) != 0)
+    return PM_E_INVALID;
+  const PmChordRules R = *rules;
+  if (!chord_rules_ok(R)) return PM_E_INVALID;
+  return launch_chords<true>(c_logits, node_cell, N, R, seed, tokens, note_count, chart, 32 * G, track_bits, stream);
 }
 
 extern "C" int pm_sample_structure(const float* s_logits, int32_t G, const PmStructureRules* rules, uint32_t seed, float* s_f32,

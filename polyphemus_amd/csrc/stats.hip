@@ -1,4 +1,5 @@
-// stats.hip — what a NoteBatch holds, counted on the device (pm_note_stats), and a subset of its pieces (pm_notes_select).
+// stats.hip — what a NoteBatch holds, counted on the device (pm_note_stats, pm_note_chroma), and a subset of its pieces
+// (pm_notes_select).
 //
 // pm_note_stats: the small integer reductions behind the usual objective measures of symbolic music (pitch range, pitches and
 // pitch classes used, polyphony, empty beats, groove: muspy.metrics), per (piece, track), from the rows the encoder would see.
@@ -13,6 +14,17 @@
 //               give the onset and sounding masks (two 32-bit words per 64 steps) and the step counts, a running maximum the
 //               largest chord and polyphony.  Sums, minima, maxima and the 128-bit pitch set end in wave reductions.
 //   One launch, no global atomics, no workspace: 12 B read per row, 96 + 8 n_bars B written per track, every word on every call.
+//
+// pm_note_chroma: the chromagram of a NoteBatch, chroma[track][segment][pitch class] = the (note, step) pairs of that class
+// sounding in the segment (segments of 1 .. 32 steps), by the row rule of pm_note_stats.
+//   layout    : per-pitch-class difference arrays over a chunk of 16 bars per workgroup (12 x 512 int32 = 24 KB of LDS; the
+//               whole piece at n_bars = 64 would need 96 KB per track), grid (4 B tracks, ceil(n_bars / 16) chunks), 256 threads
+//               striding over the track's rows and clipping every note to the chunk.  A smaller chunk would read the rows
+//               more often (every chunk reads all rows of its track: at most 4 x 12 B per row), a larger one would leave the
+//               64 KB budget with less than two workgroups per CU; 16 bars keeps short pieces (n_bars <= 16) at one read.
+//   sums      : integer LDS adds, a wave prefix sum per class and xor-shuffle sums per segment: no global atomics, no
+//               workspace, every word written by exactly one workgroup on every call, bit-identical from call to call.
+//   One launch: 12 B read per row and chunk, 48 B written per segment and track, as coalesced runs.
 //
 // pm_notes_select: pieces index[0..K) of a NoteBatch as a NoteBatch.  first[b] = lowest position j with index[j] = b (an
 // integer minimum, so it does not depend on arrival order); output piece j is piece index[j] iff that is in [0, B) and
@@ -147,6 +159,57 @@ __global__ void __launch_bounds__(256) k_note_stats(const int32_t* __restrict__ 
   }
 }
 
+// pm_note_chroma: a workgroup per (track, chunk of CHROMA_BARS bars).  diff[c][x] is the difference array of the notes of
+// pitch class c sounding at step x of the chunk; every thread strides over the track's rows and clips a note to the chunk
+// (a note that began before the chunk starts at its step 0, so no carry crosses chunks).  Wave w then scans the classes
+// w, w + 4, w + 8, 64 steps at a time, sums the counts of every segment with xor shuffles (a segment is an aligned power of
+// two of at most 32 lanes) and leaves them in place at diff[c][segment of the chunk]: the segments written in one round lie
+// at or below the steps read in it and above those written in the round before.  The whole block stores them as one
+// contiguous run of chroma words.
+constexpr int CHROMA_BARS = 16;
+
+__global__ void __launch_bounds__(256) k_note_chroma(const int32_t* __restrict__ notes, const int32_t* __restrict__ track_ptr,
+                                                     int n_bars, int M, int seg_steps, int32_t* __restrict__ chroma) {
+  extern __shared__ int lds[];                                                  // [12][CH]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, L = 32 * n_bars;
+  const int CH = 32 * min(n_bars, CHROMA_BARS);                                 // steps of a whole chunk
+  const int64_t tr = blockIdx.x;                                                // tr < 4 B
+  const int c0 = (int)blockIdx.y * CH, c1 = min(c0 + CH, L), len = c1 - c0;     // this chunk: steps [c0, c1), 0 < len <= CH
+  for (int i = threadIdx.x; i < N_PC * CH; i += 256) lds[i] = 0;
+  __syncthreads();
+
+  const TrackRange r(track_ptr, tr, M);
+  for (int i = r.lo + (int)threadIdx.x; i < r.hi; i += 256) {                   // lo <= i < hi <= M
+    const int32_t* row = notes + 3 * (int64_t)i;
+    const int t = row[0], q = min(max(row[1], 0), MAX_PITCH), e = min(max(row[2], 1), MAX_DUR);
+    if ((unsigned)t >= (unsigned)L) continue;
+    const int from = max(t, c0), to = min(min(t + e, L), c1);
+    if (from >= to) continue;                                                   // the note does not sound in this chunk
+    int* diff = lds + (q % 12) * CH;
+    atomicAdd(&diff[from - c0], 1);                                             // 0 <= from - c0 < len
+    if (to < c1) atomicAdd(&diff[to - c0], -1);                                 // 0 < to - c0 < len
+  }
+  __syncthreads();
+
+  for (int c = wave; c < N_PC; c += 4) {
+    int* diff = lds + c * CH;
+    int carry = 0;
+    for (int base = 0; base < len; base += 64) {                                // wave-uniform; len is a multiple of 32
+      const int x = base + lane;
+      const int inc = wave_inclusive(x < len ? diff[x] : 0, lane);
+      int cur = x < len ? carry + inc : 0;                                      // notes of class c sounding at step c0 + x
+      carry += __shfl(inc, 63, 64);
+      for (int o = 1; o < seg_steps; o <<= 1) cur += __shfl_xor(cur, o, 64);
+      if (x < len && (lane & (seg_steps - 1)) == 0) diff[x / seg_steps] = cur;
+    }
+  }
+  __syncthreads();
+
+  const int S = L / seg_steps, segs = len / seg_steps;                          // segments of the piece, of this chunk
+  int32_t* out = chroma + (tr * S + c0 / seg_steps) * N_PC;
+  for (int i = threadIdx.x; i < segs * N_PC; i += 256) out[i] = lds[(i % N_PC) * CH + i / N_PC];
+}
+
 __global__ void __launch_bounds__(256) k_select_init(int* __restrict__ first, int B) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b < B) first[b] = INT_MAX;
@@ -258,6 +321,21 @@ extern "C" int pm_note_stats(const int32_t* notes, const int32_t* track_ptr, int
   const size_t lds = 4 * 2 * 32 * (size_t)n_bars * sizeof(int);                 // at most 64 KB
   hipLaunchKernelGGL(k_note_stats, dim3(B), dim3(256), lds, (hipStream_t)stream, notes, track_ptr, n_bars, (int)M, track,
                      pitch_class, onsets, sounding);
+  return pm_check_launch();
+}
+
+extern "C" int pm_note_chroma(const int32_t* notes, const int32_t* track_ptr, int32_t B, int64_t M, int32_t n_bars,
+                              int32_t seg_steps, int32_t* chroma, pm_stream_t stream) {
+  if ((!notes && M > 0) || !track_ptr || !chroma || B <= 0 || n_bars < 1 || n_bars > MAX_BARS || M < 0) return PM_E_INVALID;
+  if (seg_steps < 1 || seg_steps > 32 || (seg_steps & (seg_steps - 1)) != 0) return PM_E_INVALID;
+  const int64_t tracks = 4 * (int64_t)B, words = tracks * (32 * n_bars / seg_steps) * N_PC;
+  if (M > 0x7fffffffLL / 3 || words > 0x7fffffffLL) return PM_E_INVALID;
+  const Buf buf[3] = {{notes, 3 * M, false}, {track_ptr, tracks + 1, false}, {chroma, words, true}};
+  if (misaligned(buf, 3) || clash(buf, 3)) return PM_E_INVALID;
+  const int chunk_bars = n_bars < CHROMA_BARS ? n_bars : CHROMA_BARS;
+  const size_t lds = (size_t)N_PC * 32 * chunk_bars * sizeof(int);              // at most 24 KB
+  hipLaunchKernelGGL(k_note_chroma, dim3((unsigned)tracks, (unsigned)pm_cdiv(n_bars, CHROMA_BARS)), dim3(256), lds,
+                     (hipStream_t)stream, notes, track_ptr, n_bars, (int)M, seg_steps, chroma);
   return pm_check_launch();
 }
 

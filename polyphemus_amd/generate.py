@@ -10,10 +10,13 @@ device (`NoteStats`, csrc/stats.hip), `NoteBatch.select` takes a subset of them,
 `NoteBatch.windows` cuts songs into the model's windows as the reference's preprocessing does (preprocess.py:165-205) and
 `NoteBatch.join` puts windows behind each other again (csrc/splice.hip); `encode_song` and `vary_song` take a whole song through
 the VAE on them.  `score_graph` and `score_notes` give the log-likelihood of pieces under the decoder per bar and track
-(`NoteScores`, csrc/score.hip)."""
+(`NoteScores`, csrc/score.hip).  `Harmony` (pitch-class sets per bar and segment, `harmony=` of the generation calls) makes the
+chords follow a progression, and `NoteBatch.chroma` / `NoteBatch.harmony` read the harmony of existing pieces on the device, so that
+an infill can follow what the kept tracks play (csrc/sample.hip, csrc/stats.hip)."""
 from __future__ import annotations
 
 import math
+import re
 from dataclasses import dataclass
 from typing import Any
 
@@ -70,6 +73,122 @@ def step_mask(every: int = 1, offset: int = 0, lo: int = 0, hi: int = 31) -> np.
     return (t >= lo) & (t <= hi) & (t >= offset) & ((t - offset) % int(every) == 0)
 
 
+MAJOR_SCALE = (0, 2, 4, 5, 7, 9, 11)
+MINOR_SCALE = (0, 2, 3, 5, 7, 8, 10)                             # the natural minor
+CHORD_QUALITIES = {"": (0, 4, 7), "m": (0, 3, 7), "7": (0, 4, 7, 10), "maj7": (0, 4, 7, 11), "m7": (0, 3, 7, 10),
+                   "dim": (0, 3, 6), "aug": (0, 4, 8), "sus2": (0, 2, 7), "sus4": (0, 5, 7), "5": (0, 7)}
+FREE_SET = 0xFFF                                                 # every pitch class: no constraint
+_ROOTS = {"C": 0, "D": 2, "E": 4, "F": 5, "G": 7, "A": 9, "B": 11}
+_SYMBOL = re.compile(r"^([A-G])([#b]?)(maj7|m7|m|7|dim|aug|sus2|sus4|5|)$")
+
+
+def _set_of(root: int, intervals) -> int:
+    return sum(1 << ((root + k) % 12) for k in intervals)
+
+
+class Harmony:
+    """A chord progression as pitch-class sets per cell (`harmony=` of `generate_music`, `generate_notes`, `vary_notes`,
+    `infill_notes`, `vary_song` and, through its keywords, `pick_takes`; `ops.sample_chords_at`).  `sets` is an int tensor or
+    array-like [n_bars,S] (shared by all pieces) or [B,n_bars,S]: S in {1, 2, 4, 8, 16, 32} sets per bar, each lasting 32 / S
+    steps, values in [0, 4096) with bit c set = pitch class c (0 = C) may be drawn.  `tracks` (names from TRACKS or indices
+    0..3) are the tracks the sets bind; the drums are left alone by default.  `empty="free"` turns a set of 0 into "no
+    constraint" (0xfff), `"rest"` keeps it: the bound tracks then draw no note there.  The sets bind the onsets of the drawn
+    notes; a note held into the next segment is not cut.  Bad arguments raise ValueError before a device is touched (the
+    values of a device tensor are not read: bits above 11 are ignored).  `from_chords` parses chord symbols and
+    `NoteBatch.harmony` reads the sets of existing pieces."""
+
+    def __init__(self, sets, tracks=("Bass", "Guitar", "Strings"), empty="free"):
+        self.sets, self.track_bits = ops.check_harmony_args(sets, tracks, empty)
+        self.tracks, self.empty = tuple(tracks), empty
+
+    def __repr__(self):
+        return f"Harmony(sets={tuple(self.sets.shape)} on {self.sets.device}, tracks={self.tracks!r}, empty={self.empty!r})"
+
+    @property
+    def n_bars(self) -> int:
+        return int(self.sets.shape[-2])
+
+    @property
+    def per_bar(self) -> int:
+        return int(self.sets.shape[-1])
+
+    @classmethod
+    def from_chords(cls, symbols, n_bars: int, per_bar: int = 1, scale=None, tracks=("Bass", "Guitar", "Strings"),
+                    empty="free") -> "Harmony":
+        """The sets of chord symbols, parsed on the host: `symbols` is a list of `n_bars * per_bar` strings (`per_bar` in
+        {1, 2, 4, 8, 16, 32} chords per bar, each lasting 32 / per_bar steps), a root A..G with an optional # or b and one
+        of the qualities "" (major), m, 7, maj7, m7, dim, aug, sus2, sus4, 5; "N" is no chord: every pitch class (0xfff).
+        With `scale="major"` or `"minor"` (natural) a symbol gives the seven-note scale on its root instead of its chord
+        tones.  Raises ValueError naming a symbol it cannot read."""
+        if not (ops._integer(n_bars) and n_bars >= 1):
+            raise ValueError(f"n_bars must be an int >= 1, got {n_bars!r}")
+        if not (ops._integer(per_bar) and per_bar in ops.SEG_STEPS):
+            raise ValueError(f"per_bar must be one of {ops.SEG_STEPS}, got {per_bar!r}")
+        if scale not in (None, "major", "minor"):
+            raise ValueError(f"scale must be None, 'major' or 'minor', got {scale!r}")
+        if isinstance(symbols, (str, bytes)) or not isinstance(symbols, (list, tuple)):
+            raise ValueError(f"symbols must be a list of chord symbols, got {symbols!r}")
+        if len(symbols) != n_bars * per_bar:
+            raise ValueError(f"symbols must hold n_bars * per_bar = {n_bars * per_bar} chords, got {len(symbols)}")
+        out = []
+        for sym in symbols:
+            m = _SYMBOL.match(sym) if isinstance(sym, str) else None
+            if sym == "N":
+                out.append(FREE_SET)
+            elif m is None:
+                raise ValueError(f"cannot read the chord symbol {sym!r}: a root A..G, an optional # or b and one of "
+                                 f"{sorted(CHORD_QUALITIES)}, or 'N'")
+            else:
+                root = (_ROOTS[m.group(1)] + {"": 0, "#": 1, "b": -1}[m.group(2)]) % 12
+                steps = CHORD_QUALITIES[m.group(3)] if scale is None else (MAJOR_SCALE if scale == "major" else MINOR_SCALE)
+                out.append(_set_of(root, steps))
+        return cls(np.asarray(out, np.int64).reshape(int(n_bars), int(per_bar)), tracks, empty)
+
+    def check_fit(self, B: int, n_bars: int) -> None:
+        """ValueError unless the sets fit a call on B pieces of n_bars bars."""
+        ops.check_harmony_args(self.sets, self.tracks, self.empty, B=B, n_bars=n_bars)
+
+    def chart(self, B: int, n_bars: int, device) -> torch.Tensor:
+        """The sets as the int32 [B * n_bars, 32] chart `ops.sample_chords_at` reads (a set per step of every bar), built
+        with torch ops on `device`: no host read."""
+        self.check_fit(B, n_bars)
+        s = self.sets.to(device).to(torch.int32) & FREE_SET
+        if self.empty == "free":
+            s = torch.where(s == 0, torch.full_like(s, FREE_SET), s)
+        s = s.repeat_interleave(32 // self.per_bar, dim=-1)
+        if s.dim() == 2:
+            s = s.unsqueeze(0).expand(B, n_bars, 32)
+        return s.reshape(B * n_bars, 32).contiguous()
+
+    def _like(self, sets) -> "Harmony":
+        return Harmony(sets, self.tracks, self.empty)
+
+    def repeated(self, takes: int) -> "Harmony":
+        """The harmony of `z.repeat_interleave(takes, 0)`: sets per piece are repeated per take, shared sets stay."""
+        return self if self.sets.dim() == 2 else self._like(self.sets.repeat_interleave(int(takes), 0))
+
+    def windows(self, B: int, W: int) -> "Harmony":
+        """A harmony over the bars of B songs cut into the ceil(n_bars / W) windows of W bars `vary_song` decodes, [B * S, W,
+        per_bar] in its order (the windows of a song behind each other); the last window is padded with free sets."""
+        S = -(-self.n_bars // W)
+        s = self.sets if self.sets.dim() == 3 else self.sets.unsqueeze(0).expand(B, -1, -1)
+        pad = s.new_full((B, S * W - self.n_bars, self.per_bar), FREE_SET)
+        if self.empty == "free":                                 # (a set of 0 stays what it is under "rest" only)
+            s = torch.where(s == 0, torch.full_like(s, FREE_SET), s)
+        return self._like(torch.cat([s, pad], 1).reshape(B * S, W, self.per_bar))
+
+
+def _check_harmony(harmony, chord_rules, B, n_bars):
+    """The checks of `harmony=` before the model is touched; returns the chord rules of the call: a harmony selects
+    chord-aware sampling, so without `chord_rules` it means `ChordRules()`."""
+    if harmony is None:
+        return chord_rules
+    if not isinstance(harmony, Harmony):
+        raise ValueError(f"harmony must be a Harmony, got {harmony!r}")
+    harmony.check_fit(B, n_bars)
+    return ChordRules() if chord_rules is None else chord_rules
+
+
 def _model_structure(vae, z, rules, seed):
     """the model's own structure for z, bool [B,n_bars,4,32]: drawn on the device from the structure logits under `rules` (a
     StructureRules) and `seed`, or, without rules, thresholded as `Decoder.forward` does it"""
@@ -102,7 +221,7 @@ def _decode(vae, z, s_cond, s_tensor_cond, rules=None, seed=None):
 
 
 def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
-                   return_tokens=False, chord_rules=None, return_note_counts=False, structure_rules=None):
+                   return_tokens=False, chord_rules=None, return_note_counts=False, structure_rules=None, harmony=None):
     """generate.py:21-37.  `s_cond` is a batch of bar graphs (`vae.decoder._structure_from_binary`) or None (the
     structure then comes from the decoder's own thresholded logits); `s_tensor_cond` [B,n_bars,4,32] is the binary
     structure the pianoroll is laid out on when given.  Returns (mtp [B,n_bars,4,32,15,230], s_tensor bool).
@@ -125,9 +244,15 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
     cells, allowed steps) instead of thresholded: the content decoder runs on the drawn structure, the pianoroll is laid out
     on it and it is the `s_tensor` returned.  It combines with every content mode above.  One `seed` drives both levels
     (None draws one, once); the bars are numbered along the batch, so a `z` that repeats one latent gives several takes
-    with different rhythms.  No host read is added to the one that sizes the bar graphs."""
+    with different rhythms.  No host read is added to the one that sizes the bar graphs.
+
+    With `harmony` (a `Harmony`: pitch-class sets per bar and segment, for all pieces or per piece) the chords follow a
+    progression: the call samples chord by chord as with `chord_rules` (None then means `ChordRules()`), and a pitch of a
+    track the harmony binds must also have its class in the set of its cell (`ops.sample_chords_at`).  It combines with
+    every mode above.  A harmony that does not fit z's B or the model's n_bars raises before the model is touched."""
     tokens, s_tensor, note_count, c_logits = _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed,
-                                                              chord_rules, structure_rules, return_note_counts, return_tokens)
+                                                              chord_rules, structure_rules, return_note_counts, return_tokens,
+                                                              harmony)
     if c_logits is not None:                                     # the reference's call: the active cells hold the logits
         mtp = ops.mtp_from_logits(c_logits, s_tensor)
     else:
@@ -141,16 +266,19 @@ def generate_music(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None,
 
 
 def _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules, structure_rules,
-                     return_note_counts=False, argmax_tokens=True):
+                     return_note_counts=False, argmax_tokens=True, harmony=None):
     """The part `generate_music` and `generate_notes` share: the argument checks, the seed, the decoder pass and the draw.
     Returns (tokens int32 [N,15,2], s_tensor, note_count int32 [N] or None without chord rules, c_logits): c_logits is None
     in every sampled mode; in the unsampled one it holds the content logits and `tokens` their arg-max (None when
     `argmax_tokens` is off: the caller lays the logits out and wants no tokens)."""
+    if harmony is not None:
+        chord_rules = _check_harmony(harmony, chord_rules, z.shape[0], vae.cfg["n_bars"])
     sampled = _check_draw(s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules, structure_rules, return_note_counts)
     if structure_rules is not None and seed is None:             # one seed for both levels, drawn before the structure
         seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
     c_logits, s_tensor = _decode(vae, z, s_cond, s_tensor_cond, structure_rules, seed)
-    tokens, note_count, c_logits = _draw(c_logits, s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules, argmax_tokens)
+    tokens, note_count, c_logits = _draw(c_logits, s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules, argmax_tokens,
+                                         harmony)
     return tokens, s_tensor, note_count, c_logits
 
 
@@ -175,15 +303,23 @@ def _check_draw(s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_ru
     return temperature is not None or top_k is not None or top_p is not None
 
 
-def _draw(c_logits, s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules, argmax_tokens=True):
+def _draw(c_logits, s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules, argmax_tokens=True, harmony=None):
     """The draw of `_decode_and_draw` on the content logits of the nodes of `s_tensor`, in the mode `_check_draw` found:
-    (tokens, note_count, c_logits) as `_decode_and_draw` returns them.  A `seed` of None is drawn here."""
+    (tokens, note_count, c_logits) as `_decode_and_draw` returns them.  A `seed` of None is drawn here.  With `harmony` (a
+    checked Harmony; `chord_rules` is then set) the chords are drawn under its chart on s_tensor [B,n_bars,4,32]."""
     if not sampled:
         return (ops.sample_tokens(c_logits, temperature=0.0) if argmax_tokens else None), None, c_logits
     if seed is None:
         seed = int(torch.randint(0, 1 << 32, (1,), dtype=torch.int64).item())
     if chord_rules is None:
         return ops.sample_tokens(c_logits, 1.0 if temperature is None else temperature, top_k, top_p, seed), None, None
+    if harmony is not None:
+        cells = ops.node_cells(s_tensor, c_logits.shape[0], check=False)
+        chart = harmony.chart(s_tensor.shape[0], s_tensor.shape[1], c_logits.device)
+        tokens, note_count = ops.sample_chords_at(c_logits, cells, chart, harmony.track_bits,
+                                                  1.0 if temperature is None else temperature, top_k, top_p, seed,
+                                                  chord_rules.min_notes, chord_rules.max_notes, chord_rules.allowed_pitches)
+        return tokens, note_count, None
     track = ops.node_tracks(s_tensor, c_logits.shape[0], check=False)
     tokens, note_count = ops.sample_chords(c_logits, track, 1.0 if temperature is None else temperature, top_k, top_p, seed,
                                            chord_rules.min_notes, chord_rules.max_notes, chord_rules.allowed_pitches)
@@ -276,6 +412,37 @@ class NoteBatch:
         B = track.shape[0] // 4
         return NoteStats(track.view(B, 4, -1), pitch_class.view(B, 4, 12), onsets.view(B, 4, -1), sounding.view(B, 4, -1),
                          self.n_bars, self.resolution)
+
+    def chroma(self, seg_steps: int = 32) -> torch.Tensor:
+        """The chromagram of the pieces, int32 [B,4,S,12] with S = 32 n_bars / `seg_steps` (1, 2, 4, 8, 16 or 32 steps per
+        segment): how many (note, step) pairs of every pitch class sound in each segment of each track, notes read as
+        `stats()` reads them (`ops.note_chroma`, csrc/stats.hip).  One launch, no host read."""
+        c = ops.note_chroma(self.notes, self.track_ptr, self.n_bars, seg_steps)
+        return c.view(c.shape[0] // 4, 4, c.shape[1], 12)
+
+    def harmony(self, seg_steps: int = 32, tracks=("Bass", "Guitar", "Strings"), snap=None) -> "Harmony":
+        """The harmony the pieces play, as a `Harmony` with sets [B,n_bars,32 / seg_steps]: the pitch classes sounding in
+        `tracks` (names from TRACKS or indices 0..3) in every segment of `seg_steps` steps, from `chroma()` with torch ops on
+        the device (no host read).  A segment in which those tracks are silent has the set 0, which the default
+        `empty="free"` of the result reads as no constraint.  `snap="triad"` replaces every other set by the best of the 24
+        major and minor triads: the chroma weight inside the triad minus the weight outside it, ties to the lowest template
+        (the major triads on C..B, then the minor ones).  The result binds Bass, Guitar and Strings, whatever `tracks` it was
+        read from: `Harmony(h.sets, tracks=..., empty=...)` binds otherwise."""
+        if snap not in (None, "triad"):
+            raise ValueError(f"snap must be None or 'triad', got {snap!r}")
+        _, bits = ops.check_harmony_args(np.zeros((1, 1), np.int64), tracks)
+        c = self.chroma(seg_steps).to(torch.int64)                                    # [B,4,S,12]
+        dev = c.device
+        use = torch.tensor([(bits >> k) & 1 for k in range(4)], dtype=torch.int64).to(dev)
+        w = (c * use.view(1, 4, 1, 1)).sum(1)                                         # [B,S,12]
+        sets = ((w > 0).to(torch.int64) << torch.arange(12, dtype=torch.int64, device=dev)).sum(-1)
+        if snap == "triad":
+            triads = [_set_of(r, CHORD_QUALITIES[q]) for q in ("", "m") for r in range(12)]
+            inside = torch.tensor([[(t >> k) & 1 for k in range(12)] for t in triads], dtype=torch.int64).to(dev)       # [24,12]
+            score = 2 * (w.unsqueeze(-2) * inside).sum(-1) - w.sum(-1, keepdim=True)                                  # [B,S,24]
+            best = (score * 24 + torch.arange(23, -1, -1, dtype=torch.int64, device=dev)).argmax(-1)                  # (distinct keys)
+            sets = torch.where(sets > 0, torch.tensor(triads, dtype=torch.int64).to(dev)[best], sets)
+        return Harmony(sets.view(c.shape[0], self.n_bars, 32 // int(seg_steps)))
 
     def select(self, index, check: bool = True) -> "NoteBatch":
         """The pieces `index[0..K)` (an int32 or int64 tensor or a list; entries in [0, B), distinct) as a NoteBatch of their
@@ -442,9 +609,6 @@ class WindowIndex:
     shift: torch.Tensor
 
 
-MAJOR_SCALE = (0, 2, 4, 5, 7, 9, 11)
-
-
 @dataclass
 class NoteStats:
     """The counts of `NoteBatch.stats()` (`ops.note_stats`, "Note statistics" in include/polyphemus_hip.h), int32 on the
@@ -533,7 +697,7 @@ def pick_takes(vae, z, takes: int, key, **generate_notes_kwargs):
     sampling or `structure_rules` is what makes takes differ), `key(stats)` gets the `NoteStats` of the B * takes pieces and
     returns a float tensor [B * takes] on their device, higher is better; NaN counts as -inf.  Of each group of `takes`
     consecutive rows the best is kept, ties go to the lowest row.  `s_cond` (bar graphs) and `s_tensor_cond` [B,n_bars,4,32],
-    if given, are repeated as `z` is.  Returns (NoteBatch of B pieces, s_tensor [B,n_bars,4,32] of the winners, chosen int64 [B]:
+    if given, are repeated as `z` is, and so are the sets of a `harmony` that has them per piece.  Returns (NoteBatch of B pieces, s_tensor [B,n_bars,4,32] of the winners, chosen int64 [B]:
     the row of each winner among the B * takes).  No host read beyond `generate_notes`' own."""
     if not (ops._integer(takes) and takes >= 1):
         raise ValueError(f"takes must be an int >= 1, got {takes!r}")
@@ -547,6 +711,9 @@ def pick_takes(vae, z, takes: int, key, **generate_notes_kwargs):
     takes, B = int(takes), z.shape[0]
     kw = dict(generate_notes_kwargs)
     s_cond, s_tensor_cond = kw.pop("s_cond", None), kw.pop("s_tensor_cond", None)
+    if isinstance(kw.get("harmony"), Harmony):                   # sets per piece are repeated as `z` is
+        kw["harmony"].check_fit(B, kw["harmony"].n_bars)
+        kw["harmony"] = kw["harmony"].repeated(takes)
     if s_tensor_cond is not None:
         s_tensor_cond = s_tensor_cond.repeat_interleave(takes, 0)
     if s_cond is not None:                                       # the bar graphs of the repeated structure
@@ -564,14 +731,14 @@ def pick_takes(vae, z, takes: int, key, **generate_notes_kwargs):
 
 
 def generate_notes(vae, z, s_cond=None, s_tensor_cond=None, *, temperature=None, top_k=None, top_p=None, seed=None,
-                   chord_rules=None, structure_rules=None, return_tokens=False):
+                   chord_rules=None, structure_rules=None, return_tokens=False, harmony=None):
     """`generate_music` without the pianoroll: the same arguments, checks, seed handling and draws in every mode (unsampled =
     the arg-max tokens), but the pieces come back as a `NoteBatch` — the notes the reference's `muspy_from_mtp` would read out
     of `generate_music`'s `mtp`, in its order — read from the tokens on the device (`ops.notes_from_tokens`).  Returns
     (NoteBatch, s_tensor), with `return_tokens` the int32 [N,15,2] tokens appended.  One host read beyond the one that sizes
     the bar graphs: the check that the structure has as many active cells as the decoder gave nodes."""
     tokens, s_tensor, _, _ = _decode_and_draw(vae, z, s_cond, s_tensor_cond, temperature, top_k, top_p, seed, chord_rules,
-                                              structure_rules)
+                                              structure_rules, harmony=harmony)
     notes, track_ptr, totals = ops.notes_from_tokens(tokens, s_tensor)
     batch = NoteBatch(notes, track_ptr, totals, int(s_tensor.shape[1]))
     return (batch, s_tensor, tokens) if return_tokens else (batch, s_tensor)
@@ -611,8 +778,8 @@ def vary_notes(vae, batch, strength=1.0, keep_structure=False, seed=None, return
     torch's global generator; the same `seed` goes on to `generate_notes` for all its levels.  `strength` is finite and >= 0;
     0 is the reconstruction at mu.  `keep_structure` decodes on the input's own structure (its bar graphs as `s_cond`, its
     cells as `s_tensor_cond`): same rhythm, new notes; it excludes `structure_rules` with the error `generate_music` raises.
-    Every other keyword is `generate_notes`'.  Returns what `generate_notes` returns, (NoteBatch, s_tensor[, tokens]), with
-    `return_z` the latent appended."""
+    Every other keyword is `generate_notes`', `harmony=` among them.  Returns what `generate_notes` returns, (NoteBatch,
+    s_tensor[, tokens]), with `return_z` the latent appended."""
     if not (ops._real(strength) and np.isfinite(strength) and strength >= 0):
         raise ValueError(f"strength must be a finite number >= 0, got {strength!r}")
     ops.check_sampling_args(seed=seed)
@@ -621,6 +788,9 @@ def vary_notes(vae, batch, strength=1.0, keep_structure=False, seed=None, return
             raise ValueError(f"{k} is not an argument of vary_notes: keep_structure=True passes the input's structure")
     if keep_structure and generate_notes_kwargs.get("structure_rules") is not None:
         raise ValueError("structure_rules draws the structure itself: it needs s_cond and s_tensor_cond both None")
+    if generate_notes_kwargs.get("harmony") is not None:         # before the encoder runs
+        _check_batch(vae, batch)
+        _check_harmony(generate_notes_kwargs["harmony"], None, (batch.track_ptr.shape[0] - 1) // 4, batch.n_bars)
     mu, log_var, graph = _encode(vae, batch)
     z = mu
     if strength != 0:
@@ -663,7 +833,8 @@ def vary_song(vae, song, strength=1.0, keep_structure=False, seed=None, **genera
     """Variations of whole songs: `song` is cut into windows of the model's W bars, the windows go through `vary_notes`
     as one batch (its arguments, `strength=0` is the reconstruction) and come back behind each other (`NoteBatch.join`) as a
     NoteBatch of B songs of W ceil(n_bars / W) bars.  Cutting and joining happen on the device and read nothing back, so
-    the host reads are those of `vary_notes`."""
+    the host reads are those of `vary_notes`.  A `harmony=` spans the song's bars ([n_bars,S] or [B,n_bars,S] with the song's
+    n_bars) and is cut into the windows with it; the bars a last window has beyond the song's end are free."""
     for k in ("return_tokens", "return_z"):
         if k in generate_notes_kwargs:
             raise ValueError(f"{k} is not an argument of vary_song: the windows' tokens and latents are not kept")
@@ -671,8 +842,15 @@ def vary_song(vae, song, strength=1.0, keep_structure=False, seed=None, **genera
         raise ValueError(f"song must be a NoteBatch, got {type(song).__name__}")
     if not (ops._real(strength) and np.isfinite(strength) and strength >= 0):
         raise ValueError(f"strength must be a finite number >= 0, got {strength!r}")
+    kw = dict(generate_notes_kwargs)
+    if kw.get("harmony") is not None:                            # over the song's bars: cut into the windows
+        h = kw["harmony"]
+        if not (ops._integer(song.n_bars) and song.n_bars >= 1):
+            raise ValueError(f"song.n_bars must be an int >= 1, got {song.n_bars!r}")
+        _check_harmony(h, None, (song.track_ptr.shape[0] - 1) // 4, song.n_bars)
+        kw["harmony"] = h.windows((song.track_ptr.shape[0] - 1) // 4, vae.cfg["n_bars"])
     wins, B, S = _song_windows(vae, song)
-    varied = vary_notes(vae, wins, strength, keep_structure, seed, **generate_notes_kwargs)[0]
+    varied = vary_notes(vae, wins, strength, keep_structure, seed, **kw)[0]
     index = torch.arange(B * S, dtype=torch.int32, device=varied.notes.device).view(B, S)
     return varied.join(index, check=False)
 
@@ -727,7 +905,9 @@ def infill_notes(vae, batch, region, strength=0.0, keep_structure=False, seed=No
 
     Decoding: the content decoder runs on the merged structure's bar graphs and the tokens of every node are drawn in the
     mode the keywords select, with `generate_notes`' arguments and checks (unsampled = arg-max, `temperature` / `top_k` /
-    `top_p`, `chord_rules`); `ops.infill_tokens` puts the kept cells' tokens back and `ops.notes_from_tokens` reads the piece.
+    `top_p`, `chord_rules`, `harmony`); `ops.infill_tokens` puts the kept cells' tokens back and `ops.notes_from_tokens` reads the
+    piece, so a harmony acts on the region only: `harmony=batch.harmony(tracks=...)` makes the new part follow what the kept
+    tracks play.
     The decoder is not autoregressive: given z and the bar graph the regenerated cells do not depend on the kept notes.
     `s_cond` / `s_tensor_cond` are rejected as in `vary_notes`.
 
@@ -747,7 +927,7 @@ def infill_notes(vae, batch, region, strength=0.0, keep_structure=False, seed=No
             raise ValueError(f"{k} is not an argument of infill_notes: keep_structure=True keeps the input's structure")
     temperature, top_k, top_p = kw.pop("temperature", None), kw.pop("top_k", None), kw.pop("top_p", None)
     chord_rules, structure_rules = kw.pop("chord_rules", None), kw.pop("structure_rules", None)
-    return_tokens = kw.pop("return_tokens", False)
+    return_tokens, harmony = kw.pop("return_tokens", False), kw.pop("harmony", None)
     if kw:
         raise TypeError(f"infill_notes got an unexpected keyword argument {sorted(kw)[0]!r}")
     if keep_structure and structure_rules is not None:
@@ -755,6 +935,7 @@ def infill_notes(vae, batch, region, strength=0.0, keep_structure=False, seed=No
     _check_batch(vae, batch)
     B, n_bars = (batch.track_ptr.shape[0] - 1) // 4, batch.n_bars
     region = ops.check_region(region, B, n_bars)
+    chord_rules = _check_harmony(harmony, chord_rules, B, n_bars)
     sampled = _check_draw(None, None, temperature, top_k, top_p, seed, chord_rules, structure_rules)
     mu, log_var, graph = _encode(vae, batch)
     z = mu
@@ -773,7 +954,8 @@ def infill_notes(vae, batch, region, strength=0.0, keep_structure=False, seed=No
         merged = vae.decoder._structure_from_binary(s_bool)      # (no bar is empty: the structure stays as merged)
     s_tensor = merged.s_tensor.view(B, n_bars, 4, 32).bool()
     _, c_logits = vae.decoder(z, merged)
-    tokens, _, _ = _draw(c_logits.detach().contiguous().float(), s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules)
+    tokens, _, _ = _draw(c_logits.detach().contiguous().float(), s_tensor, sampled, temperature, top_k, top_p, seed, chord_rules,
+                         harmony=harmony)
     info = ops.infill_tokens(s_in, merged.s_tensor, region, graph.tokens, tokens, bar_forced)
     notes, track_ptr, totals = ops.notes_from_tokens(tokens, s_tensor)
     out = (NoteBatch(notes, track_ptr, totals, n_bars, batch.resolution), s_tensor)

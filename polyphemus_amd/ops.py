@@ -319,6 +319,28 @@ def node_tracks(s_tensor: torch.Tensor, N: int, check: bool = True) -> torch.Ten
     return out
 
 
+def node_cells(s_tensor: torch.Tensor, N: int, check: bool = True) -> torch.Tensor:
+    """`pm_node_cells` ("Harmony" in include/polyphemus_hip.h): int32 [N], the cell index 128 g + 32 track + step of every node
+    of the binary structure `s_tensor` ([...,4,32], any dtype; g counts the bars along the batch), nodes numbered in cell order
+    as in `node_tracks`: `(node_cells >> 5) & 3` is `node_tracks`.  Entries behind the active cells are 0.  `check` reads the
+    active-cell count back (one host sync) and raises when it differs from `N`."""
+    s, G, bn, npt = _structure_prologue(s_tensor, s_tensor.device, s_tensor.dim() >= 3, "s_tensor must be [...,4,32]")
+    if not s_tensor.is_cuda:
+        raise HipExtensionError(f"s_tensor lives on {s_tensor.device}: the HIP path needs device tensors (no CPU fallback)")
+    N = int(N)
+    if N < 0:
+        raise ValueError(f"N must be >= 0, got {N}")
+    out = torch.empty(N, dtype=I32, device=s.device)
+    if G == 0:
+        if check and N:
+            raise ValueError(f"shape mismatch: s_tensor has 0 active cells, {N} nodes asked for")
+        return out.zero_()
+    call("pm_node_cells", ptr(s), G, N, ptr(bn), ptr(npt), ptr(out) if N else None, stream())
+    if check:
+        _check_active(npt[G], N, f"{N} nodes asked for")
+    return out
+
+
 def notes_from_tokens(tokens: torch.Tensor, s_tensor: torch.Tensor, check: bool = True):
     """`pm_notes_from_tokens` ("Note events" in include/polyphemus_hip.h): the notes the reference's `muspy_from_mtp` reads out
     of `mtp_from_tokens(tokens, s_tensor)`, without the pianoroll.  `tokens` int32 [N,15,2], `s_tensor` [B,n_bars,4,32] of any
@@ -551,6 +573,28 @@ def note_stats(notes: torch.Tensor, track_ptr: torch.Tensor, n_bars: int, check:
     return track, pitch_class, onsets, sounding
 
 
+SEG_STEPS = (1, 2, 4, 8, 16, 32)                 # the segment lengths of a chromagram, and the sets per bar of a harmony
+
+
+def note_chroma(notes: torch.Tensor, track_ptr: torch.Tensor, n_bars: int, seg_steps: int = 32) -> torch.Tensor:
+    """`pm_note_chroma` ("Harmony" in include/polyphemus_hip.h): the chromagram of the pieces of the `NoteBatch` layout (`notes`
+    int32 [M,3], `track_ptr` int32 [4B+1], `n_bars` bars of 32 steps, at most 64), int32 [4B, S, 12] with S = 32 n_bars /
+    `seg_steps` (1, 2, 4, 8, 16 or 32): entry [track, s, c] counts the (note, step) pairs of pitch class c sounding in segment
+    s.  A row counts as in `note_stats` (a time inside the piece, the pitch clamped to 0..127, the duration to 1..96 and cut at
+    the piece's end).  One launch, nothing is read back; bit-identical from call to call."""
+    check_device = _note_batch_args(notes, track_ptr)
+    if not (_integer(n_bars) and 1 <= n_bars <= MAX_STAT_BARS):
+        raise ValueError(f"n_bars must be an int in [1, {MAX_STAT_BARS}], got {n_bars!r}")
+    if not (_integer(seg_steps) and seg_steps in SEG_STEPS):
+        raise ValueError(f"seg_steps must be one of {SEG_STEPS}, got {seg_steps!r}")
+    check_device()
+    notes, track_ptr, n_bars, seg_steps = notes.contiguous(), track_ptr.contiguous(), int(n_bars), int(seg_steps)
+    B, M = track_ptr.shape[0] // 4, notes.shape[0]
+    chroma = torch.empty(4 * B, 32 * n_bars // seg_steps, 12, dtype=I32, device=notes.device)
+    call("pm_note_chroma", ptr(notes) if M else None, ptr(track_ptr), B, M, n_bars, seg_steps, ptr(chroma), stream())
+    return chroma
+
+
 def notes_select(notes: torch.Tensor, track_ptr: torch.Tensor, index, check: bool = True):
     """`pm_notes_select` ("Note statistics" in include/polyphemus_hip.h): the pieces `index[0..K)` of the `NoteBatch` layout
     (`notes` int32 [M,3], `track_ptr` int32 [4B+1]), in that order, without leaving the device.  `index` is an int32 or int64
@@ -781,6 +825,95 @@ def sample_chords(c_logits: torch.Tensor, node_track: torch.Tensor, temperature=
                 rules.pitch_mask[k][w] = words[k][w]
         call("pm_sample_chords", ptr(c_logits), ptr(node_track), N, ctypes.addressof(rules), int(seed), ptr(tokens),
              ptr(note_count), stream())
+    return tokens, note_count
+
+
+TRACK_NAMES = ("Drums", "Bass", "Guitar", "Strings")            # constants.py:5
+
+
+def check_harmony_args(sets, tracks=("Bass", "Guitar", "Strings"), empty="free", B=None, n_bars=None):
+    """The argument rules of a harmony (`generate.Harmony`, `sample_chords_at`): raises ValueError naming the argument, before
+    anything touches the device.  `sets` is an int tensor or array-like [n_bars,S] (shared by all pieces) or [B,n_bars,S] with
+    S in {1, 2, 4, 8, 16, 32} sets per bar and values in [0, 4096): bit c set = pitch class c may sound.  The values of a host
+    array or CPU tensor are checked; a device tensor is not read (the sampler ignores the bits above 11).  `tracks` holds
+    names from TRACK_NAMES or indices 0..3, `empty` is "free" or "rest"; `B` and `n_bars`, when given, are what the sets must
+    fit.  Returns (sets as an integer tensor on the device it came from, track_bits)."""
+    if empty not in ("free", "rest"):
+        raise ValueError(f"empty must be 'free' or 'rest', got {empty!r}")
+    if isinstance(tracks, (str, bytes)) or not isinstance(tracks, (list, tuple, set, frozenset)):
+        raise ValueError(f"tracks must be a list of names from {TRACK_NAMES} or indices 0..3, got {tracks!r}")
+    track_bits = 0
+    for k in tracks:
+        if isinstance(k, str) and k in TRACK_NAMES:
+            k = TRACK_NAMES.index(k)
+        if not (_integer(k) and 0 <= k < 4):
+            raise ValueError(f"tracks must hold names from {TRACK_NAMES} or indices 0..3, got {k!r}")
+        track_bits |= 1 << int(k)
+    if isinstance(sets, torch.Tensor):
+        t = sets
+        if t.dtype not in (torch.uint8, torch.int8, torch.int16, I32, I64):
+            raise ValueError(f"sets must hold integers, got {t.dtype}")
+    else:
+        try:
+            a = np.asarray(sets)
+        except Exception as e:
+            raise ValueError(f"sets must be an int tensor or array-like, got {type(sets).__name__}") from e
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"sets must hold integers, got {a.dtype}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= 4096):            # (before the cast can wrap)
+            raise ValueError(f"sets must hold values in [0, 4096), got {int(a.min())} .. {int(a.max())}")
+        t = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64)))
+    if t.dim() not in (2, 3) or 0 in t.shape or t.shape[-1] not in SEG_STEPS:
+        raise ValueError(f"sets must be [n_bars,S] or [B,n_bars,S] with S in {SEG_STEPS}, got {tuple(t.shape)}")
+    if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) >= 4096):
+        raise ValueError(f"sets must hold values in [0, 4096), got {int(t.min())} .. {int(t.max())}")
+    if n_bars is not None and t.shape[-2] != n_bars:
+        raise ValueError(f"harmony: sets hold {t.shape[-2]} bars, the call has n_bars = {n_bars}")
+    if B is not None and t.dim() == 3 and t.shape[0] != B:
+        raise ValueError(f"harmony: sets hold {t.shape[0]} pieces, the call has B = {B}")
+    return t, track_bits
+
+
+def sample_chords_at(c_logits: torch.Tensor, node_cell: torch.Tensor, chart: torch.Tensor, track_bits: int = 0b1110,
+                     temperature=1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0, min_notes=1,
+                     max_notes=14, allowed_pitches=None):
+    """`pm_sample_chords_at` ("Harmony" in include/polyphemus_hip.h): `sample_chords` under a chart of pitch-class sets.
+    `node_cell` is int32 [N] (see `node_cells`: the track, bar and step of every node), `chart` int32 [G,32] on the device of
+    `c_logits`: bits 0..11 of chart[g][t] are the pitch classes that may be drawn at step t of bar g by the tracks whose bit
+    is set in `track_bits` (bit k = track k; the default binds Bass, Guitar and Strings).  A pitch of a bound track must be
+    allowed by `allowed_pitches` and by its cell's set; a set that leaves none gives an empty chord, whatever `min_notes`
+    says.  Everything else, the noise stream included, is `sample_chords`: with `track_bits` 0 or every set 0xfff the result
+    is its result bit for bit.  Returns (tokens int32 [N,15,2], note_count int32 [N])."""
+    from ._lib import PmChordRules
+    _chk(c_logits, F32, "c_logits")
+    if c_logits.dim() != 3 or c_logits.shape[1:] != (C.MAX_SIMU_TOKENS - 1, C.D_TOKEN_PAIR):
+        raise ValueError("c_logits must be [N,15,230]")
+    temps, mn, mx, words = check_chord_args(temperature, top_k, top_p, seed, min_notes, max_notes, allowed_pitches)
+    N = c_logits.shape[0]
+    if not isinstance(node_cell, torch.Tensor) or node_cell.dtype != I32 or node_cell.dim() != 1 or not node_cell.is_contiguous():
+        raise ValueError("node_cell must be a contiguous int32 tensor [N]")
+    if node_cell.shape[0] != N or node_cell.device != c_logits.device:
+        raise ValueError(f"node_cell must be int32 [N = {N}] on {c_logits.device}, got [{node_cell.shape[0]}] on {node_cell.device}")
+    if (not isinstance(chart, torch.Tensor) or chart.dtype != I32 or chart.dim() != 2 or chart.shape[0] < 1 or chart.shape[1] != 32
+            or not chart.is_contiguous()):
+        raise ValueError("chart must be a contiguous int32 tensor [G,32] with G >= 1")
+    if chart.device != c_logits.device:
+        raise ValueError(f"chart lives on {chart.device}, c_logits on {c_logits.device}")
+    if not (_integer(track_bits) and 0 <= track_bits <= 15):
+        raise ValueError(f"track_bits must be an int in [0, 15], got {track_bits!r}")
+    tokens = torch.empty(N, C.MAX_SIMU_TOKENS - 1, 2, dtype=I32, device=c_logits.device)
+    note_count = torch.empty(N, dtype=I32, device=c_logits.device)
+    if N:
+        rules = PmChordRules()
+        rules.temperature[0], rules.temperature[1] = temps
+        rules.top_k = 0 if top_k is None else min(int(top_k), 1 << 30)
+        rules.top_p = 1.0 if top_p is None else float(top_p)
+        for k in range(4):
+            rules.min_notes[k], rules.max_notes[k] = mn[k], mx[k]
+            for w in range(4):
+                rules.pitch_mask[k][w] = words[k][w]
+        call("pm_sample_chords_at", ptr(c_logits), ptr(node_cell), N, ptr(chart), chart.shape[0], int(track_bits),
+             ctypes.addressof(rules), int(seed), ptr(tokens), ptr(note_count), stream())
     return tokens, note_count
 
 
