@@ -69,7 +69,8 @@ enum { PM_N_REL = 6, PM_N_DIST = 32, PM_N_SLOTS = 15, PM_N_PITCH = 131, PM_N_DUR
  *   PmChordRules struct); structure sampling (pm_sample_structure; the PmStructureRules struct); note events
  *   (pm_notes_from_tokens); the GCL self block without its round trip (pm_gcl_forward_fused_sel / _sel_h2,
  *   pm_gcl_weight_grad_fused_x / _x_h2: new entry points, no existing argument list changed); harmony (pm_node_cells,
- *   pm_sample_chords_at, pm_note_chroma). */
+ *   pm_sample_chords_at, pm_note_chroma); the resident data set (pm_dataset_pack_count, pm_dataset_pack_rows,
+ *   pm_dataset_gather). */
 #define PM_ABI_VERSION 9
 int pm_abi_version(void);
 const char* pm_build_info(void);
@@ -203,6 +204,56 @@ int pm_binary_from_logits(const float* s_logits /* [G,4,32] */, int32_t G, float
 int pm_mtp_from_logits(const float* c_logits /* [N,15,230] */, const float* s_tensor /* [G,4,32] 0/1 */, int32_t G,
                        int64_t N, int32_t* bar_nodes /* [G] */, int32_t* node_ptr /* [G+1] */,
                        float* mtp /* [G,4,32,15,230] */, pm_stream_t stream);
+
+/* ------------------------------------------------------------------ Resident data set
+ * A whole data set kept on the device in compact form, and batches gathered from it by index.  Replaces what the reference
+ * does per sample, per batch and per epoch on the host: `PolyphemusDataset.__getitem__` opening one `.npz` and re-laying
+ * the dense token grid out bar by bar (data.py:218-233), and the random transposition that preprocessing bakes into the
+ * files once (preprocess.py:196-205), which a resident set draws afresh for every batch.  Additive, same ABI version.
+ *
+ * The store of n samples of n_bars bars (1 <= n_bars <= 64):
+ *   s_bits   [n, n_bars, 4] uint32  bit t of word (bar, track): cell (track, t) of the bar is active; a bar without an active
+ *                                   cell has cell [0,0] (data.py:148-153).
+ *   rows     [R, 16, 2] uint8       the token rows (pitch id < 131, duration id < 99) of the active cells of all samples, in
+ *                                   the order pm_graph_emit numbers nodes in: (sample, bar, track, step).
+ *   cell_ptr [n + 1] int64          the rows of sample i are rows[cell_ptr[i] : cell_ptr[i + 1]].
+ *
+ * pm_dataset_pack_count (data.py:218-233): a chunk of n samples in the layout the reference's __getitem__ produces,
+ *   token_grid int16 [n, n_bars, 4, 32, 16, 2] and s_grid uint8 [n, n_bars, 4, 32] (non-zero = active), becomes s_bits
+ *   [n, n_bars, 4], cells [n] (active cells per sample, the empty-bar cell included) and last_slot [n] (the last of the
+ *   slots 1..15 that holds a non-PAD pitch or duration in an active cell, 0: none).  status [1], zeroed by the caller, gains
+ *   the number of token ids of active cells outside [0, 131) / [0, 99).  One launch, a workgroup per sample.
+ * pm_dataset_pack_rows (data.py:218-233): the byte rows of the chunk's active cells, written at rows[row_base + cell_off[i]
+ *   + r] for cell r of sample i; cell_off [n + 1] int64 is the exclusive scan of `cells` inside the chunk, row_base the
+ *   64-bit row at which the chunk starts and R the rows the buffer holds.  Nothing is written at or beyond row R nor beyond
+ *   a sample's span of cell_off.  Ids are cut to their low byte (pm_dataset_pack_count has counted those that do not fit).
+ * pm_dataset_gather (data.py:218-233, preprocess.py:196-205): batch entry j < B is sample index[j]; in ONE launch, a
+ *   workgroup per entry, s_tensor [B n_bars, 4, 32] fp32 0/1 is expanded from the masks and the entry's rows are widened to
+ *   tokens [N, 16, 2] int32 at row out_ptr[j].  out_ptr [B + 1] int32 is the caller's exclusive scan of the entries' cells
+ *   (host arithmetic on the counts of pm_dataset_pack_count): no device scan, nothing to read back.  An entry is followed
+ *   iff 0 <= index[j] < n and out_ptr[j + 1] - out_ptr[j] equals both cell_ptr's span of the sample and the cells of its
+ *   masks, with 0 <= out_ptr[j], out_ptr[j + 1] <= N, 0 <= cell_ptr[i] and cell_ptr[i + 1] <= R.  Any other gets a structure
+ *   of zeros and no row and is counted in status [2], zeroed by the caller: [0] indices outside [0, n), [1] spans that do
+ *   not match.  No row at or beyond N is written, whatever the inputs hold.  Entries may repeat.
+ *   transpose  NULL or [B] int32 semitones: on tracks 1..3 (never the drums) a pitch id <= 127 (not SOS, EOS or PAD) of
+ *              entry j becomes clamp(id + transpose[j], 0, 127); durations are untouched.  The caller keeps |shift| <= 127.
+ * The only atomics are the status counters.  Per batch 32 B are read and 128 B written per row, 16 B read and 512 B written
+ * per bar.
+ * PM_E_INVALID (before any launch): a NULL pointer (transpose may be NULL); n < 1, B < 1, N < 1, R < 1, row_base < 0 or
+ *   >= R; n_bars outside [1, 64]; 128 n n_bars (pack) or 128 B n_bars (gather) >= 2^31; n (gather) or N >= 2^31; N above
+ *   128 B n_bars; R above 2^40; token_grid, rows, s_tensor or tokens not 16-byte aligned, cell_off / cell_ptr not
+ *   8-byte aligned, any other pointer but s_grid not 4-byte aligned; an output overlapping any other buffer. */
+int pm_dataset_pack_count(const int16_t* token_grid /* [n,n_bars,4,32,16,2] */, const uint8_t* s_grid /* [n,n_bars,4,32] */,
+                          int64_t n, int32_t n_bars, uint32_t* s_bits /* [n,n_bars,4] */, int32_t* cells /* [n] */,
+                          int32_t* last_slot /* [n] */, int32_t* status /* [1] */, pm_stream_t stream);
+int pm_dataset_pack_rows(const int16_t* token_grid /* [n,n_bars,4,32,16,2] */, const uint32_t* s_bits /* [n,n_bars,4] */,
+                         const int64_t* cell_off /* [n+1] */, int64_t n, int32_t n_bars, uint8_t* rows /* [R,16,2] */,
+                         int64_t row_base, int64_t R, pm_stream_t stream);
+int pm_dataset_gather(const uint32_t* s_bits /* [n,n_bars,4] */, const uint8_t* rows /* [R,16,2] */,
+                      const int64_t* cell_ptr /* [n+1] */, int64_t n, int32_t n_bars, int64_t R,
+                      const int32_t* index /* [B] */, const int32_t* out_ptr /* [B+1] */,
+                      const int32_t* transpose /* [B] or NULL */, int32_t B, int64_t N, float* s_tensor /* [B n_bars,4,32] */,
+                      int32_t* tokens /* [N,16,2] */, int32_t* status /* [2] */, pm_stream_t stream);
 
 /* ------------------------------------------------------------------ sampled generation
  * No line of the reference stands behind these entries: its `muspy_from_mtp` (utils.py:103-105) takes the arg-max of every

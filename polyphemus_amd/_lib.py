@@ -197,6 +197,9 @@ _SIGS = {
     "pm_node_cells": "pilppps",
     "pm_sample_chords_at": "pplpiipupps",
     "pm_note_chroma": "ppiliips",
+    "pm_dataset_pack_count": "pplipppps",
+    "pm_dataset_pack_rows": "pppliplls",
+    "pm_dataset_gather": "ppplilpppilppps",
 }
 _CT = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "f": C.c_float, "u": C.c_uint32, "s": C.c_void_p, "D": C.c_double}
 _RET64 = {"pm_vae_step_workspace_bytes", "pm_vae_layout_bytes", "pm_vae_step_state_bytes", "pm_unembed_scratch_bytes",

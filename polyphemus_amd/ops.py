@@ -156,10 +156,14 @@ def edge_table_bwd(dT, d_nn_weight, d_nn_bias):
     call("pm_edge_table_bwd", ptr(dT), dT.shape[1], ptr(d_nn_weight), ptr(d_nn_bias), stream())
 
 
-def graph_build(s_tensor: torch.Tensor, n_bars: int):
+def graph_build(s_tensor: torch.Tensor, n_bars: int, sizes=None):
     """Bar graphs of a batch on the device (`pm_graph_count` + `pm_graph_emit`): `s_tensor` float32 [G,4,32] 0/1
     (empty bars get cell [0,0] switched on in place, data.py:152-153).  Returns a dict of device tensors with the
-    reference's node numbering and edge order; ONE host read (N, E) sizes the outputs."""
+    reference's node numbering and edge order; ONE host read (N, E) sizes the outputs.  A caller that knows the totals
+    passes `sizes=(N, E)`: they are trusted, nothing is read back, and the device's own totals come along as `totals`
+    (int32 [2]) for a later comparison (`ResidentDataset.batch`, whose counts are host arithmetic)."""
+    if sizes is not None and not (isinstance(sizes, (tuple, list)) and len(sizes) == 2 and all(_integer(v) and 1 <= v < (1 << 31) for v in sizes)):
+        raise ValueError(f"sizes must be None or two ints (N, E) in [1, 2^31), got {sizes!r}")
     _chk(s_tensor, F32, "s_tensor")
     G = s_tensor.shape[0]
     dev = s_tensor.device
@@ -167,7 +171,10 @@ def graph_build(s_tensor: torch.Tensor, n_bars: int):
     npt, ept = torch.empty(G + 1, dtype=I32, device=dev), torch.empty(G + 1, dtype=I32, device=dev)
     tot = torch.empty(2, dtype=I32, device=dev)
     call("pm_graph_count", ptr(s_tensor), G, ptr(bn), ptr(be), ptr(npt), ptr(ept), ptr(tot), stream())
-    N, E = (int(v) for v in tot.tolist())
+    if sizes is None:
+        N, E = (int(v) for v in tot.tolist())
+    else:
+        N, E = int(sizes[0]), int(sizes[1])
     out = dict(edge_index=torch.empty(2, E, dtype=I64, device=dev), edge_type=torch.empty(E, dtype=I32, device=dev),
                edge_dist=torch.empty(E, dtype=I32, device=dev), bars=torch.empty(N, dtype=I64, device=dev),
                batch=torch.empty(N, dtype=I64, device=dev), is_drum=torch.empty(N, dtype=U8, device=dev),
@@ -175,7 +182,125 @@ def graph_build(s_tensor: torch.Tensor, n_bars: int):
     call("pm_graph_emit", ptr(s_tensor), G, n_bars, ptr(npt), ptr(ept), N, E, ptr(out["edge_index"]), ptr(out["edge_type"]),
          ptr(out["edge_dist"]), ptr(out["bars"]), ptr(out["batch"]), ptr(out["is_drum"]), ptr(out["node_cell"]), stream())
     out["is_drum"] = out["is_drum"].view(torch.bool)
+    if sizes is not None:
+        out["totals"] = tot
     return out
+
+
+def _dataset_store_args(s_bits, rows, cell_ptr, n_bars):
+    """The checks the readers of the resident store share: `s_bits` int32 [n,n_bars,4] (the bits of the ABI's uint32 words),
+    `rows` uint8 [R,16,2], `cell_ptr` int64 [n+1] (ValueError); returns (n, R)."""
+    for t, name in ((s_bits, "s_bits"), (rows, "rows"), (cell_ptr, "cell_ptr")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if not (_integer(n_bars) and 1 <= n_bars <= MAX_DATASET_BARS):
+        raise ValueError(f"n_bars must be an int in [1, {MAX_DATASET_BARS}], got {n_bars!r}")
+    if s_bits.dtype != I32 or s_bits.dim() != 3 or s_bits.shape[0] < 1 or tuple(s_bits.shape[1:]) != (n_bars, 4):
+        raise ValueError(f"s_bits must be int32 [n,{n_bars},4] with n >= 1, got {s_bits.dtype} {tuple(s_bits.shape)}")
+    if rows.dtype != U8 or rows.dim() != 3 or rows.shape[0] < 1 or tuple(rows.shape[1:]) != (C.MAX_SIMU_TOKENS, 2):
+        raise ValueError(f"rows must be uint8 [R,16,2] with R >= 1, got {rows.dtype} {tuple(rows.shape)}")
+    n = s_bits.shape[0]
+    if cell_ptr.dtype != I64 or tuple(cell_ptr.shape) != (n + 1,):
+        raise ValueError(f"cell_ptr must be int64 [n + 1 = {n + 1}], got {cell_ptr.dtype} {tuple(cell_ptr.shape)}")
+    return n, rows.shape[0]
+
+
+MAX_DATASET_BARS = 64
+
+
+def dataset_pack(token_grid: torch.Tensor, s_grid: torch.Tensor, rows: Optional[torch.Tensor] = None, row_base: int = 0):
+    """`pm_dataset_pack_count` + `pm_dataset_pack_rows` ("Resident data set" in include/polyphemus_hip.h): a chunk of samples
+    in `PolyphemusDataset`'s layout, `token_grid` int16 [n,n_bars,4,32,16,2] and `s_grid` uint8 [n,n_bars,4,32], packed into
+    the compact store.  The chunk's rows go to `rows` (uint8 [capacity,16,2]) from row `row_base` on; a missing or too small
+    buffer is replaced by a larger one that keeps the rows in front of `row_base`.  Returns a dict: s_bits int32 [n,n_bars,4],
+    rows (the buffer written), cells / edges / last_slot (numpy int32 [n]: nodes, edges and last live token slot per sample;
+    the edges are `pm_graph_count`'s on the chunk's structure) and total (the chunk's rows).  ONE host read per chunk brings
+    the counts; token ids of active cells outside their ranges raise ValueError with their number.  Runs once per data set."""
+    for t, name in ((token_grid, "token_grid"), (s_grid, "s_grid")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if token_grid.dtype != torch.int16 or token_grid.dim() != 6 or token_grid.shape[0] < 1 or token_grid.shape[1] < 1 or \
+            tuple(token_grid.shape[2:]) != (C.N_TRACKS, C.N_TIMESTEPS, C.MAX_SIMU_TOKENS, 2):
+        raise ValueError(f"token_grid must be int16 [n,n_bars,4,32,16,2], got {token_grid.dtype} {tuple(token_grid.shape)}")
+    n, n_bars = int(token_grid.shape[0]), int(token_grid.shape[1])
+    if n_bars > MAX_DATASET_BARS:
+        raise ValueError(f"token_grid: n_bars must be at most {MAX_DATASET_BARS}, got {n_bars}")
+    if s_grid.dtype != U8 or tuple(s_grid.shape) != (n, n_bars, C.N_TRACKS, C.N_TIMESTEPS):
+        raise ValueError(f"s_grid must be uint8 [{n},{n_bars},4,32], got {s_grid.dtype} {tuple(s_grid.shape)}")
+    if 128 * n * n_bars > 0x7fffffff:
+        raise ValueError(f"token_grid: a chunk holds at most 2^31 cells, got n = {n} samples of {n_bars} bars")
+    if rows is not None and not (isinstance(rows, torch.Tensor) and rows.dtype == U8 and rows.dim() == 3
+                                 and tuple(rows.shape[1:]) == (C.MAX_SIMU_TOKENS, 2)):
+        raise ValueError("rows must be None or a uint8 tensor [capacity,16,2]")
+    if not (_integer(row_base) and 0 <= row_base <= (0 if rows is None else rows.shape[0])):
+        raise ValueError(f"row_base must be an int inside the rows buffer, got {row_base!r}")
+    _on_device([(token_grid, "token_grid"), (s_grid, "s_grid")] + ([(rows, "rows")] if rows is not None else []))
+    token_grid, s_grid, row_base, dev = token_grid.contiguous(), s_grid.contiguous(), int(row_base), token_grid.device
+    s_bits = torch.empty(n, n_bars, 4, dtype=I32, device=dev)
+    counts = torch.zeros(2 * n + 1, dtype=I32, device=dev)                         # cells, last_slot, status
+    call("pm_dataset_pack_count", ptr(token_grid), ptr(s_grid), n, n_bars, ptr(s_bits), ptr(counts), ptr(counts[n:]),
+         ptr(counts[2 * n:]), stream())
+    G = n * n_bars
+    s_f32 = s_grid.view(G, C.N_TRACKS, C.N_TIMESTEPS).to(F32)
+    bn, be = torch.empty(G, dtype=I32, device=dev), torch.empty(G, dtype=I32, device=dev)
+    scan = torch.empty(2 * G + 4, dtype=I32, device=dev)
+    call("pm_graph_count", ptr(s_f32), G, ptr(bn), ptr(be), ptr(scan), ptr(scan[G + 1:]), ptr(scan[2 * G + 2:]), stream())
+    host = torch.cat([counts, be.view(n, n_bars).sum(dim=1, dtype=I32)]).cpu().numpy()     # the one host read
+    cells, last_slot, bad, edges = host[:n], host[n:2 * n], int(host[2 * n]), host[2 * n + 1:]
+    if bad:
+        raise ValueError(f"token_grid: {bad} token ids of active cells outside their ranges (pitch [0, {C.N_PITCH_TOKENS}), "
+                         f"duration [0, {C.N_DUR_TOKENS}))")
+    cell_off = np.zeros(n + 1, np.int64)
+    np.cumsum(cells, out=cell_off[1:])
+    total = int(cell_off[-1])
+    if rows is None or rows.shape[0] < row_base + total:
+        grown = torch.empty(max(row_base + total, 2 * (0 if rows is None else rows.shape[0])), C.MAX_SIMU_TOKENS, 2, dtype=U8, device=dev)
+        if row_base:
+            grown[:row_base] = rows[:row_base]
+        rows = grown
+    elif not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    cell_off_d = torch.from_numpy(cell_off).to(dev)
+    call("pm_dataset_pack_rows", ptr(token_grid), ptr(s_bits), ptr(cell_off_d), n, n_bars, ptr(rows), row_base, rows.shape[0],
+         stream())
+    return dict(s_bits=s_bits, rows=rows, cells=cells.copy(), edges=edges.copy(), last_slot=last_slot.copy(), total=total)
+
+
+def dataset_gather(s_bits: torch.Tensor, rows: torch.Tensor, cell_ptr: torch.Tensor, n_bars: int, index: torch.Tensor,
+                   out_ptr: torch.Tensor, N: int, transpose: Optional[torch.Tensor] = None):
+    """`pm_dataset_gather` ("Resident data set" in include/polyphemus_hip.h): the batch whose entry j is sample `index[j]` of
+    the store (`s_bits` int32 [n,n_bars,4], `rows` uint8 [R,16,2], `cell_ptr` int64 [n+1]), in ONE launch.  `index` int32 [B]
+    and `out_ptr` int32 [B+1] (the entries' row offsets, `N` = out_ptr[B] rows in all) are device tensors the caller computed
+    on the host; `transpose` is None or int32 [B] semitones for the pitches of tracks 1..3.  Returns (s_tensor fp32
+    [B n_bars,4,32], tokens int32 [N,16,2], status int32 [2] = indices outside [0, n), spans that do not match the store).
+    An entry that is counted gets a structure of zeros and no rows; nothing is read back."""
+    _dataset_store_args(s_bits, rows, cell_ptr, n_bars)
+    if not isinstance(index, torch.Tensor) or index.dtype != I32 or index.dim() != 1 or index.shape[0] < 1:
+        raise ValueError("index must be an int32 tensor [B] with B >= 1, got "
+                         + (f"{index.dtype} {tuple(index.shape)}" if isinstance(index, torch.Tensor) else type(index).__name__))
+    B = index.shape[0]
+    if not isinstance(out_ptr, torch.Tensor) or out_ptr.dtype != I32 or tuple(out_ptr.shape) != (B + 1,):
+        raise ValueError(f"out_ptr must be an int32 tensor [B + 1 = {B + 1}], got "
+                         + (f"{out_ptr.dtype} {tuple(out_ptr.shape)}" if isinstance(out_ptr, torch.Tensor) else type(out_ptr).__name__))
+    if transpose is not None and not (isinstance(transpose, torch.Tensor) and transpose.dtype == I32 and tuple(transpose.shape) == (B,)):
+        raise ValueError(f"transpose must be None or an int32 tensor [B = {B}], got "
+                         + (f"{transpose.dtype} {tuple(transpose.shape)}" if isinstance(transpose, torch.Tensor) else type(transpose).__name__))
+    if not (_integer(N) and 1 <= N <= min(0x7fffffff, 128 * n_bars * B)):
+        raise ValueError(f"N must be an int in [1, 128 n_bars B = {128 * n_bars * B}] below 2^31, got {N!r}")
+    if 128 * n_bars * B > 0x7fffffff:
+        raise ValueError(f"index: a batch holds at most 2^31 cells, got B = {B} entries of {n_bars} bars")
+    named = [(s_bits, "s_bits"), (rows, "rows"), (cell_ptr, "cell_ptr"), (index, "index"), (out_ptr, "out_ptr")]
+    _on_device(named + ([(transpose, "transpose")] if transpose is not None else []))
+    for t, name in named + [(transpose, "transpose")]:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    dev, N, n_bars = s_bits.device, int(N), int(n_bars)
+    s = torch.empty(B * n_bars, C.N_TRACKS, C.N_TIMESTEPS, dtype=F32, device=dev)
+    tokens = torch.empty(N, C.MAX_SIMU_TOKENS, 2, dtype=I32, device=dev)
+    status = torch.zeros(2, dtype=I32, device=dev)
+    call("pm_dataset_gather", ptr(s_bits), ptr(rows), ptr(cell_ptr), s_bits.shape[0], n_bars, rows.shape[0], ptr(index),
+         ptr(out_ptr), ptr(transpose), B, N, ptr(s), ptr(tokens), ptr(status), stream())
+    return s, tokens, status
 
 
 def binary_from_logits(s_logits: torch.Tensor, thresh: float = 0.5) -> torch.Tensor:
